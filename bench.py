@@ -49,6 +49,9 @@ STRONG_REF = {   # (global elements per direction, p, dtype) -> (ms, source)
 
 TRAFFIC_FILE = 'profiles/traffic_r04.json'
 
+# --dump-outputs: bytes of x over all ranks (the whole dump stays under 64 MB)
+DUMP_X_BYTES = 32 << 20
+
 
 def kernel_source_hash():
   """sha256 over the kernel sources (csrc/*.h, *.hip, include/sfem.h): the
@@ -270,6 +273,12 @@ def main():
                        'one `value` is computed from; their ms per step go to '
                        'config.repeat_ms_per_step (box-to-box and run-to-run '
                        'spread of a 30 ms measurement)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='after the timed iterations (the --repeats batches '
+                       'included), write the CG iterate x (in the --dtype '
+                       'precision; a fixed seeded sample of positions where '
+                       'it exceeds 32 MB) and the residual r.r (float64) as '
+                       'DIR/<name>.npy, so that two builds can be compared')
   ap.add_argument('--dry-run', action='store_true',
                   help='rehearse launch, rendezvous, block build and one '
                        'interface exchange on CPU tensors (gloo) and print a '
@@ -361,6 +370,27 @@ def manufactured_solution(mesh, periodic):
   if periodic:
     xs = xs + torch.cos(k * x[:, 0])
   return xs
+
+
+def dump_outputs(directory, run, world, rank):
+  """Writes what the timed CG hands its caller (`linalg.cg.cg`) after the last
+  step: the iterate x as `x.npy` (`x_rank<r>.npy` per rank when N > 1) and
+  the residual r.r of its `info` as `residual.npy`.  An x larger than its
+  share of DUMP_X_BYTES is written at a fixed seeded sample of positions, in
+  increasing order, the same for every run with the same arguments."""
+  import torch
+  x = run.x.reshape(-1)
+  residual = run.info()['residual'].double().reshape(1).cpu().numpy()
+  keep = DUMP_X_BYTES // world // x.element_size()
+  if x.numel() > keep:
+    idx = np.sort(np.random.default_rng(rank).choice(x.numel(), keep,
+                                                     replace=False))
+    x = x[torch.from_numpy(idx).to(x.device)]
+  os.makedirs(directory, exist_ok=True)
+  name = 'x.npy' if world == 1 else 'x_rank%d.npy' % rank
+  np.save(os.path.join(directory, name), x.cpu().numpy())
+  if rank == 0:
+    np.save(os.path.join(directory, 'residual.npy'), residual)
 
 
 def rank_main(args, world, rank, device):
@@ -467,6 +497,8 @@ def rank_main(args, world, rank, device):
     if world > 1:
       tt = comm.all_reduce_max_(tt)
     repeat_ms.append(1e3 * float(tt.item()) / args.steps)
+  if args.dump_outputs:
+    dump_outputs(args.dump_outputs, run, world, rank)
 
   # ---- roofline of the dominant kernel: HIP events around ONE apply as the
   # solver issues it -- the fused kernel and whatever it needs around it (the

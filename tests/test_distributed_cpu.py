@@ -397,6 +397,33 @@ def test_bench_two_ranks_on_the_gpu_as_a_plain_command():
 
 
 @pytest.mark.gpu
+def test_bench_dumps_what_the_timed_solver_computed(tmp_path):
+  """`--dump-outputs DIR`: after `--steps` timed iterations the CG iterate x
+  and the residual r.r its caller would receive, the same in two runs with
+  the same arguments (the lazy x update of the 64^3 run included)."""
+  dumps = []
+  for k in range(2):
+    out = tmp_path / str(k)
+    res, line = _run_bench('--elems', '4', '--steps', '7', '--warmup', '2',
+                           '--repeats', '0', '--no-cpu-baseline',
+                           '--no-general', '--dump-outputs', str(out),
+                           SFEM_LAZY_X_MIN_MB='0')
+    assert res.returncode == 0, res.stderr[-2000:]
+    assert line['steps'] == 7 and line['ms_per_step'] > 0
+    assert line['config']['solver']['lazy_x'] is not None
+    assert sorted(os.listdir(out)) == ['residual.npy', 'x.npy']
+    x, rr = np.load(out / 'x.npy'), np.load(out / 'residual.npy')
+    assert x.dtype == np.float64 and x.shape == ((4 * 7 + 1) ** 3,)
+    assert rr.dtype == np.float64 and rr.shape == (1,)
+    assert np.abs(x).max() > 0 and 0 < rr[0] < np.inf
+    dumps.append((x, rr))
+  scale = np.abs(dumps[0][0]).max()
+  np.testing.assert_allclose(dumps[1][0], dumps[0][0], rtol=0,
+                             atol=1e-12 * scale)
+  np.testing.assert_allclose(dumps[1][1], dumps[0][1], rtol=1e-10)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize('flags,blocks', [
     (('--elems', '16'), '2x2x2'),
     (('--elems', '16', '--periodic'), '2x2x2'),
