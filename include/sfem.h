@@ -764,6 +764,66 @@ int sfem_ens_subtract_weighted_mean(const void* w, const void* b, double total,
                                     void* out, double* partials, int64_t len,
                                     int members, int dtype,
                                     sfem_stream_t stream);
+/* ------------------------------------------- Jacobi preconditioning ---
+ * sfem_helmholtz_diag: the element diagonals of the mass and stiffness parts
+ * of the operator sfem_helmholtz_apply / sfem_helmholtz_local apply, in the
+ * same form (G = w detJ J^-1 J^-T and W = w detJ, stored per point for
+ * SFEM_GEO_POINT elements -- geo, geo_index as in sfem_helmholtz_args -- or
+ * evaluated from the (E, 24) multilinear coefficients geo_elem for
+ * SFEM_GEO_AFFINE / SFEM_GEO_MULTILINEAR elements at the quadrature `nodes`).
+ * Node i = (i0, i1[, i2]) of element e, axis 0 slowest:
+ *   mass_out[e, i]  = sum_q W(q) prod_c B(q_c, i_c)^2
+ *   stiff_out[e, i] = sum_q sum_ab G_ab(q) g_a(q) g_b(q),
+ *                     g_a = prod_c (c == a ? Dt(q_c, i_c) : B(q_c, i_c))
+ * with B = bmat, the (Q, P) interpolation from the P nodes to the Q
+ * quadrature points, and Dt = dtil its derivative (Q, P) (D_q B).  bmat = NULL:
+ * collocated (Q = P, B = I, dtil = the nodal differentiation matrix).  Only
+ * the listed elements' rows are written.  Either output may be NULL.  All
+ * pointers are device pointers.                                            */
+typedef struct sfem_diag_args {
+  void* mass_out;           /* (E, P^d) or NULL                              */
+  void* stiff_out;          /* (E, P^d) or NULL                              */
+  const void* geo;          /* stored factors (SFEM_GEO_POINT) or NULL       */
+  const void* geo_elem;     /* (E, 24) multilinear coefficients or NULL      */
+  const int32_t* geo_index; /* (E,) slot of element in `geo`, or NULL        */
+  const int32_t* elem_list; /* (num_listed,) element ids, or NULL = all      */
+  const void* bmat;         /* (Q, P) or NULL (collocated)                   */
+  const void* dtil;         /* (Q, P)                                         */
+  const void* weights;      /* (Q,) 1D quadrature weights                    */
+  const void* nodes;        /* (Q,) 1D quadrature points in [-1, 1]          */
+  int64_t num_elements;
+  int64_t num_listed;
+  int ndim;                 /* 2 or 3                                         */
+  int P;                    /* 2..12                                          */
+  int Q;                    /* P..16 (ignored when collocated)                */
+  int dtype;
+  int geo_mode;             /* SFEM_GEO_POINT / _AFFINE / _MULTILINEAR        */
+} sfem_diag_args;
+int sfem_helmholtz_diag(const sfem_diag_args* args, sfem_stream_t stream);
+/* CG with M r = dinv (.) r folded into the two vector updates (z = M r is
+ * never stored), the Jacobi form of sfem_cg_update_r / sfem_cg_update_xp:
+ *   sfem_cg_update_r_jacobi : r -= alpha Ap;  gamma_new += r . (dinv (.) r)
+ *   sfem_cg_update_xp_jacobi: x += alpha p;   p = dinv (.) r + beta p
+ * `dinv`: (period,) shared by the `ncomp` components of a component-major
+ * field (component c at c * period; ncomp > 1 needs period to be a multiple
+ * of the 16-byte vector width).  update_r_jacobi takes Ap in the layered form
+ * of sfem_cg_update_r_layered (num_layers = 0: plain Ap; layers need
+ * ncomp = 1).  rz_partials = NULL: the r.z sums go to the striped slots of
+ * `scalars` (as sfem_cg_update_r with fuse_rr = 2); otherwise one STORED sum
+ * per workgroup (at most rz_capacity; *num_rz receives the count) for the
+ * fixed-order sum of sfem_cg_scalars_n phase 8 -- bitwise reproducible.   */
+int sfem_cg_update_r_jacobi(void* r, const void* ap_ext, const void* dinv,
+                            int64_t period, int ncomp,
+                            const int64_t* layer_len,
+                            const int64_t* layer_off, int num_layers,
+                            const uint8_t* layer_masks,
+                            const int64_t* mask_off, double* scalars,
+                            double* rz_partials, int64_t rz_capacity,
+                            int64_t* num_rz, int dtype, sfem_stream_t stream);
+int sfem_cg_update_xp_jacobi(void* x, void* p, const void* r,
+                             const void* dinv, int64_t period, int ncomp,
+                             double* scalars, int dtype,
+                             sfem_stream_t stream);
 /* y = a*x + b*y (plain fused vector update used outside the CG core)         */
 int sfem_axpby(double a, const void* x, double b, void* y, int64_t count,
                int dtype, sfem_stream_t stream);

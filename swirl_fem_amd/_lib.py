@@ -75,6 +75,17 @@ class StokesArgs(ctypes.Structure):
   ]
 
 
+class DiagArgs(ctypes.Structure):
+  """Mirror of `struct sfem_diag_args`."""
+  _fields_ = [
+      ('mass_out', c_ptr), ('stiff_out', c_ptr), ('geo', c_ptr),
+      ('geo_elem', c_ptr), ('geo_index', c_ptr), ('elem_list', c_ptr),
+      ('bmat', c_ptr), ('dtil', c_ptr), ('weights', c_ptr), ('nodes', c_ptr),
+      ('num_elements', c_i64), ('num_listed', c_i64), ('ndim', c_i32),
+      ('P', c_i32), ('Q', c_i32), ('dtype', c_i32), ('geo_mode', c_i32),
+  ]
+
+
 GEO_POINT, GEO_AFFINE, GEO_MULTILINEAR, GEO_BOX = 0, 1, 3, 5
 
 # name -> argument types (all functions return int unless noted)
@@ -169,6 +180,12 @@ SIGNATURES = {
     'sfem_cg_update_xp_mean': [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_dbl,
                                c_i32, c_ptr],
     'sfem_axpby': [c_dbl, c_ptr, c_dbl, c_ptr, c_i64, c_i32, c_ptr],
+    'sfem_helmholtz_diag': [ctypes.POINTER(DiagArgs), c_ptr],
+    'sfem_cg_update_r_jacobi': [c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_ptr,
+                                c_ptr, c_i32, c_ptr, c_ptr, c_ptr, c_ptr,
+                                c_i64, c_ptr, c_i32, c_ptr],
+    'sfem_cg_update_xp_jacobi': [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i32,
+                                 c_ptr, c_i32, c_ptr],
     'sfem_stokes_setup': [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_i32,
                           c_i32, c_ptr],
     'sfem_stokes_div': [c_ptr, c_ptr],

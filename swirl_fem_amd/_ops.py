@@ -1206,3 +1206,74 @@ def axpby(a, x, b, y):
         float(a), _ptr(x), float(b), _ptr(y), x.numel(), _dtype_code(x),
         _stream(dev)), 'sfem_axpby')
   return y
+
+
+# ------------------------------------------------------------------- Jacobi
+def helmholtz_diag(parts, num_elements, ndim, P, dtil, weights, nodes,
+                   bmat=None, want_mass=True, want_stiff=True, dtype=None,
+                   device=None):
+  """Element diagonals (E, P^d) of the mass and stiffness parts of the fused
+  operator described by `parts` (`sfem_helmholtz_diag`): `dtil` (Q, P) the
+  derivative of the nodal basis at the quadrature points, `weights`, `nodes`
+  (Q,) the quadrature rule, `bmat` (Q, P) the interpolation (None:
+  collocated).  Host arrays; returns (mass or None, stiffness or None)."""
+  n = P ** ndim
+  dev = torch.device(device)
+  mk = lambda a: None if a is None else torch.as_tensor(
+      np.ascontiguousarray(a), dtype=dtype, device=dev)
+  dt_d, w_d, x_d, b_d = mk(dtil), mk(weights), mk(nodes), mk(bmat)
+  Q = P if bmat is None else int(np.asarray(bmat).shape[0])
+  mass = (torch.zeros((num_elements, n), dtype=dtype, device=dev)
+          if want_mass else None)
+  stiff = (torch.zeros((num_elements, n), dtype=dtype, device=dev)
+           if want_stiff else None)
+  with torch.cuda.device(dev):
+    for part in parts:
+      lst = part.get('elem_list')
+      geo, geo_elem = part.get('geo'), part.get('geo_elem')
+      _dev(geo, geo_elem, lst, part.get('geo_index'), dt_d)
+      args = _lib.DiagArgs(
+          mass_out=_ptr(mass), stiff_out=_ptr(stiff), geo=_ptr(geo),
+          geo_elem=_ptr(geo_elem), geo_index=_ptr(part.get('geo_index')),
+          elem_list=_ptr(lst), bmat=_ptr(b_d), dtil=_ptr(dt_d),
+          weights=_ptr(w_d), nodes=_ptr(x_d), num_elements=num_elements,
+          num_listed=0 if lst is None else lst.numel(), ndim=ndim, P=P, Q=Q,
+          dtype=_DT[dtype], geo_mode=part['geo_mode'])
+      _lib.check(_lib.load().sfem_helmholtz_diag(ctypes.byref(args),
+                                                 _stream(dev)),
+                 'sfem_helmholtz_diag')
+  return mass, stiff
+
+
+def cg_update_r_jacobi(r, ap_ext, dinv, scalars, ncomp=1, layers=(),
+                       masks=None, rz_partials=None):
+  """r -= alpha Ap (assembled from its `layers`, if any); r . (dinv r) into the
+  striped slots of `scalars`, or as stored per-workgroup sums in `rz_partials`
+  (returns how many).  `r`, `ap_ext`: flat, `ncomp` components of
+  `dinv.numel()` values each."""
+  dev = _dev(r, ap_ext, dinv, scalars, rz_partials)
+  ln, off, n = _layer_arrays(list(layers))
+  mptr, moff = _mask_args(masks, n)
+  count = ctypes.c_int64(0)
+  if r.dtype != dinv.dtype:
+    raise TypeError('cg_update_r_jacobi: r and dinv must share the dtype')
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_cg_update_r_jacobi(
+        _ptr(r), _ptr(ap_ext), _ptr(dinv), dinv.numel(), int(ncomp), ln, off,
+        n, mptr, moff, _ptr(scalars), _ptr(rz_partials),
+        0 if rz_partials is None else rz_partials.numel(),
+        ctypes.byref(count), _dtype_code(r), _stream(dev)),
+        'sfem_cg_update_r_jacobi')
+  return count.value
+
+
+def cg_update_xp_jacobi(x, p, r, dinv, scalars, ncomp=1):
+  """x += alpha p;  p = dinv r + beta p  (flat, `ncomp` components)."""
+  dev = _dev(x, p, r, dinv, scalars)
+  if r.dtype != dinv.dtype:
+    raise TypeError('cg_update_xp_jacobi: r and dinv must share the dtype')
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_cg_update_xp_jacobi(
+        _ptr(x), _ptr(p), _ptr(r), _ptr(dinv), dinv.numel(), int(ncomp),
+        _ptr(scalars), _dtype_code(r), _stream(dev)),
+        'sfem_cg_update_xp_jacobi')

@@ -409,6 +409,8 @@ class HelmholtzOperator:
   facet_parts: list | None = None
   _vector_parts: list | None = None   # launches of vector fields (`_parts_for`)
   _layer_plan: object = None          # LayerPlan, False = none (`layer_plan`)
+  keep: torch.Tensor | None = None    # (N,) 1 inside, 0 on Dirichlet nodes
+  _diag: tuple | None = None          # assembled (diag B, diag A), `diagonal`
 
   @classmethod
   def create(cls, fespace, dirichlet_mask=None, geometry='auto',
@@ -534,7 +536,8 @@ class HelmholtzOperator:
     return cls(fespace=fespace, parts=parts, enc=enc, host=host,
                zero_range=zero_range, num_affine=counts[_GEO_AFFINE],
                num_multilinear=counts[_GEO_MULTILINEAR],
-               num_curved=counts[_GEO_POINT], facet_parts=facet_parts)
+               num_curved=counts[_GEO_POINT], facet_parts=facet_parts,
+               keep=None if mask is None else (mask == 0).to(fespace.dtype))
 
   def split(self, element_mask):
     """Two operators over the elements inside / outside `element_mask` (E,)
@@ -578,7 +581,8 @@ class HelmholtzOperator:
                else restrict(self.facet_parts, keep))
       # (each half covers part of the mesh only: no layer plan)
       halves.append(dataclasses.replace(self, parts=parts, facet_parts=facet,
-                                        _vector_parts=None, _layer_plan=False))
+                                        _vector_parts=None, _layer_plan=False,
+                                        _diag=None))
     return tuple(halves)
 
   def apply(self, u, lambda0=0.0, lambda1=1.0, out=None, *, zero=True,
@@ -683,6 +687,23 @@ class HelmholtzOperator:
             {k: v for k, v in q.items() if k != 'chains'}
             if q['geo_mode'] == _GEO_POINT else q for q in self.facet_parts]
     return self._vector_parts
+
+  def diagonal(self, lambda0=0.0, lambda1=1.0, assembled=True):
+    """The assembled diagonal (N,) of what `apply(u, lambda0, lambda1)`
+    computes: Dirichlet rows 0, shared nodes and periodic images summed as the
+    mesh's scatter sums them, and on a partitioned mesh summed over the
+    partitions by the exchange (`assembled=False`: this partition's share).
+    The element diagonals use the factors of the index-row launches: affine
+    / box elements evaluate G and W from their multilinear coefficients, as
+    the index-row kernels do, where the facet kernels read per-element
+    constants -- the same values up to rounding.  The mass and stiffness
+    parts are computed once per operator (`sfem_helmholtz_diag`) and combined
+    here."""
+    if self._diag is None:
+      self._diag = _assembled_diagonal(self.fespace, self.parts, self.host,
+                                       self.keep, None)
+    return _combine_diagonal(self._diag, lambda0, lambda1, assembled,
+                             self.fespace.mesh)
 
   def apply_local(self, u_local, lambda0=0.0, lambda1=1.0):
     """Element-local action (E, n[, nc]) -> (E, n[, nc]); no gather/scatter."""
@@ -1286,6 +1307,44 @@ def _like_layout(t, ref):
 # ---------------------------------------------------------------------------
 # Helmholtz operator with a quadrature that differs from the nodes
 # ---------------------------------------------------------------------------
+def _assembled_diagonal(fespace, parts, host, keep, bmat):
+  """(diag B, diag A) of a fused operator on this partition, (N,) each:
+  element diagonals from `sfem_helmholtz_diag`, summed per node in ascending
+  slot order by `sfem_scatter_csr` (deterministic: no atomics), Dirichlet
+  rows zeroed.  `bmat` (Q, P): the interpolation of a two-grid operator."""
+  mesh = fespace.mesh
+  P = mesh.gridpoints_1d.num_points
+  dq = np.asarray(host['dmat'], dtype=np.float64)
+  dtil = dq if bmat is None else dq @ bmat
+  mass, stiff = _ops.helmholtz_diag(
+      parts, mesh.num_elements, mesh.ndim, P, dtil, host['weights'],
+      host['nodes'], bmat, dtype=fespace.dtype, device=fespace.device)
+  offsets, slots = mesh.assembly_plan().csr()
+  out = []
+  for loc in (mass, stiff):
+    d = _ops.scatter_csr(loc.reshape(-1), offsets, slots, mesh.num_nodes)
+    if keep is not None:
+      d = d * keep
+    out.append(d)
+  return tuple(out)
+
+
+def _combine_diagonal(parts, lambda0, lambda1, assembled, mesh):
+  """lambda0 diag B + lambda1 diag A; summed over the partitions (the mesh's
+  exchange, a collective) when `assembled` and the mesh is partitioned."""
+  mass, stiff = parts
+  if lambda0 == 0.0:
+    d = stiff * lambda1
+  elif lambda1 == 0.0:
+    d = mass * lambda0
+  else:
+    d = mass * lambda0 + stiff * lambda1
+  if assembled and (mesh.axis_name is not None or
+                    mesh.neighbor_plan is not None):
+    d = mesh.exchange(d)
+  return d
+
+
 def supports_two_grid(fespace) -> str | None:
   """None if `TwoGridHelmholtzOperator` applies, else the reason."""
   mesh = fespace.mesh
@@ -1328,6 +1387,7 @@ class TwoGridHelmholtzOperator:
   parts: list
   host: dict
   mask: torch.Tensor | None        # (N,) 1 inside, 0 on Dirichlet nodes
+  _diag: tuple | None = None       # assembled (diag B, diag A), `diagonal`
 
   @classmethod
   def create(cls, fespace, dirichlet_mask=None,
@@ -1422,6 +1482,18 @@ class TwoGridHelmholtzOperator:
 
   def linear_operator(self, lambda0=0.0, lambda1=1.0):
     return lambda u: self.apply(u, lambda0, lambda1)
+
+  def diagonal(self, lambda0=0.0, lambda1=1.0, assembled=True):
+    """The assembled diagonal of `apply(u, lambda0, lambda1)` (N,), see
+    `HelmholtzOperator.diagonal`: the element diagonals of I^T H_q I with
+    I the (Q, P) interpolation and D_q I its derivative."""
+    if self._diag is None:
+      interp = self.fespace.interpolator
+      bmat = np.asarray(interp._interpolation_matrix_1d(), dtype=np.float64)
+      self._diag = _assembled_diagonal(self.fespace, self.parts, self.host,
+                                       self.mask, bmat)
+    return _combine_diagonal(self._diag, lambda0, lambda1, assembled,
+                             self.fespace.mesh)
 
 
 # ---------------------------------------------------------------------------

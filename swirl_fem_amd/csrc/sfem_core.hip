@@ -1031,6 +1031,141 @@ static void launch_update_r(int fuse_rr, bool nt, int grid, hipStream_t stream,
 #undef SFEM_UPDATE_R
 }
 
+// Jacobi preconditioner  M r = dinv (.) r  folded into the two updates (z is
+// never stored), for scalar fields and component-major fields of `ncomp`
+// components that share one (period,) diagonal:
+//   update_r_jacobi : r -= alpha Ap (Ap assembled from its layers, if any);
+//                     sums r . (dinv (.) r)          reads r, Ap, dinv; writes r
+//   update_xp_jacobi: x += alpha p;  p = dinv (.) r + beta p
+//                                                 reads x, p, r, dinv; writes x, p
+// dinv is read once per node for all components.  The sums of r.z go where
+// the fused r.r goes (striped slots, or stored per workgroup for the
+// fixed-order sum of phase 8).  Component c starts at c * period; with
+// ncomp > 1 the period is a multiple of the 16-byte vector width.
+template <typename T, bool NT, bool STORE>
+__global__ void __launch_bounds__(512)
+cg_update_r_jacobi_kernel(T* __restrict__ r, const T* __restrict__ ap,
+                          const T* __restrict__ dinv, int64_t period,
+                          int ncomp, LayerDesc ld,
+                          double* __restrict__ scalars,
+                          double* __restrict__ rz_partials) {
+  if (scalars[7] != 0.0) return;
+  using V = typename Vec16<T>::type;
+  constexpr int VN = Vec16<T>::N;
+  const T alpha = (T)(scalars[0] / scalars[1]);
+  const int64_t nvec = period / VN;
+  const V* dv = reinterpret_cast<const V*>(dinv);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  double acc = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
+       i += stride) {
+    const V dd = ld16<T, NT>(&dv[i]);
+    for (int c = 0; c < ncomp; ++c) {
+      V* rv = reinterpret_cast<V*>(r + c * period);
+      const T* apc = ap + c * period;
+      V rr = ld16<T, NT>(&rv[i]);
+      V aa = ld16<T, NT>(reinterpret_cast<const V*>(apc) + i);
+      if (c == 0) aa = add_layers<T, NT>(aa, ap, i, ld);
+#pragma unroll
+      for (int k = 0; k < VN; ++k) {
+        T* re = reinterpret_cast<T*>(&rr) + k;
+        *re -= alpha * vget<T>(aa, k);
+        acc += (double)*re * (double)vget<T>(dd, k) * (double)*re;
+      }
+      st16<T, NT>(rr, &rv[i]);
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x < period - nvec * VN) {
+    const int64_t i = nvec * VN + threadIdx.x;
+    const T d = dinv[i];
+    for (int c = 0; c < ncomp; ++c) {
+      const int64_t j = c * period + i;
+      T a = ap[j];
+      if (c == 0)
+        for (int k = 0; k < ld.nl; ++k)
+          if (i < ld.len[k]) a += ap[ld.off[k] + i];
+      const T rn = r[j] - alpha * a;
+      r[j] = rn;
+      acc += (double)rn * (double)d * (double)rn;
+    }
+  }
+  const double total = block_sum(acc);
+  if (threadIdx.x == 0) {
+    if (STORE)            // summed in index order by phase 8
+      rz_partials[blockIdx.x] = total;
+    else
+      unsafeAtomicAdd(&scalars[SFEM_CG_NSCALARS_NAMED +
+                               (blockIdx.x & (SFEM_CG_RR_SLOTS - 1))], total);
+  }
+}
+
+template <typename T, bool NT>
+__global__ void __launch_bounds__(512)
+cg_update_xp_jacobi_kernel(T* __restrict__ x, T* __restrict__ p,
+                           const T* __restrict__ r,
+                           const T* __restrict__ dinv, int64_t period,
+                           int ncomp, const double* __restrict__ scalars) {
+  if (scalars[7] != 0.0) return;
+  using V = typename Vec16<T>::type;
+  constexpr int VN = Vec16<T>::N;
+  const T alpha = (T)(scalars[0] / scalars[1]);
+  const T beta = (T)(cg_gamma_new(scalars) / scalars[0]);
+  const int64_t nvec = period / VN;
+  const V* dv = reinterpret_cast<const V*>(dinv);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
+       i += stride) {
+    const V dd = ld16<T, NT>(&dv[i]);
+    for (int c = 0; c < ncomp; ++c) {
+      V* xv = reinterpret_cast<V*>(x + c * period);
+      V* pv = reinterpret_cast<V*>(p + c * period);
+      const V* rv = reinterpret_cast<const V*>(r + c * period);
+      V xx = ld16<T, NT>(&xv[i]);
+      V pp = ld16<T, NT>(&pv[i]);
+      const V rr = ld16<T, NT>(&rv[i]);
+#pragma unroll
+      for (int k = 0; k < VN; ++k) {
+        T* xe = reinterpret_cast<T*>(&xx) + k;
+        T* pe = reinterpret_cast<T*>(&pp) + k;
+        *xe += alpha * *pe;
+        *pe = vget<T>(dd, k) * vget<T>(rr, k) + beta * *pe;
+      }
+      st16<T, NT>(xx, &xv[i]);
+      st16<T, NT>(pp, &pv[i]);
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x < period - nvec * VN) {
+    const int64_t i = nvec * VN + threadIdx.x;
+    const T d = dinv[i];
+    for (int c = 0; c < ncomp; ++c) {
+      const int64_t j = c * period + i;
+      const T pj = p[j];
+      x[j] += alpha * pj;
+      p[j] = d * r[j] + beta * pj;
+    }
+  }
+}
+
+template <typename T>
+static void launch_update_r_jacobi(bool nt, bool store, int grid,
+                                   hipStream_t st, T* r, const T* ap,
+                                   const T* dinv, int64_t period, int ncomp,
+                                   const LayerDesc& ld, double* scalars,
+                                   double* rz_partials) {
+#define SFEM_UPDATE_RJ(NTV, STV)                                            \
+  hipLaunchKernelGGL((cg_update_r_jacobi_kernel<T, NTV, STV>), dim3(grid),  \
+                     dim3(512), 0, st, r, ap, dinv, period, ncomp, ld,      \
+                     scalars, rz_partials)
+  if (store) {
+    if (nt) SFEM_UPDATE_RJ(true, true);
+    else SFEM_UPDATE_RJ(false, true);
+  } else {
+    if (nt) SFEM_UPDATE_RJ(true, false);
+    else SFEM_UPDATE_RJ(false, false);
+  }
+#undef SFEM_UPDATE_RJ
+}
+
 // One-thread bookkeeping between the vector kernels of an iteration.
 // phase 2 (init, after b.b -> [5] and gamma0 -> [0]):
 //     atol2 = max(tol^2 b.b, atol^2); clear pAp, iterations;
@@ -1705,6 +1840,70 @@ int sfem_cg_update_xp(void* x, void* p, const void* z, int64_t count,
                          dim3(stream_grid(count, 512 * 2)), dim3(512), 0,
                          as_stream(stream), (T*)x, (T*)p, (const T*)z, count,
                          scalars);
+  });
+  SFEM_LAUNCH_CHECK();
+  return SFEM_OK;
+}
+
+int sfem_cg_update_r_jacobi(void* r, const void* ap_ext, const void* dinv,
+                            int64_t period, int ncomp,
+                            const int64_t* layer_len,
+                            const int64_t* layer_off, int num_layers,
+                            const uint8_t* layer_masks,
+                            const int64_t* mask_off, double* scalars,
+                            double* rz_partials, int64_t rz_capacity,
+                            int64_t* num_rz, int dtype, sfem_stream_t stream) {
+  SFEM_REQUIRE(period >= 0 && ncomp >= 1 && scalars &&
+                   (!rz_partials || (num_rz && rz_capacity >= 1)),
+               "sfem_cg_update_r_jacobi: bad arguments");
+  SFEM_REQUIRE(dtype == SFEM_F32 || dtype == SFEM_F64,
+               "sfem_cg_update_r_jacobi: unknown dtype %d", dtype);
+  const int vn = dtype == SFEM_F64 ? 2 : 4;
+  SFEM_REQUIRE(ncomp == 1 || (period % vn == 0 && num_layers == 0),
+               "sfem_cg_update_r_jacobi: %d components need a period that is "
+               "a multiple of %d and no layers", ncomp, vn);
+  if (num_rz) *num_rz = 0;
+  if (period == 0) return SFEM_OK;
+  SFEM_REQUIRE(r && ap_ext && dinv, "sfem_cg_update_r_jacobi: null pointer");
+  LayerDesc ld;
+  const int rc = make_layer_desc("sfem_cg_update_r_jacobi", layer_len,
+                                 layer_off, num_layers, period, vn, &ld,
+                                 layer_masks, mask_off);
+  if (rc != SFEM_OK) return rc;
+  int grid = stream_grid(period, 512 * 2);
+  if (rz_partials && grid > rz_capacity) grid = (int)rz_capacity;
+  if (num_rz) *num_rz = rz_partials ? grid : 0;
+  DISPATCH_DTYPE(dtype, launch_update_r_jacobi<T>(
+      streams_past_caches(period * ncomp, sizeof(T)), rz_partials != nullptr,
+      grid, as_stream(stream), (T*)r, (const T*)ap_ext, (const T*)dinv,
+      period, ncomp, ld, scalars, rz_partials));
+  SFEM_LAUNCH_CHECK();
+  return SFEM_OK;
+}
+
+int sfem_cg_update_xp_jacobi(void* x, void* p, const void* r,
+                             const void* dinv, int64_t period, int ncomp,
+                             double* scalars, int dtype,
+                             sfem_stream_t stream) {
+  SFEM_REQUIRE(period >= 0 && ncomp >= 1 && scalars,
+               "sfem_cg_update_xp_jacobi: bad arguments");
+  SFEM_REQUIRE(dtype == SFEM_F32 || dtype == SFEM_F64,
+               "sfem_cg_update_xp_jacobi: unknown dtype %d", dtype);
+  SFEM_REQUIRE(ncomp == 1 || period % (dtype == SFEM_F64 ? 2 : 4) == 0,
+               "sfem_cg_update_xp_jacobi: %d components need a period that "
+               "is a multiple of the vector width", ncomp);
+  if (period == 0) return SFEM_OK;
+  SFEM_REQUIRE(x && p && r && dinv, "sfem_cg_update_xp_jacobi: null pointer");
+  DISPATCH_DTYPE(dtype, {
+    const unsigned grid = stream_grid(period, 512 * 2);
+    if (streams_past_caches(period * ncomp, sizeof(T)))
+      hipLaunchKernelGGL((cg_update_xp_jacobi_kernel<T, true>), dim3(grid),
+                         dim3(512), 0, as_stream(stream), (T*)x, (T*)p,
+                         (const T*)r, (const T*)dinv, period, ncomp, scalars);
+    else
+      hipLaunchKernelGGL((cg_update_xp_jacobi_kernel<T, false>), dim3(grid),
+                         dim3(512), 0, as_stream(stream), (T*)x, (T*)p,
+                         (const T*)r, (const T*)dinv, period, ncomp, scalars);
   });
   SFEM_LAUNCH_CHECK();
   return SFEM_OK;

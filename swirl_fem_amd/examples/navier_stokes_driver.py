@@ -104,7 +104,8 @@ def _histories(sem, u0, p0, time_order):
 def lid_driven_cavity(n=8, order=5, reynolds=100.0, dt=1e-3, steps=10,
                       time_order=3, device=None, premesh=None, tol=1e-8,
                       profile=None, pressure_projection=None,
-                      pressure_preconditioner=None):
+                      pressure_preconditioner=None,
+                      velocity_preconditioner=None):
   """2D lid-driven cavity on [0,1]^2; returns (sem, u, p, diagnostics)."""
   timer = _StepTimer(profile, device)
   pm = premesh if premesh is not None else unit_cube_mesh(n, ndim=2)
@@ -126,7 +127,8 @@ def lid_driven_cavity(n=8, order=5, reynolds=100.0, dt=1e-3, steps=10,
         sem, us, ps, Cus, reynolds=reynolds, dt=dt, time_order=time_order,
         u_boundary=u_b, tol=tol, atol=0.0,
         pressure_projection=pressure_projection,
-        pressure_preconditioner=pressure_preconditioner)
+        pressure_preconditioner=pressure_preconditioner,
+        velocity_preconditioner=velocity_preconditioner)
     us, ps, Cus = us[1:] + (u,), ps[1:] + (p,), Cus[1:] + (Cu,)
     timer.step_done()
     iters.append((aux['u_star_info']['num_iterations'],
@@ -140,7 +142,7 @@ def lid_driven_cavity(n=8, order=5, reynolds=100.0, dt=1e-3, steps=10,
 
 def taylor_green(n=4, order=3, reynolds=100.0, dt=1e-2, steps=5, time_order=3,
                  device=None, tol=1e-8, profile=None, pressure_projection=None,
-                 pressure_preconditioner=None):
+                 pressure_preconditioner=None, velocity_preconditioner=None):
   """3D Taylor-Green vortex on the periodic box [0, 2 pi]^3 (`n` elements
   per direction, or one count per direction)."""
   timer = _StepTimer(profile, device)
@@ -164,7 +166,8 @@ def taylor_green(n=4, order=3, reynolds=100.0, dt=1e-2, steps=5, time_order=3,
     u, p, Cu, aux = navier_stokes_step(
         sem, us, ps, Cus, reynolds=reynolds, dt=dt, time_order=time_order,
         tol=tol, atol=0.0, pressure_projection=pressure_projection,
-        pressure_preconditioner=pressure_preconditioner)
+        pressure_preconditioner=pressure_preconditioner,
+        velocity_preconditioner=velocity_preconditioner)
     us, ps, Cus = us[1:] + (u,), ps[1:] + (p,), Cus[1:] + (Cu,)
     timer.step_done()
     energy.append(float(0.5 * (w * u ** 2).sum()))
@@ -178,7 +181,8 @@ def taylor_green(n=4, order=3, reynolds=100.0, dt=1e-2, steps=5, time_order=3,
 def taylor_green_blocks(n=4, order=3, block_grid=(2, 2, 2), rank=None,
                         reynolds=100.0, dt=1e-2, steps=5, time_order=3,
                         device=None, tol=1e-8, profile=None,
-                        pressure_projection=None, pressure_preconditioner=None):
+                        pressure_projection=None, pressure_preconditioner=None,
+                        velocity_preconditioner=None):
   """BASELINE config 4: the 3D Taylor-Green vortex on the triply periodic box
   [0, 2 pi]^3, one `n^3`-element block per rank (`block_grid` ranks, launched
   with torch.distributed; 2 x 2 x 2 blocks of 64^3 elements are the 128^3
@@ -212,7 +216,8 @@ def taylor_green_blocks(n=4, order=3, block_grid=(2, 2, 2), rank=None,
     u, p, Cu, aux = navier_stokes_step(
         sem, us, ps, Cus, reynolds=reynolds, dt=dt, time_order=time_order,
         tol=tol, atol=0.0, pressure_projection=pressure_projection,
-        pressure_preconditioner=pressure_preconditioner)
+        pressure_preconditioner=pressure_preconditioner,
+        velocity_preconditioner=velocity_preconditioner)
     us, ps, Cus = us[1:] + (u,), ps[1:] + (p,), Cus[1:] + (Cu,)
     energy.append(float(sem._global_sum(0.5 * (w * u ** 2).sum().reshape(1))))
     iters.append((aux['u_star_info']['num_iterations'],

@@ -213,6 +213,43 @@ class _MassPreconditioner:
     return f * z
 
 
+class _JacobiVelocityPreconditioner(_MassPreconditioner):
+  """`z = (d_max / d) . QQ^T r` with d the exchanged diagonal of the stepper's
+  Helmholtz operator H = (beta / dt) B + mu A (`HelmholtzOperator.diagonal`,
+  the stiffness part included): the Jacobi preconditioner, opt-in like
+  'mass'.  d_max is the maximum over all partitions, so d_max / d >= 1 and the
+  stopping rule is at least as strict as the reference's; d is equal on the
+  copies of a node, so M commutes with QQ^T and is symmetric.  Zero on the
+  Dirichlet rows.  Where QQ^T is the identity (one partition, no periodic
+  images, one member) M is diagonal and offers `jacobi_diagonal()`: `cg`
+  then folds it into its vector updates (linalg/jacobi.py)."""
+
+  def __init__(self, sem, beta_dt, mu):
+    op = sem._masked_operator()
+    if op is None:
+      raise NotImplementedError(
+          "velocity_preconditioner='jacobi' needs the fused velocity operator")
+    dim = sem.velocity_mass_diag.shape[-1]
+    d1 = op.diagonal(float(beta_dt), float(mu), assembled=False)
+    d = sem.velocity.exchange(d1[:, None].expand(-1, dim).contiguous())
+    top = sem._global_sum_max(d.max().reshape(1))
+    inside = sem.velocity.interior_mask != 0
+    self.sem = sem
+    self.factor = torch.where(inside & (d != 0), top / torch.where(
+        d != 0, d, torch.ones_like(d)), torch.zeros_like(d))
+    self._laid_out = {}
+    mesh = sem.velocity.mesh
+    gi = mesh.exchange_gather_indices
+    identity = (gi is None or gi.numel() == 0 or (
+        mesh.axis_name is None and mesh.exchange_unique_indices is None))
+    self._dinv = (self.factor[:, 0].contiguous()
+                  if identity and mesh.neighbor_plan is None and
+                  sem.members == 1 else None)
+
+  def jacobi_diagonal(self):
+    return self._dinv
+
+
 class _SolutionProjection:
   """Successive right-hand sides (Fischer, "Projection techniques for
   iterative solution of A x = b with successive right-hand sides", Comput.
@@ -850,7 +887,9 @@ class StokesSEM:
 
     `velocity_preconditioner` (beyond the reference; None = the switch
     SFEM_VELOCITY_PC, default 'exchange' = the reference's M = QQ^T): 'mass'
-    (`_MassPreconditioner`) or a callable r -> z for the Helmholtz solve.
+    (`_MassPreconditioner`), 'jacobi' (`_JacobiVelocityPreconditioner`, the
+    inverse diagonal of (beta / dt) B + mu A, kept per (beta / dt, mu)) or a
+    callable r -> z for the Helmholtz solve.
 
     `pressure_projection` (beyond the reference; None = the switch
     SFEM_PRESSURE_PROJECTION, default 0 = off): number of earlier pressure
@@ -925,6 +964,11 @@ class StokesSEM:
       if 'velocity_mass_pc' not in self._cache:
         self._cache['velocity_mass_pc'] = _MassPreconditioner(self)
       M_v = self._cache['velocity_mass_pc']
+    elif vpc == 'jacobi':
+      key = ('velocity_jacobi_pc', beta_k / dt, float(mu))
+      if key not in self._cache:
+        self._cache[key] = _JacobiVelocityPreconditioner(self, beta_k / dt, mu)
+      M_v = self._cache[key]
     elif callable(vpc):
       M_v = vpc
     else:

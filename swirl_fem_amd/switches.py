@@ -92,6 +92,10 @@ SWITCHES = {
     'SFEM_FUSED_MEAN': ('1', 'linalg/cg.py',
                         '0: the mean projection of the pressure '
                         'preconditioner is applied as a separate kernel'),
+    'SFEM_FUSED_JACOBI': ('1', 'linalg/cg.py',
+                          '0: a Jacobi preconditioner (`linalg/jacobi.py`) is '
+                          'called as a function and z = M r stored, instead '
+                          'of being folded into the two CG vector updates'),
     'SFEM_GRAPHS': ('1', 'navier_stokes/navier_stokes.py',
                     '0: solver iterations are never replayed as HIP graphs'),
     'SFEM_GRAPH_REUSE': ('1', 'navier_stokes/navier_stokes.py',
@@ -109,7 +113,9 @@ SWITCHES = {
                          "preconditioner of the stepper's Helmholtz solve: "
                          "'exchange' (the reference's M = QQ^T) or 'mass' "
                          '(inverse assembled lumped mass, scaled so that the '
-                         "reference's stopping rule still holds)"),
+                         "reference's stopping rule still holds) or 'jacobi' "
+                         '(inverse assembled diagonal of the whole Helmholtz '
+                         'operator, same scaling)'),
     'SFEM_PC_FUSED': ('1', 'navier_stokes/pressure_preconditioner.py',
                       "0: the 'schwarz' preconditioner forms the element sums, "
                       'the coarse correction and the mean removal in separate '
