@@ -824,6 +824,64 @@ int sfem_cg_update_xp_jacobi(void* x, void* p, const void* r,
                              const void* dinv, int64_t period, int ncomp,
                              double* scalars, int dtype,
                              sfem_stream_t stream);
+/* ------------------------------------------------------- p-multigrid ---
+ * Transfers between two polynomial orders of the same elements
+ * (linalg/pmg.py), sizes in points per direction, 2 <= pc < pf <= 13, ndim 2
+ * or 3.  The pairs of the default schedules p -> p / 2 (points 3->2, 4->2,
+ * 5->3, 6->3, 7->4, 8->4, 9->5, 10->5, 11->6, 12->6, 13->7) are compiled with
+ * fixed sizes, other pairs run with run-time sizes.  One wave per element.
+ *   cidx (E, pc^ndim), fidx (E, pf^ndim): int32 index rows; a Dirichlet node
+ *       is stored as ~id (reads as 0; prolong stores 0 there);
+ *   owner (E, ceil(pf^ndim / 32)) uint32: bit t of element e set iff e owns
+ *       its local fine node t; every fine node has exactly one owner;
+ *   mat (pf, pc) row-major: the 1D interpolation from the coarse to the fine
+ *       points (Lagrange basis of the coarse points at the fine points).
+ * sfem_pmg_prolong:  uf = P uc (add != 0: uf += P uc, Dirichlet nodes left as
+ *                    they are), written once per fine node at its owner: no
+ *                    atomics, no element-local result in memory;
+ * sfem_pmg_restrict: rc_local[e] = the transposed contraction of the owned
+ *                    fine values of element e, coarse Dirichlet slots 0;
+ *                    sfem_scatter_csr over the coarse mesh sums them in a
+ *                    fixed order, and the two together are exactly P^T.     */
+int sfem_pmg_prolong(const void* uc, void* uf, const int32_t* cidx,
+                     const int32_t* fidx, const uint32_t* owner,
+                     const void* mat, int64_t num_elements, int ndim, int pc,
+                     int pf, int add, int dtype, sfem_stream_t stream);
+int sfem_pmg_restrict(const void* rf, void* rc_local, const int32_t* cidx,
+                      const int32_t* fidx, const uint32_t* owner,
+                      const void* mat, int64_t num_elements, int ndim, int pc,
+                      int pf, int dtype, sfem_stream_t stream);
+/* One step of the Chebyshev-Jacobi smoother in one pass over n values:
+ *   mode 0:  d = a d + c dinv (b - ax);  x += d
+ *   mode 1:  d = c dinv b;  x = d          (start from x = 0: ax, x, d unread)
+ *   mode 2:  r = b - ax                    (the residual before restriction)
+ *   mode 3:  d = c dinv (b - ax);  x += d  (d unread)
+ * dinv is 0 on Dirichlet rows.  Pointers a mode does not use may be NULL.   */
+int sfem_cheb_step(void* x, void* d, const void* ax, const void* b,
+                   const void* dinv, void* r, double a, double c, int64_t n,
+                   int mode, int dtype, sfem_stream_t stream);
+/* CG that stops on the true-residual norm r.r instead of r.Mr (a V-cycle M
+ * approximates A^-1, so r.Mr is an energy norm), with reproducible inner
+ * products: sfem_pmg_dot2 stores, per workgroup g < groups, the sum of a.b at
+ * partials[g] and (c != NULL) of a.c at partials[groups + g];
+ * sfem_pmg_cg_scalars adds n stored partials in a fixed order:
+ *   phase 3: [5] b.b = sum partials[0, n)
+ *   phase 2: init: [13] r.r = sum [0, n), [0] gamma = r.z = sum [n, 2n),
+ *            atol2, counters, status; done if r.r <= atol2
+ *   phase 0: [1] p.Ap = sum [0, n); alpha; [2] = 0 (BAD_PAP as phase 0 of
+ *            sfem_cg_scalars)
+ *   phase 4: [13] r.r = sum [0, n), [2] gamma_new = r.z = sum [n, 2n)
+ *   phase 1: close: beta, gamma <- gamma_new, ++iterations; done when
+ *            r.r <= atol2, r.z is negative / not finite, or maxiter.
+ * The scalar slots are those of sfem_cg_scalars, so sfem_cg_update_r
+ * (fuse_rr = 0), sfem_cg_update_r_layered and sfem_cg_update_xp run
+ * unchanged between them.                                                    */
+int sfem_pmg_dot2(const void* a, const void* b, const void* c, int64_t n,
+                  double* partials, int groups, int dtype,
+                  sfem_stream_t stream);
+int sfem_pmg_cg_scalars(double* scalars, int phase, const double* partials,
+                        int64_t n, double maxiter, double tol, double atol,
+                        sfem_stream_t stream);
 /* y = a*x + b*y (plain fused vector update used outside the CG core)         */
 int sfem_axpby(double a, const void* x, double b, void* y, int64_t count,
                int dtype, sfem_stream_t stream);

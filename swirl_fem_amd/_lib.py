@@ -193,6 +193,15 @@ SIGNATURES = {
     'sfem_stokes_e_first': [c_ptr, c_ptr],
     'sfem_stokes_e_second': [c_ptr, c_ptr],
     'sfem_stokes_convect_local': [c_ptr, c_ptr],
+    'sfem_pmg_prolong': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64,
+                         c_i32, c_i32, c_i32, c_i32, c_i32, c_ptr],
+    'sfem_pmg_restrict': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64,
+                          c_i32, c_i32, c_i32, c_i32, c_ptr],
+    'sfem_cheb_step': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_dbl, c_dbl,
+                       c_i64, c_i32, c_i32, c_ptr],
+    'sfem_pmg_dot2': [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i32, c_i32, c_ptr],
+    'sfem_pmg_cg_scalars': [c_ptr, c_i32, c_ptr, c_i64, c_dbl, c_dbl, c_dbl,
+                            c_ptr],
     'sfem_abi_version': [],
 }
 

@@ -116,11 +116,16 @@ def scatter_add(u_local, indices, num_nodes, ncomp=1):
   return out
 
 
-def scatter_csr(u_local, offsets, slots, num_nodes, ncomp=1):
+def scatter_csr(u_local, offsets, slots, num_nodes, ncomp=1, out=None):
   u_local = u_local.contiguous()
   dev = _dev(u_local, offsets, slots)
   shape = (num_nodes,) if ncomp == 1 else (num_nodes, ncomp)
-  out = torch.empty(shape, dtype=u_local.dtype, device=dev)
+  if out is None:
+    out = torch.empty(shape, dtype=u_local.dtype, device=dev)
+  elif (tuple(out.shape) != shape or out.dtype != u_local.dtype or
+        not out.is_contiguous()):
+    raise ValueError('scatter_csr: `out` must be a dense (num_nodes[, ncomp]) '
+                     'tensor of the values\' dtype')
   with torch.cuda.device(dev):
     _lib.check(_lib.load().sfem_scatter_csr(
         _ptr(u_local), _ptr(offsets), _ptr(slots), _ptr(out), num_nodes, ncomp,
@@ -763,12 +768,13 @@ def add_element_constants_(z, yc, shift, n, elems_per_member):
   return z
 
 
-def ell_chebyshev(cols, vals, dinv, b, steps, lmin, lmax, work=None):
+def ell_chebyshev(cols, vals, dinv, b, steps, lmin, lmax, work=None,
+                  out=None):
   """x = Chebyshev polynomial of the Jacobi-scaled ELL matrix applied to b
   (`sfem_ell_chebyshev`); cols / vals (width, n) int32 / real."""
   dev = _dev(cols, vals, dinv, b)
   n = b.numel()
-  x = torch.empty_like(b)
+  x = torch.empty_like(b) if out is None else out
   if work is None:
     work = torch.empty(3 * n, dtype=b.dtype, device=b.device)
   with torch.cuda.device(dev):
@@ -1277,3 +1283,70 @@ def cg_update_xp_jacobi(x, p, r, dinv, scalars, ncomp=1):
         _ptr(x), _ptr(p), _ptr(r), _ptr(dinv), dinv.numel(), int(ncomp),
         _ptr(scalars), _dtype_code(r), _stream(dev)),
         'sfem_cg_update_xp_jacobi')
+
+
+# ------------------------------------------------------------- p-multigrid
+def pmg_prolong(uc, uf, cidx, fidx, owner, mat, ndim, pc, pf, add=False):
+  """uf = P uc (add: uf += P uc), see `sfem_pmg_prolong`; in place."""
+  dev = _dev(uc, uf, cidx, fidx, owner, mat)
+  if uc.dtype != uf.dtype or mat.dtype != uf.dtype:
+    raise ValueError('pmg_prolong: one dtype for uc, uf and mat')
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_pmg_prolong(
+        _ptr(uc), _ptr(uf), _ptr(cidx), _ptr(fidx), _ptr(owner), _ptr(mat),
+        cidx.shape[0], int(ndim), int(pc), int(pf), int(bool(add)),
+        _dtype_code(uf), _stream(dev)), 'sfem_pmg_prolong')
+  return uf
+
+
+def pmg_restrict(rf, rc_local, cidx, fidx, owner, mat, ndim, pc, pf):
+  """rc_local (E, pc^ndim) = element-local P^T rf, see `sfem_pmg_restrict`."""
+  dev = _dev(rf, rc_local, cidx, fidx, owner, mat)
+  if rf.dtype != rc_local.dtype or mat.dtype != rf.dtype:
+    raise ValueError('pmg_restrict: one dtype for rf, rc_local and mat')
+  if rc_local.numel() != cidx.numel():
+    raise ValueError('pmg_restrict: rc_local must match the coarse index rows')
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_pmg_restrict(
+        _ptr(rf), _ptr(rc_local), _ptr(cidx), _ptr(fidx), _ptr(owner),
+        _ptr(mat), cidx.shape[0], int(ndim), int(pc), int(pf),
+        _dtype_code(rf), _stream(dev)), 'sfem_pmg_restrict')
+  return rc_local
+
+
+CHEB_GENERAL, CHEB_FIRST, CHEB_RESIDUAL, CHEB_RESTART = 0, 1, 2, 3
+
+
+def cheb_step(x, d, ax, b, dinv, r, a, c, mode):
+  """One fused Chebyshev-Jacobi step (`sfem_cheb_step`); in place."""
+  vs = [t for t in (x, d, ax, b, dinv, r) if t is not None]
+  dev = _dev(*vs)
+  n = b.numel()
+  if any(t.numel() != n or t.dtype != b.dtype for t in vs):
+    raise ValueError('cheb_step: vectors of one size and dtype')
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_cheb_step(
+        _ptr(x), _ptr(d), _ptr(ax), _ptr(b), _ptr(dinv), _ptr(r), float(a),
+        float(c), n, int(mode), _dtype_code(b), _stream(dev)),
+        'sfem_cheb_step')
+
+
+def pmg_dot2(a, b, c, partials, groups):
+  """partials[:groups] = stored sums of a.b, partials[groups:2 groups] of a.c
+  (`sfem_pmg_dot2`)."""
+  vs = [t for t in (a, b, c) if t is not None]
+  dev = _dev(*vs, partials)
+  if partials.dtype != torch.float64 or partials.numel() < 2 * groups:
+    raise ValueError('pmg_dot2: partials must hold 2 * groups doubles')
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_pmg_dot2(
+        _ptr(a), _ptr(b), _ptr(c), a.numel(), _ptr(partials), int(groups),
+        _dtype_code(a), _stream(dev)), 'sfem_pmg_dot2')
+
+
+def pmg_cg_scalars(scalars, phase, partials, n, maxiter, tol, atol):
+  dev = _dev(scalars, partials)
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_pmg_cg_scalars(
+        _ptr(scalars), int(phase), _ptr(partials), int(n), float(maxiter),
+        float(tol), float(atol), _stream(dev)), 'sfem_pmg_cg_scalars')

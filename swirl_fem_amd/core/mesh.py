@@ -137,7 +137,8 @@ class Mesh:
         node_indices=node_indices,
         physical_masks={k: v.repeat(members)
                         for k, v in self.physical_masks.items()},
-        exchange_gather_indices=gi, exchange_unique_indices=ui)
+        exchange_gather_indices=gi, exchange_unique_indices=ui,
+        _cache={'replicas': members})
 
   # ------------------------------------------------------------- properties
   @property

@@ -44,12 +44,14 @@ def solve_poisson(mesh: Mesh, forcing,
                   return_info: bool = False, preconditioner=None):
   """Solves Poisson's equation on `mesh` for the nodal `forcing`.
 
-  `preconditioner`: None (the reference's unpreconditioned CG) or 'jacobi':
+  `preconditioner`: None (the reference's unpreconditioned CG), 'jacobi':
   the inverse assembled diagonal of the stiffness operator
   (`linalg.jacobi.JacobiPreconditioner`, strict: the stopping rule is at
-  least as tight as without it); needs the fused operator.
+  least as tight as without it), or 'pmg': one p-multigrid V-cycle
+  (`linalg.pmg.PMultigridPreconditioner`); CG then stops on the true residual,
+  ||b - A u|| <= max(rtol ||b||, atol).  Both need the fused operator.
   """
-  if preconditioner not in (None, 'jacobi'):
+  if preconditioner not in (None, 'jacobi', 'pmg'):
     raise ValueError(f'unknown preconditioner {preconditioner!r}')
   quadrature = Quadrature1D.create(
       num_points=mesh.order + (mesh.ndim + 1) // 2,
@@ -99,6 +101,9 @@ def solve_poisson(mesh: Mesh, forcing,
     if preconditioner == 'jacobi':
       from swirl_fem_amd.linalg.jacobi import JacobiPreconditioner
       M = JacobiPreconditioner(op, 0.0, 1.0)
+    elif preconditioner == 'pmg':
+      from swirl_fem_amd.linalg.pmg import PMultigridPreconditioner
+      M = PMultigridPreconditioner(op, 0.0, 1.0)
   elif preconditioner is not None:
     raise NotImplementedError(
         f"preconditioner={preconditioner!r} needs the fused operator: "

@@ -14,6 +14,12 @@ each iteration; once it fires every later kernel is a no-op, and the host only
 polls the flag every `check_every` iterations.  Iterates and iteration count
 are therefore identical to a loop that tests every iteration.
 
+A preconditioner with `stops_on_residual = True` (`linalg/pmg.py`, a V-cycle:
+M ~ A^-1, so r . M r is an energy norm) switches the stopping test to the true
+residual, r . r <= max(tol^2 b.b, atol^2), and sums every inner product of the
+solve in a fixed order (`sfem_pmg_dot2`, `sfem_pmg_cg_scalars`); with a
+layered operator the iteration is then bitwise reproducible.
+
 A preconditioner that offers `mean_projection()` (M r = r - (w.r / total) 1,
 the nullspace projection of the pressure solve) is folded into the two vector
 updates: z = M r is never stored and r . z comes out of the sums update_r takes
@@ -69,6 +75,7 @@ MAX_KEPT_RUNNERS = 6   # solver states a `workspace` of `cg` holds at most
 # SFEM_LAZY_X_MIN_MB overrides it, the tests set 0)
 LAZY_X_MIN_BYTES = 1 << 28
 RR_PARTIALS = 1 << 16      # stored r.r sums: one per workgroup of the r update
+RESIDUAL_STOP_GROUPS = 512  # stored partial sums per inner product (r.r stop)
 
 
 def _lazy_min_bytes():
@@ -160,6 +167,12 @@ class CGRunner:
     self.parts = s.partials if self.fused_dot else None
     _ops.cg_scalars(s.t, 2, maxiter, tol, atol, self.parts)
     self.fuse_rr = self.identity_m and dot_fn is None
+    # stop on r.r with fixed-order sums: the preconditioner asks for it
+    self.rr_stop = None
+    if (getattr(M, 'stops_on_residual', False) and dot_fn is None and
+        reduce_fn is None and interface is None and
+        isinstance(self.r, torch.Tensor) and self.r.dim() == 1):
+      self._residual_stop_setup(A, b, z)
     # r.r spread over 64 slots: update_r then streams with 128 workgroups per
     # CU.  When something needs the complete sum in the named slot right after
     # the update (an all-reduce, the interface correction) one tiny scalar
@@ -171,7 +184,7 @@ class CGRunner:
     # M r = r - (w . r / total) 1 folded into the two vector updates
     self.mean = None
     probe = getattr(M, 'mean_projection', None)
-    if (probe is not None and dot_fn is None and reduce_fn is None and
+    if (probe is not None and self.rr_stop is None and dot_fn is None and reduce_fn is None and
         interface is None and isinstance(self.r, torch.Tensor) and
         switches.get('SFEM_FUSED_MEAN') != '0'):
       found = probe()
@@ -185,7 +198,8 @@ class CGRunner:
     # of a scalar or component-major field (one dinv for all components)
     self.jacobi = None
     probe = getattr(M, 'jacobi_diagonal', None)
-    if (probe is not None and self.mean is None and dot_fn is None and
+    if (probe is not None and self.mean is None and self.rr_stop is None and
+        dot_fn is None and
         reduce_fn is None and interface is None and
         isinstance(self.r, torch.Tensor) and
         switches.get('SFEM_FUSED_JACOBI') != '0'):
@@ -210,7 +224,8 @@ class CGRunner:
     # On partitions (`reduce_fn`, `interface`) the operator hands back the
     # layered result with its interface nodes already whole and exchanged.
     self.layered = None
-    if (self.fused_dot and self.mean is None and self._p.dim() == 1 and
+    if (self.fused_dot and self.mean is None and self.rr_stop is None and
+        self._p.dim() == 1 and
         hasattr(A, 'apply_layered_with_dot')):
       self.layered = A.layer_plan()
     # ... and with the two inner products of the iteration summed from STORED
@@ -234,6 +249,7 @@ class CGRunner:
     # (With the fused Jacobi updates x is updated every iteration.)
     m = int(switches.get('SFEM_LAZY_X'))
     if (m >= 2 and self.mean is None and self.jacobi is None and
+        self.rr_stop is None and
         isinstance(self._p, torch.Tensor) and
         self._p.is_contiguous() and
         self._p.numel() * self._p.element_size() >= _lazy_min_bytes()):
@@ -249,6 +265,57 @@ class CGRunner:
     self.issued = 0
     self._graph = None
     self._capture_failed = False
+
+  def _residual_stop_setup(self, A, b, z):
+    """State of the r.r-stopping path: stored partial sums of the inner
+    products, and the layered apply (per-wave p.Ap sums) when A has one."""
+    dev = self.r.device
+    G = RESIDUAL_STOP_GROUPS
+    layered = None
+    if hasattr(A, 'apply_layered_with_dot') and hasattr(A, 'layer_plan'):
+      layered = A.layer_plan()
+    waves = A.layered_dot_slots() if layered is not None else 0
+    self.rr_stop = dict(
+        groups=G, layered=layered,
+        parts=torch.zeros(2 * G, dtype=torch.float64, device=dev),
+        waves=torch.zeros(waves + _lib.SFEM_FOLD_GROUPS, dtype=torch.float64,
+                          device=dev), num_waves=waves)
+    self.fused_dot = False
+    self.parts = None
+    self._residual_stop_start(b, z)
+
+  def _residual_stop_start(self, b, z):
+    """b.b, r.r and gamma_0 = r.z as fixed-order sums; the stop rule on r.r."""
+    st = self.rr_stop
+    G, parts = st['groups'], st['parts']
+    args = (self.maxiter, self.tol, self.atol)
+    _ops.pmg_dot2(b, b, None, parts, G)
+    _ops.pmg_cg_scalars(self.s.t, 3, parts, G, *args)
+    _ops.pmg_dot2(self.r, self.r, layout.like(z, self.r).contiguous(), parts,
+                  G)
+    _ops.pmg_cg_scalars(self.s.t, 2, parts, G, *args)
+
+  def _step_residual_stop(self):
+    """One PCG iteration that stops on r.r (see the module docstring)."""
+    s, st = self.s, self.rr_stop
+    G, parts = st['groups'], st['parts']
+    args = (self.maxiter, self.tol, self.atol)
+    if st['layered'] is not None:
+      Ap = self.A.apply_layered_with_dot(self.p, st['waves'], per_wave=True)
+      _ops.pmg_cg_scalars(s.t, 0, st['waves'], st['num_waves'], *args)
+      _ops.cg_update_r_layered(self.r, Ap, st['layered'].layers, s.t, 0,
+                               masks=st['layered'].masks)
+    else:
+      Ap = layout.like(self.A(self.p), self.r).contiguous()
+      _ops.pmg_dot2(self.p, Ap, None, parts, G)
+      _ops.pmg_cg_scalars(s.t, 0, parts, G, *args)
+      _ops.cg_update_r(self.r, Ap, s.t, 0)
+    z = layout.like(self.M(self.r), self.r).contiguous()
+    _ops.pmg_dot2(self.r, self.r, z, parts, G)
+    _ops.pmg_cg_scalars(s.t, 4, parts, G, *args)
+    _ops.cg_update_xp(self._x, self.p, z, s.t)
+    _ops.pmg_cg_scalars(s.t, 1, parts, G, *args)
+    self.issued += 1
 
   def _reproducible_start(self, b, z):
     """b.b and gamma_0 = r.z again, as tree reductions without atomics (the
@@ -335,6 +402,8 @@ class CGRunner:
     _ops.cg_scalars(s.t, 2, self.maxiter, self.tol, self.atol, self.parts)
     if self.det is not None:
       self._reproducible_start(b, z)
+    if self.rr_stop is not None:
+      self._residual_stop_start(b, z)
     if self.mean is not None:
       self.mean[2].zero_()
     self.issued = 0
@@ -348,6 +417,9 @@ class CGRunner:
     self._step_eager()
 
   def _step_eager(self):
+    if self.rr_stop is not None:
+      self._step_residual_stop()
+      return
     s, S = self.s, _Scalars
     A, M, dot_fn, reduce_fn = self.A, self.M, self.dot_fn, self.reduce_fn
     args = (self.maxiter, self.tol, self.atol, self.parts)
@@ -561,7 +633,8 @@ def cg(A, b, x0=None, *, tol=1e-5, atol=0.0, maxiter=None, M=None,
     A: linear operator on pytrees of device tensors.
     b: right-hand side pytree.
     x0: initial guess (default zeros).
-    tol, atol: stop when r^T M r <= max(tol^2 b.b, atol^2).
+    tol, atol: stop when r^T M r <= max(tol^2 b.b, atol^2) (r^T r with a
+      preconditioner that sets `stops_on_residual`, e.g. p-multigrid).
     maxiter: iteration cap (default 10 * size).
     M: preconditioner (default identity).
     dot_fn: optional custom inner product `(a, b) -> scalar tensor`; the default

@@ -1,0 +1,256 @@
+"""NumPy restatement of p-multigrid (`swirl_fem_amd/linalg/pmg.py`) for the
+tests: element matrices from the oracle's geometric factors, the transfers
+as explicit sparse matrices (owner rule, facet rule for the coarse Dirichlet
+nodes), the Chebyshev-Jacobi smoother, the coarse Chebyshev polynomial, the
+V-cycle and PCG that stops on r.r.  The node numbering of the coarse meshes
+is `pmg.coarse_numbering` (host NumPy); the tests check it on its own.
+"""
+import numpy as np
+import scipy.sparse as sp
+
+from oracle import sfem_oracle as O
+from swirl_fem_amd.linalg import pmg
+
+
+def interp_1d(pc, pf):
+  """(pf + 1, pc + 1): coarse GLL Lagrange basis at the fine GLL points."""
+  return np.asarray(O.Interpolator(1, pc + 1, 'gll', pf + 1, 'gll')
+                    .interpolation_matrix(), dtype=np.float64)
+
+
+def element_matrices(coords, elements, P, quad, l0, l1):
+  """(E, n, n) element matrices of l0 B + l1 A (quad = (num, type))."""
+  fes = O.FESpace(coords, elements, (P, 'gll'), quad)
+  wdet = fes.jacdets * fes.weights[None, :]
+  phys = np.einsum('qid,eqjd->eqij', fes.G, fes.invjacs)     # (E, Q, n, d)
+  K = l1 * np.einsum('eq,eqid,eqjd->eij', wdet, phys, phys)
+  if l0:
+    K = K + l0 * np.einsum('eq,qi,qj->eij', wdet, fes.M, fes.M)
+  return K
+
+
+class Level:
+  def __init__(self, coords, elements, order, dirichlet, K):
+    self.coords, self.elements, self.order = coords, elements, order
+    self.N = coords.shape[0]
+    self.dirichlet = dirichlet
+    self.keep = (~dirichlet).astype(np.float64)
+    self.K = K
+    d = np.bincount(elements.ravel(),
+                    weights=np.einsum('eii->ei', K).ravel(), minlength=self.N)
+    self.diag = d * self.keep
+    self.dinv = np.where(self.diag > 0, 1.0 / np.where(self.diag > 0,
+                                                       self.diag, 1.0), 0.0)
+
+  def apply(self, u):
+    """K scatter(K_e gather(u)) (rows of Dirichlet nodes zero)."""
+    loc = np.einsum('eij,ej->ei', self.K, u[self.elements])
+    return self.keep * np.bincount(self.elements.ravel(), weights=loc.ravel(),
+                                   minlength=self.N)
+
+  def matrix(self):
+    E, n = self.elements.shape
+    rows = np.repeat(self.elements[:, :, None], n, 2).ravel()
+    cols = np.repeat(self.elements[:, None, :], n, 1).ravel()
+    A = sp.csr_matrix((np.broadcast_to(self.K, (E, n, n)).ravel(),
+                       (rows, cols)), shape=(self.N, self.N))
+    k = sp.diags(self.keep)
+    return (k @ A @ k).tocsr()
+
+
+def facet_rule(fine_dir_local, d, pf, pc):
+  """Coarse element-local Dirichlet flags by the facet rule, one coarse node
+  at a time."""
+  E = fine_dir_local.shape[0]
+  Pf, Pc = pf + 1, pc + 1
+  out = np.zeros((E, Pc ** d), dtype=bool)
+  fine_idx = np.stack(np.meshgrid(*[np.arange(Pf)] * d, indexing='ij'),
+                      -1).reshape(-1, d)
+  for t, c in enumerate(np.stack(np.meshgrid(*[np.arange(Pc)] * d,
+                                             indexing='ij'), -1).reshape(-1, d)):
+    sel = np.ones(len(fine_idx), dtype=bool)
+    for a in range(d):
+      if c[a] == 0:
+        sel &= fine_idx[:, a] == 0
+      elif c[a] == pc:
+        sel &= fine_idx[:, a] == pf
+    out[:, t] = fine_dir_local[:, sel].all(axis=1)
+  return out
+
+
+def coarsen(fine, pc, l0, l1):
+  """(coarse Level, P (Nf x Nc) sparse) of order pc below `fine`."""
+  d = fine.coords.shape[1]
+  pf = fine.order
+  celems, _, nc = pmg.coarse_numbering(fine.elements.astype(np.int64), None,
+                                       d, pf, pc)
+  Jg = np.asarray(O.Interpolator(1, pf + 1, 'gll', pc + 1, 'gll')
+                  .interpolation_matrix(), dtype=np.float64)
+  Jgd = Jg
+  for _ in range(d - 1):
+    Jgd = np.kron(Jgd, Jg)
+  xc = np.einsum('cf,efd->ecd', Jgd, fine.coords[fine.elements])
+  coords = np.zeros((nc, d))
+  E = celems.shape[0]
+  for e in range(E - 1, -1, -1):          # the lowest element wins
+    coords[celems[e]] = xc[e]
+  cdir_loc = facet_rule(fine.dirichlet[fine.elements], d, pf, pc)
+  cdir = np.zeros(nc, dtype=bool)
+  cdir[celems.ravel()] = cdir_loc.ravel()
+  K = element_matrices(coords, celems, pc + 1, (pc + 1, 'gll'), l0, l1)
+  coarse = Level(coords, celems, pc, cdir, K)
+  # P: every fine node interpolated from its lowest-numbered element
+  J = interp_1d(pc, pf)
+  Jd = J
+  for _ in range(d - 1):
+    Jd = np.kron(Jd, J)
+  owner = np.full(fine.N, -1)
+  for e in range(E - 1, -1, -1):
+    owner[fine.elements[e]] = e
+  rows, cols, vals = [], [], []
+  for e in range(E):
+    mine = np.nonzero(owner[fine.elements[e]] == e)[0]
+    for t in mine:
+      rows += [fine.elements[e, t]] * Jd.shape[1]
+      cols += list(celems[e])
+      vals += list(Jd[t])
+  P = sp.csr_matrix((vals, (rows, cols)), shape=(fine.N, nc))
+  P = sp.diags(fine.keep) @ P @ sp.diags(coarse.keep)
+  return coarse, P.tocsr()
+
+
+def cheb_coefficients(lo, hi, degree):
+  theta, delta = 0.5 * (hi + lo), 0.5 * (hi - lo)
+  sigma = theta / delta
+  rho = 1.0 / sigma
+  out = [(0.0, 1.0 / theta)]
+  for _ in range(1, degree):
+    rho_new = 1.0 / (2.0 * sigma - rho)
+    out.append((rho_new * rho, 2.0 * rho_new / delta))
+    rho = rho_new
+  return out
+
+
+def smooth(level, b, x, coefs):
+  d = np.zeros_like(b)
+  for a, c in coefs:
+    d = a * d + c * level.dinv * (b - level.apply(x))
+    x = x + d
+  return x
+
+
+def coarse_chebyshev(A, dinv, b, steps, lmin, lmax):
+  """The polynomial of `sfem_ell_chebyshev`."""
+  theta, delta = 0.5 * (lmax + lmin), 0.5 * (lmax - lmin)
+  sigma = theta / delta
+  x = np.zeros_like(b)
+  r = b.copy()
+  d = dinv * b / theta
+  rho = 1.0 / sigma
+  for _ in range(steps):
+    rho_new = 1.0 / (2.0 * sigma - rho)
+    x = x + d
+    r = r - A @ d
+    d = rho_new * rho * d + 2.0 * rho_new / delta * dinv * r
+    rho = rho_new
+  return x
+
+
+class Hierarchy:
+  """Levels, transfers and smoother / coarse parameters of a V-cycle.
+
+  `lam_max` (one per smoothed level) and `coarse` = (steps, lmin, lmax): the
+  values the GPU preconditioner chose, or None to take exact ones here."""
+
+  def __init__(self, coords, elements, order, dirichlet, l0, l1, *,
+               orders=None, degree=2, quad=None, lam_max=None, coarse=None,
+               low=pmg.SMOOTHER_LOW, high=pmg.SMOOTHER_HIGH):
+    orders = pmg.default_orders(order) if orders is None else orders
+    quad = (order + 1, 'gll') if quad is None else quad
+    K = element_matrices(coords, elements, order + 1, quad, l0, l1)
+    self.levels = [Level(coords, elements, order, dirichlet, K)]
+    self.P = []
+    for pc in orders[1:]:
+      c, P = coarsen(self.levels[-1], pc, l0, l1)
+      self.levels.append(c)
+      self.P.append(P)
+    self.cheb = []
+    for i, lev in enumerate(self.levels[:-1]):
+      if lam_max is None:
+        import scipy.sparse.linalg as spla
+        inner = np.nonzero(lev.dinv > 0)[0]
+        s = sp.diags(np.sqrt(lev.dinv[inner]))
+        S = s @ lev.matrix()[inner][:, inner] @ s
+        lam = float(spla.eigsh(S, k=1, which='LA', tol=1e-6,
+                               return_eigenvectors=False)[0])
+      else:
+        lam = lam_max[i]
+      self.cheb.append(cheb_coefficients(low * lam, high * lam, degree))
+    last = self.levels[-1]
+    self.A0 = last.matrix()
+    if coarse is None:
+      inner = last.dinv > 0
+      s = np.sqrt(last.dinv[inner])
+      ev = np.linalg.eigvalsh(s[:, None] * self.A0.toarray()[
+          np.ix_(inner, inner)] * s[None, :])
+      lmin, lmax = 0.9 * ev[0], 1.05 * ev[-1]
+      steps = int(np.ceil(0.5 * np.sqrt(lmax / lmin) *
+                          np.log(2.0 / pmg.COARSE_REDUCTION)))
+      coarse = (max(2, steps), lmin, lmax)
+    self.coarse = coarse
+
+  def vcycle(self, b, l=0):
+    lev = self.levels[l]
+    if l == len(self.levels) - 1:
+      steps, lmin, lmax = self.coarse
+      return coarse_chebyshev(self.A0, lev.dinv, b, steps, lmin, lmax)
+    x = smooth(lev, b, np.zeros_like(b), self.cheb[l])
+    r = b - lev.apply(x)
+    xc = self.vcycle(self.P[l].T @ r, l + 1)
+    x = x + self.P[l] @ xc
+    return smooth(lev, b, x, self.cheb[l])
+
+  def pcg(self, b, rtol, maxiter=10000, precondition=True):
+    """PCG stopping on r.r <= rtol^2 b.b; (x, iterations)."""
+    lev = self.levels[0]
+    M = self.vcycle if precondition else (lambda r: r)
+    x = np.zeros_like(b)
+    r = b.copy()
+    z = M(r)
+    p = z.copy()
+    gamma = r @ z
+    stop = rtol ** 2 * (b @ b)
+    it = 0
+    while r @ r > stop and it < maxiter:
+      Ap = lev.apply(p)
+      alpha = gamma / (p @ Ap)
+      x = x + alpha * p
+      r = r - alpha * Ap
+      z = M(r)
+      g_new = r @ z
+      p = z + g_new / gamma * p
+      gamma = g_new
+      it += 1
+    return x, it
+
+
+def box(n, ndim, P, mode='uniform', seed=0, periodic=()):
+  """Host premesh of an n^d box refined to P points (GLL), perturbed."""
+  from swirl_fem_amd.common.premesh_commons import unit_cube_mesh
+  from swirl_fem_amd.core.interpolation import Nodes1D, NodeType
+  from swirl_fem_amd.core.mesh_refiner import refine_premesh
+  rng = np.random.default_rng(seed)
+  pm = unit_cube_mesh(n, ndim=ndim, periodic_dims=periodic)
+  x = pm.node_coords.copy()
+  if mode == 'jitter':
+    x = x + 0.1 / n * rng.uniform(-1, 1, x.shape)
+  elif mode == 'sheared':
+    A = np.eye(ndim) + 0.3 * rng.uniform(-1, 1, (ndim, ndim))
+    x = x @ A.T + 0.1
+  rp = refine_premesh(pm.replace(node_coords=x),
+                      Nodes1D.create(P, NodeType.GAUSS_LOBATTO_LEGENDRE))
+  if mode == 'curved':
+    xc = rp.node_coords.copy()
+    xc[:, 0] += 0.03 * np.sin(np.pi * xc[:, 1])
+    rp = rp.replace(node_coords=xc)
+  return rp
