@@ -882,6 +882,19 @@ int sfem_pmg_dot2(const void* a, const void* b, const void* c, int64_t n,
 int sfem_pmg_cg_scalars(double* scalars, int phase, const double* partials,
                         int64_t n, double maxiter, double tol, double atol,
                         sfem_stream_t stream);
+/* y = A x on some rows of an ELL matrix in the layout of sfem_ell_chebyshev
+ * (n rows of `width` entries, column-major: entry k of row i at [k n + i];
+ * every column index in [0, n)): the rows [row_begin, row_end) when `rows` is
+ * NULL, else the `num_rows` rows listed in `rows` (int32, each in [0, n),
+ * no repeats).  Rows not named are not written.  The coarse Chebyshev step of
+ * p-multigrid on a partition (linalg/pmg.py): interface rows, exchange posted,
+ * interior rows, exchange finished, sfem_cheb_step.  A row range runs 2
+ * (fp64) / 4 (fp32) rows per lane with 16-byte loads of the values when n is
+ * a multiple of that; row lists one row per lane.                            */
+int sfem_ell_spmv(const int32_t* cols, const void* vals, const void* x,
+                  void* y, int64_t n, int width, int64_t row_begin,
+                  int64_t row_end, const int32_t* rows, int64_t num_rows,
+                  int dtype, sfem_stream_t stream);
 /* y = a*x + b*y (plain fused vector update used outside the CG core)         */
 int sfem_axpby(double a, const void* x, double b, void* y, int64_t count,
                int dtype, sfem_stream_t stream);

@@ -785,6 +785,38 @@ def ell_chebyshev(cols, vals, dinv, b, steps, lmin, lmax, work=None,
   return x
 
 
+
+def ell_spmv(cols, vals, x, y, rows=None, row_range=None):
+  """y[i] = (A x)[i] for the ELL matrix cols / vals (width, n) int32 / real
+  (`sfem_ell_spmv`), on the rows of `rows` (int32 device tensor, each in
+  [0, n)) or of `row_range` = (begin, end) (default: all rows); the other
+  rows of y are not written.  Returns y."""
+  dev = _dev(cols, vals, x, y, rows)
+  n = x.numel()
+  if cols.shape != vals.shape or cols.shape[1] != n or y.numel() != n:
+    raise ValueError('ell_spmv: cols / vals must be (width, n), x and y (n,)')
+  if cols.dtype != torch.int32 or vals.dtype != x.dtype or y.dtype != x.dtype:
+    raise TypeError('ell_spmv: int32 columns, one real dtype for vals, x, y')
+  if not (cols.is_contiguous() and vals.is_contiguous() and
+          x.is_contiguous() and y.is_contiguous()):
+    raise ValueError('ell_spmv: contiguous operands only')
+  if rows is not None:
+    if rows.dtype != torch.int32 or not rows.is_contiguous():
+      raise TypeError('ell_spmv: rows must be a contiguous int32 tensor')
+    begin, end, count = 0, 0, rows.numel()
+  else:
+    begin, end = (0, n) if row_range is None else (int(row_range[0]),
+                                                    int(row_range[1]))
+    if not 0 <= begin <= end <= n:
+      raise ValueError(f'ell_spmv: row range {(begin, end)} outside [0, {n}]')
+    count = 0
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_ell_spmv(
+        _ptr(cols), _ptr(vals), _ptr(x), _ptr(y), n, cols.shape[0], begin,
+        end, _ptr(rows), count, _dtype_code(x), _stream(dev)),
+        'sfem_ell_spmv')
+  return y
+
 # ------------------------------------------------------- ensemble CG (vmap)
 def _ens_check(members, *vs):
   dev = _dev(*vs)

@@ -489,6 +489,107 @@ pmg_cg_scalars_kernel(double* __restrict__ s, int phase,
   }
 }
 
+
+// ------------------------------------------------------ ELL product ---
+// y = A x on some rows of the order-1 matrix in the column-major ELL layout
+// of sfem_ell_chebyshev (entry k of row i at [k n + i]): the coarse step of
+// the V-cycle on a partition, split into interface and interior rows so that
+// the neighbour exchange overlaps the interior rows.  A row range runs VN
+// consecutive rows per lane (16-byte loads of the values, 8- / 16-byte loads
+// of the columns; a wave covers 128 (fp64) or 256 (fp32) rows); a row list or
+// an unaligned range runs one row per lane.  x is gathered through the
+// columns (order-1 stencils: the neighbours' values are close in memory).
+template <typename T>
+struct EllCols;
+template <>
+struct EllCols<double> {
+  typedef int32_t type __attribute__((ext_vector_type(2)));
+};
+template <>
+struct EllCols<float> {
+  typedef int32_t type __attribute__((ext_vector_type(4)));
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+ell_spmv_vec_kernel(const int32_t* __restrict__ cols, const T* __restrict__ vals,
+                    const T* __restrict__ x, T* __restrict__ y, int64_t n,
+                    int width, int64_t row_begin, int64_t nvec) {
+  using V = typename PmgVec<T>::type;
+  using C = typename EllCols<T>::type;
+  constexpr int VN = PmgVec<T>::N;
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nvec) return;
+  const int64_t i0 = row_begin + t * VN;
+  V acc = V(0);
+#pragma unroll 4
+  for (int k = 0; k < width; ++k) {
+    const int64_t at = (int64_t)k * n + i0;
+    const C c = *reinterpret_cast<const C*>(cols + at);
+    const V v = *reinterpret_cast<const V*>(vals + at);
+#pragma unroll
+    for (int j = 0; j < VN; ++j) acc[j] += v[j] * x[c[j]];
+  }
+  *reinterpret_cast<V*>(y + i0) = acc;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+ell_spmv_row_kernel(const int32_t* __restrict__ cols, const T* __restrict__ vals,
+                    const T* __restrict__ x, T* __restrict__ y, int64_t n,
+                    int width, int64_t row_begin, const int32_t* __restrict__ rows,
+                    int64_t count) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= count) return;
+  const int64_t i = rows ? (int64_t)rows[t] : row_begin + t;
+  T acc = T(0);
+#pragma unroll 4
+  for (int k = 0; k < width; ++k) {
+    const int64_t at = (int64_t)k * n + i;
+    acc += vals[at] * x[cols[at]];
+  }
+  y[i] = acc;
+}
+
+template <typename T>
+void launch_ell_spmv(const int32_t* cols, const T* vals, const T* x, T* y,
+                     int64_t n, int width, int64_t row_begin, int64_t row_end,
+                     const int32_t* rows, int64_t num_rows, hipStream_t st) {
+  constexpr int VN = PmgVec<T>::N;
+  const dim3 block(256);
+  if (rows) {
+    hipLaunchKernelGGL(ell_spmv_row_kernel<T>,
+                       dim3((unsigned)((num_rows + 255) / 256)), block, 0, st,
+                       cols, vals, x, y, n, width, (int64_t)0, rows, num_rows);
+    return;
+  }
+  int64_t head = row_begin;
+  const bool aligned = n % VN == 0 &&
+                       reinterpret_cast<uintptr_t>(vals) % 16 == 0 &&
+                       reinterpret_cast<uintptr_t>(cols) % (4 * VN) == 0 &&
+                       reinterpret_cast<uintptr_t>(y) % 16 == 0;
+  if (aligned) {
+    // the unaligned head and the tail of the range run one row per lane
+    const int64_t first = (row_begin + VN - 1) / VN * VN;
+    const int64_t nvec = first < row_end ? (row_end - first) / VN : 0;
+    if (nvec > 0) {
+      if (first > row_begin)
+        hipLaunchKernelGGL(ell_spmv_row_kernel<T>, dim3(1), block, 0, st,
+                           cols, vals, x, y, n, width, row_begin,
+                           (const int32_t*)nullptr, first - row_begin);
+      hipLaunchKernelGGL(ell_spmv_vec_kernel<T>,
+                         dim3((unsigned)((nvec + 255) / 256)), block, 0, st,
+                         cols, vals, x, y, n, width, first, nvec);
+      head = first + nvec * VN;
+    }
+  }
+  if (row_end > head)
+    hipLaunchKernelGGL(ell_spmv_row_kernel<T>,
+                       dim3((unsigned)((row_end - head + 255) / 256)), block,
+                       0, st, cols, vals, x, y, n, width, head,
+                       (const int32_t*)nullptr, row_end - head);
+}
+
 }  // namespace
 }  // namespace sfem
 
@@ -579,6 +680,32 @@ extern "C" int sfem_pmg_cg_scalars(double* scalars, int phase,
   hipLaunchKernelGGL(pmg_cg_scalars_kernel, dim3(1), dim3(256), 0,
                      as_stream(stream), scalars, phase, partials, n, maxiter,
                      tol, atol);
+  SFEM_LAUNCH_CHECK();
+  return SFEM_OK;
+}
+
+extern "C" int sfem_ell_spmv(const int32_t* cols, const void* vals,
+                             const void* x, void* y, int64_t n, int width,
+                             int64_t row_begin, int64_t row_end,
+                             const int32_t* rows, int64_t num_rows, int dtype,
+                             sfem_stream_t stream) {
+  SFEM_REQUIRE(n >= 0 && width >= 1 && num_rows >= 0 &&
+                   (rows || (0 <= row_begin && row_begin <= row_end &&
+                             row_end <= n)),
+               "sfem_ell_spmv: bad sizes or row range");
+  SFEM_REQUIRE(dtype == SFEM_F32 || dtype == SFEM_F64,
+               "sfem_ell_spmv: unknown dtype %d", dtype);
+  if (rows ? num_rows == 0 : row_end == row_begin) return SFEM_OK;
+  SFEM_REQUIRE(cols && vals && x && y, "sfem_ell_spmv: null pointer");
+  hipStream_t st = as_stream(stream);
+  if (dtype == SFEM_F64)
+    launch_ell_spmv<double>(cols, (const double*)vals, (const double*)x,
+                            (double*)y, n, width, row_begin, row_end, rows,
+                            num_rows, st);
+  else
+    launch_ell_spmv<float>(cols, (const float*)vals, (const float*)x,
+                           (float*)y, n, width, row_begin, row_end, rows,
+                           num_rows, st);
   SFEM_LAUNCH_CHECK();
   return SFEM_OK;
 }

@@ -14,6 +14,11 @@ local sum minus a correction over the O(N^(2/3)) interface nodes
 single-GPU iteration costs plus a packed neighbour exchange and two scalar
 all-reduces.  In exact arithmetic the iterates are those of the reference
 convention (x identical, r_here = QQ^T r_reference).
+
+A preconditioner must map consistent vectors to consistent vectors
+(`consistent = True`): `linalg.jacobi.JacobiPreconditioner` of the local
+operator (its diagonal is exchanged) or `linalg.pmg.PMultigridPreconditioner`
+of the local operator on a block partition.
 """
 
 from __future__ import annotations
@@ -150,13 +155,15 @@ class OverlappedHelmholtz:
 
 def make_runner(local_op, b_local, plan: comm.NeighborPlan, *, x0=None,
                 tol=1e-5, atol=0.0, maxiter=None, group=None,
-                assembled_rhs=False) -> cg_lib.CGRunner:
+                assembled_rhs=False, M=None) -> cg_lib.CGRunner:
   """CGRunner for `QQ^T A_local x = QQ^T b_local` on this rank's partition.
 
   `b_local` is the unassembled local covector (as `local_covector` returns it)
   unless `assembled_rhs`; `x0`, if given, must be consistent.  `local_op` is a
   rank-local operator (wrapped in `PartitionedOperator`) or an
-  `OverlappedHelmholtz`, which already returns the assembled result.
+  `OverlappedHelmholtz`, which already returns the assembled result.  `M`: an
+  optional preconditioner with `consistent = True` (see the module
+  docstring); a p-multigrid one makes CG stop on the global r.r.
   """
   b = b_local if assembled_rhs else comm.neighbor_exchange_(
       b_local.clone(), plan, group)
@@ -165,17 +172,18 @@ def make_runner(local_op, b_local, plan: comm.NeighborPlan, *, x0=None,
        else PartitionedOperator(local_op, plan, group))
   return cg_lib.CGRunner(
       A, b, x0, tol=tol, atol=atol,
-      maxiter=maxiter, reduce_fn=reduce_fn,
+      maxiter=maxiter, reduce_fn=reduce_fn, M=M,
       interface=plan.interface_weights(b.device, num_nodes=b.shape[0],
                                        group=group))
 
 
 def cg(local_op, b_local, plan: comm.NeighborPlan, *, x0=None, tol=1e-5,
        atol=0.0, maxiter=None, group=None, assembled_rhs=False,
-       check_every=16):
+       check_every=16, M=None):
   """Partitioned CG; returns `(x, info)` like `linalg.cg.cg` (x consistent)."""
   run = make_runner(local_op, b_local, plan, x0=x0, tol=tol, atol=atol,
-                    maxiter=maxiter, group=group, assembled_rhs=assembled_rhs)
+                    maxiter=maxiter, group=group, assembled_rhs=assembled_rhs,
+                    M=M)
   while run.issued < run.maxiter:
     for _ in range(min(check_every, run.maxiter - run.issued)):
       run.step()

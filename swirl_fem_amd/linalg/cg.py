@@ -20,6 +20,14 @@ residual, r . r <= max(tol^2 b.b, atol^2), and sums every inner product of the
 solve in a fixed order (`sfem_pmg_dot2`, `sfem_pmg_cg_scalars`); with a
 layered operator the iteration is then bitwise reproducible.
 
+On partitions (`interface`) a preconditioner is accepted when it maps
+consistent vectors to consistent vectors (`consistent = True`: Jacobi with the
+exchanged diagonal, p-multigrid on a block partition).  Every inner product is
+then the plain local sum minus the interface correction, all-reduced: r . z
+as r . r is; the fused Jacobi update corrects r . (dinv r) on the interface
+nodes only; the r.r-stopping path corrects and all-reduces its stored partial
+sums before they are added up, so every rank adds the same numbers.
+
 A preconditioner that offers `mean_projection()` (M r = r - (w.r / total) 1,
 the nullspace projection of the pressure solve) is folded into the two vector
 updates: z = M r is never stored and r . z comes out of the sums update_r takes
@@ -133,9 +141,12 @@ class CGRunner:
 
   def __init__(self, A, b, x0=None, *, tol=1e-5, atol=0.0, maxiter=None,
                M=None, dot_fn=None, reduce_fn=None, interface=None):
-    if interface is not None and (M is not None or dot_fn is not None):
+    if interface is not None and (
+        dot_fn is not None or
+        (M is not None and not getattr(M, 'consistent', False))):
       raise ValueError('interface weights apply to the plain dot of consistent '
-                       'vectors (M = None, dot_fn = None)')
+                       'vectors (M = None or a preconditioner that maps '
+                       'consistent vectors to consistent ones, dot_fn = None)')
     b_leaves = [_as_vec(l) for l in _leaves(b)]
     if not all(l.is_cuda for l in b_leaves):
       raise RuntimeError('swirl_fem_amd.linalg.cg runs on MI355X device '
@@ -170,7 +181,6 @@ class CGRunner:
     # stop on r.r with fixed-order sums: the preconditioner asks for it
     self.rr_stop = None
     if (getattr(M, 'stops_on_residual', False) and dot_fn is None and
-        reduce_fn is None and interface is None and
         isinstance(self.r, torch.Tensor) and self.r.dim() == 1):
       self._residual_stop_setup(A, b, z)
     # r.r spread over 64 slots: update_r then streams with 128 workgroups per
@@ -200,7 +210,7 @@ class CGRunner:
     probe = getattr(M, 'jacobi_diagonal', None)
     if (probe is not None and self.mean is None and self.rr_stop is None and
         dot_fn is None and
-        reduce_fn is None and interface is None and
+        (interface is not None or reduce_fn is None) and
         isinstance(self.r, torch.Tensor) and
         switches.get('SFEM_FUSED_JACOBI') != '0'):
       dinv = probe()
@@ -217,6 +227,13 @@ class CGRunner:
         ncomp = None       # (row-major fields: M is called as a function)
       if ncomp is not None and self.r.shape[0] == n:
         self.jacobi = (dinv, ncomp)
+    # r . (dinv r) of consistent vectors: its interface correction is the
+    # r . r one with the weights w dinv (dinv is the same on every holder)
+    self.jacobi_interface = None
+    if self.jacobi is not None and interface is not None:
+      idx, w = interface
+      self.jacobi_interface = (
+          idx, (w * self.jacobi[0][idx].double()).contiguous())
     # Layered assembly: the operator leaves the contributions of shared nodes
     # in layers of an extended Ap (plain stores: no atomics, no cleared range)
     # and `r -= alpha Ap` adds them up where it streams Ap anyway, in a fixed
@@ -272,7 +289,8 @@ class CGRunner:
     dev = self.r.device
     G = RESIDUAL_STOP_GROUPS
     layered = None
-    if hasattr(A, 'apply_layered_with_dot') and hasattr(A, 'layer_plan'):
+    if (hasattr(A, 'apply_layered_with_dot') and hasattr(A, 'layer_plan') and
+        self.reduce_fn is None and self.interface is None):
       layered = A.layer_plan()
     waves = A.layered_dot_slots() if layered is not None else 0
     self.rr_stop = dict(
@@ -289,11 +307,26 @@ class CGRunner:
     st = self.rr_stop
     G, parts = st['groups'], st['parts']
     args = (self.maxiter, self.tol, self.atol)
-    _ops.pmg_dot2(b, b, None, parts, G)
+    self._dot2(b, b, None)
     _ops.pmg_cg_scalars(self.s.t, 3, parts, G, *args)
-    _ops.pmg_dot2(self.r, self.r, layout.like(z, self.r).contiguous(), parts,
-                  G)
+    self._dot2(self.r, self.r, layout.like(z, self.r).contiguous())
     _ops.pmg_cg_scalars(self.s.t, 2, parts, G, *args)
+
+  def _dot2(self, a, b, c):
+    """Stored partial sums of a.b (and a.c) for `sfem_pmg_cg_scalars`; on
+    partitions the interface correction goes into the first partial of each
+    and the partials are all-reduced, so every rank adds the same numbers."""
+    st = self.rr_stop
+    G, parts = st['groups'], st['parts']
+    _ops.pmg_dot2(a, b, c, parts, G)
+    if self.interface is not None:
+      idx, w = self.interface
+      if idx.numel():
+        _ops.dot_indexed(a, b, idx, w, parts, 0, -1.0)
+        if c is not None:
+          _ops.dot_indexed(a, c, idx, w, parts, G, -1.0)
+    if self.reduce_fn is not None:
+      self.reduce_fn(parts[:G if c is None else 2 * G])
 
   def _step_residual_stop(self):
     """One PCG iteration that stops on r.r (see the module docstring)."""
@@ -307,11 +340,11 @@ class CGRunner:
                                masks=st['layered'].masks)
     else:
       Ap = layout.like(self.A(self.p), self.r).contiguous()
-      _ops.pmg_dot2(self.p, Ap, None, parts, G)
+      self._dot2(self.p, Ap, None)
       _ops.pmg_cg_scalars(s.t, 0, parts, G, *args)
       _ops.cg_update_r(self.r, Ap, s.t, 0)
     z = layout.like(self.M(self.r), self.r).contiguous()
-    _ops.pmg_dot2(self.r, self.r, z, parts, G)
+    self._dot2(self.r, self.r, z)
     _ops.pmg_cg_scalars(s.t, 4, parts, G, *args)
     _ops.cg_update_xp(self._x, self.p, z, s.t)
     _ops.pmg_cg_scalars(s.t, 1, parts, G, *args)
@@ -495,6 +528,8 @@ class CGRunner:
           isinstance(self.r, torch.Tensor)):
         # the preconditioner accumulates r . M r itself (slot is zero here)
         z = M.apply_with_dot(self.r, s.t, S.GAMMA_NEW)
+        if self.interface is not None:
+          s.interface_correction(S.GAMMA_NEW, self.r, z, self.interface)
         if reduce_fn is not None:
           reduce_fn(s.t[S.GAMMA_NEW:S.GAMMA_NEW + 1])
       elif dot_fn is None:
@@ -502,6 +537,8 @@ class CGRunner:
         for xx, yy in zip(_leaves(self.r), _leaves(z)):
           _ops.dot(layout.flat(xx), layout.flat(layout.like(yy, xx)), s.t,
                    S.GAMMA_NEW, accumulate=True)
+        if self.interface is not None:
+          s.interface_correction(S.GAMMA_NEW, self.r, z, self.interface)
         if reduce_fn is not None:
           reduce_fn(s.t[S.GAMMA_NEW:S.GAMMA_NEW + 1])
       else:
@@ -541,6 +578,14 @@ class CGRunner:
       _ops.cg_update_r_jacobi(layout.flat(self.r),
                               layout.flat(layout.like(Ap, self.r)), dinv, s.t,
                               ncomp)
+    if self.reduce_fn is not None:
+      # the striped r . (dinv r) into [2], corrected on the interface nodes,
+      # summed over the partitions
+      _ops.cg_scalars(s.t, 7, *args)
+      if self.jacobi_interface is not None:
+        s.interface_correction(_Scalars.GAMMA_NEW, self.r, self.r,
+                               self.jacobi_interface)
+      self.reduce_fn(s.t[_Scalars.GAMMA_NEW:_Scalars.GAMMA_NEW + 1])
     _ops.cg_update_xp_jacobi(layout.flat(self._x), layout.flat(self.p),
                              layout.flat(self.r), dinv, s.t, ncomp)
     if not merged:

@@ -48,6 +48,9 @@ class JacobiPreconditioner:
   """
 
   capturable = True
+  # consistent vectors in, consistent vectors out (on a partition dinv is the
+  # same on every holder of a node): partitioned CG accepts it
+  consistent = True
 
   def __init__(self, op_or_diag, lambda0=0.0, lambda1=1.0, strict=True,
                reduce_max=None):

@@ -26,7 +26,8 @@ Hierarchy (setup):
   one bit per local node (`sfem_pmg_prolong` writes through it).
 
 Operators: the smoother of the finest level applies the operator CG solves
-with; a collocated one through a coloured-assembly copy, a two-grid one
+with; a collocated one through a coloured-assembly copy (on a partition the
+operator itself, and default assembly on the coarse levels), a two-grid one
 element-locally with a fixed-order sum (`sfem_scatter_csr`), so that every
 sum in the V-cycle has a fixed order and the preconditioner is bitwise
 reproducible.  Coarse levels are collocated GLL `HelmholtzOperator`s with the
@@ -36,6 +37,25 @@ same (lambda0, lambda1), coloured assembly.
 stops on the true-residual norm r.r <= max(tol^2 b.b, atol^2) instead of the
 reference's r.Mr (an energy norm when M ~ A^-1), with inner products summed in
 a fixed order.
+
+Block partitions (`distributed.blocks.build_block_partition`, world > 1): every
+rank builds the hierarchy of its own block, and every vector of the V-cycle is
+*consistent* (equal on all ranks that hold a node), as in the partitioned CG:
+* each coarse mesh carries a coarse `NeighborPlan` derived from the fine one
+  without communication (`coarse_plan`): a coarse node is shared with rank q
+  iff all the fine nodes of its key are in the fine list for q, and the shared
+  coarse nodes are ordered by the sorted positions of those fine nodes in that
+  list -- the same on both sides;
+* level operators are QQ^T A_local (the exchange after the local apply);
+* restriction: every fine node also has one owning RANK, the lowest that holds
+  it (`restrict_owner`), so the local restrictions summed by the coarse
+  exchange are the global P^T r; prolongation writes every local fine node;
+* Lanczos runs with global inner products from a start vector that is a
+  function of the node coordinates, so every rank gets the same estimates;
+* the coarsest level keeps its rank-local (unassembled) order-1 matrix and
+  applies the polynomial of `sfem_ell_chebyshev` step by step: y = QQ^T A_loc x
+  (`sfem_ell_spmv` on the interface rows, exchange posted, interior rows,
+  exchange finished), then `sfem_cheb_step`.
 """
 
 from __future__ import annotations
@@ -57,6 +77,12 @@ SMOOTHER_HIGH = 1.1
 LANCZOS_STEPS = 16          # estimate of lambda_max(D^-1 A) per level
 COARSE_REDUCTION = 0.1      # the coarse polynomial's error bound (steps=None)
 COARSE_MAX_STEPS = 256
+# Lanczos on the partitioned coarse matrix: checked every COARSE_LANCZOS_CHECK
+# steps, stopped when both extreme Ritz values move less than
+# COARSE_LANCZOS_RTOL, at most COARSE_LANCZOS_MAX steps (see `_coarse_bounds`)
+COARSE_LANCZOS_CHECK = 10
+COARSE_LANCZOS_RTOL = 1e-3
+COARSE_LANCZOS_MAX = 300
 
 
 def default_orders(p: int) -> list:
@@ -91,8 +117,18 @@ def _flat(idx, P):
 
 
 def _check_mesh(mesh):
-  if mesh.axis_name is not None or mesh.neighbor_plan is not None:
-    raise NotImplementedError('p-multigrid on a partitioned mesh')
+  plan = mesh.neighbor_plan
+  if plan is None and mesh.axis_name is not None:
+    raise NotImplementedError(
+        'p-multigrid on a partitioned mesh without a NeighborPlan (the coarse '
+        'exchange is derived from the fine plan)')
+  if plan is not None and mesh.axis_name is None:
+    raise NotImplementedError(
+        'p-multigrid on a partitioned mesh without an axis_name')
+  if plan is not None and plan.has_local_images:
+    raise NotImplementedError(
+        'p-multigrid on a partitioned mesh whose plan has local periodic '
+        'images (a direction that is periodic with a single block)')
   if mesh._cache.get('replicas', 1) > 1:
     raise NotImplementedError('p-multigrid on an ensemble (Mesh.replicate)')
   if mesh.ndim not in (2, 3):
@@ -130,18 +166,7 @@ def coarse_numbering(elements: np.ndarray, reps: np.ndarray | None, ndim: int,
         creps[:, sel] = ids
       start += E * sel.size
       continue
-    # the 2^k fine nodes around each coarse node (k directions inside)
-    combos = []
-    for bits in range(2 ** k):
-      f = np.empty((sel.size, ndim), dtype=np.int64)
-      for j, s in enumerate(sel):
-        axes = np.nonzero(inner[s])[0]
-        for a in range(ndim):
-          f[j, a] = (lo if a not in axes else
-                     (hi if (bits >> list(axes).index(a)) & 1 else lo))[
-                         cloc[s, a]]
-      combos.append(_flat(f, Pf))
-    cols = np.stack(combos, axis=-1)                         # (ns, 2^k)
+    cols = _key_columns(sel, k, cloc, inner, lo, hi, ndim, Pf)
     keys = np.sort(elements[:, cols], axis=-1).reshape(-1, 2 ** k)
     ids, n_new = _number_rows(keys)
     celems[:, sel] = start + ids.reshape(E, sel.size)
@@ -154,6 +179,82 @@ def coarse_numbering(elements: np.ndarray, reps: np.ndarray | None, ndim: int,
       creps[:, sel] = start + low[rid].reshape(E, sel.size)
     start += n_new
   return celems, creps, start
+
+
+def _key_columns(sel, k, cloc, inner, lo, hi, ndim, Pf):
+  """(ns, 2^k) fine element-local columns of the key of every coarse local
+  node in `sel` (k directions inside the element): the 2^k fine nodes around
+  it."""
+  combos = []
+  for bits in range(2 ** k):
+    f = np.empty((sel.size, ndim), dtype=np.int64)
+    for j, s in enumerate(sel):
+      axes = np.nonzero(inner[s])[0]
+      for a in range(ndim):
+        f[j, a] = (lo if a not in axes else
+                   (hi if (bits >> list(axes).index(a)) & 1 else lo))[
+                       cloc[s, a]]
+    combos.append(_flat(f, Pf))
+  return np.stack(combos, axis=-1)
+
+
+def coarse_keys(elements, celems: np.ndarray, num_coarse: int, ndim: int,
+                pf: int, pc: int) -> np.ndarray:
+  """(num_coarse, 2^ndim) int64: the fine nodes of every coarse node's key
+  (those of `coarse_numbering`, sorted, padded with -1; all -1 for element
+  interiors, which no other element or rank shares)."""
+  Pc = pc + 1
+  lo, hi = _bracket(pc, pf)
+  cloc = _lex((Pc,) * ndim)
+  inner = (cloc > 0) & (cloc < pc)
+  k_of = inner.sum(axis=1)
+  out = np.full((num_coarse, 2 ** ndim), -1, dtype=np.int64)
+  for k in range(ndim):
+    sel = np.nonzero(k_of == k)[0]
+    if not sel.size:
+      continue
+    cols = _key_columns(sel, k, cloc, inner, lo, hi, ndim, Pf=pf + 1)
+    keys = np.sort(elements[:, cols], axis=-1)               # (E, ns, 2^k)
+    out[celems[:, sel].reshape(-1), :2 ** k] = keys.reshape(-1, 2 ** k)
+  return out
+
+
+def coarse_plan(fine_plan, keys: np.ndarray):
+  """The coarse `NeighborPlan` from the fine one, without communication.
+
+  For neighbour q the fine list `indices[q]` numbers the fine nodes shared
+  with q in an order both sides agree on.  A coarse node is shared with q iff
+  every fine node of its key (`coarse_keys`) is in that list, and the shared
+  coarse nodes are ordered by the sorted tuple of those list positions: the
+  same fine nodes give the same tuple on both sides, so the same order."""
+  from swirl_fem_amd.distributed import comm
+  nf = max([int(np.max(ix)) + 1 for ix in fine_plan.indices if len(ix)] +
+           [int(keys.max()) + 1 if keys.size else 0])
+  valid = keys >= 0
+  neighbors, indices = [], []
+  for q, ix in zip(fine_plan.neighbors, fine_plan.indices):
+    pos = np.full(nf, -1, dtype=np.int64)
+    pos[np.asarray(ix, dtype=np.int64)] = np.arange(len(ix))
+    kp = np.where(valid, pos[np.where(valid, keys, 0)], -1)
+    shared = valid[:, 0] & ((kp >= 0) | ~valid).all(axis=1)
+    nodes = np.nonzero(shared)[0]
+    tup = np.sort(kp[nodes], axis=1)             # -1 padding sorts first
+    order = np.lexsort(tup.T[::-1]) if nodes.size else nodes
+    if nodes.size:
+      neighbors.append(int(q))
+      indices.append(nodes[order].astype(np.int32))
+  return comm.NeighborPlan(rank=fine_plan.rank, neighbors=neighbors,
+                           indices=indices)
+
+
+def rank_owned(plan, num_nodes: int) -> np.ndarray:
+  """(num_nodes,) bool: this rank owns the node for the restriction -- it is
+  the lowest-numbered rank that holds it."""
+  mine = np.ones(num_nodes, dtype=bool)
+  for q, ix in zip(plan.neighbors, plan.indices):
+    if q < plan.rank:
+      mine[np.asarray(ix, dtype=np.int64)] = False
+  return mine
 
 
 def _number_rows(keys: np.ndarray):
@@ -213,16 +314,20 @@ def encode_rows(elements: torch.Tensor, dirichlet: torch.Tensor | None):
   return torch.where(dirichlet[elements.to(torch.int64)], ~el, el).contiguous()
 
 
-def owner_bits(elements: torch.Tensor, num_nodes: int) -> torch.Tensor:
+def owner_bits(elements: torch.Tensor, num_nodes: int,
+               node_mask: torch.Tensor | None = None) -> torch.Tensor:
   """(E, ceil(n / 32)) int32 words (bit t of word t // 32: element e owns its
   local node t): every node is owned by the lowest-numbered element that
-  contains it."""
+  contains it.  `node_mask` (num_nodes,) bool: nodes outside it have no owner
+  at all (the restriction of a partition: nodes another rank owns)."""
   E, n = elements.shape
   el = elements.to(torch.int64)
   eidx = torch.arange(E, device=el.device)[:, None].expand(E, n)
   first = torch.full((num_nodes,), E, dtype=torch.int64, device=el.device)
   first.scatter_reduce_(0, el.reshape(-1), eidx.reshape(-1), reduce='amin')
   owned = first[el] == eidx
+  if node_mask is not None:
+    owned = owned & node_mask.to(el.device)[el]
   words = (n + 31) // 32
   pad = torch.zeros((E, words * 32), dtype=torch.int64, device=el.device)
   pad[:, :n] = owned.to(torch.int64)
@@ -242,7 +347,9 @@ def coarse_mesh(mesh, pc: int):
   if not 1 <= pc < pf:
     raise ValueError(f'coarse order {pc} must be in 1..{pf - 1}')
   dev = mesh.device
-  periodic = (mesh.exchange_gather_indices is not None and
+  plan = mesh.neighbor_plan
+  # (on a partition the exchange indices are the plan's, not periodic images)
+  periodic = (plan is None and mesh.exchange_gather_indices is not None and
               mesh.exchange_gather_indices.numel() > 0)
   # only the fine columns the keys need travel to the host
   Pf = pf + 1
@@ -265,7 +372,7 @@ def coarse_mesh(mesh, pc: int):
   # move affine elements outside classify_geometry's tolerance)
   J = torch.as_tensor(_kron(interpolation_1d_geometry(pf, pc), d),
                       dtype=torch.float64, device=dev)       # (nc_loc, nf_loc)
-  xe = mesh.element_coords().double()                        # (E, nf, d)
+  xe = mesh.node_coords.double()[mesh.elements.to(torch.int64)]  # (E, nf, d)
   xc_loc = torch.einsum('cf,efd->ecd', J, xe).to(mesh.dtype)
   E, ncl = celems.shape
   first = torch.full((nc,), E, dtype=torch.int64, device=dev)
@@ -282,6 +389,12 @@ def coarse_mesh(mesh, pc: int):
     gi, ui = gather_scatter.get_exchange_indices(node_indices)
     kw = dict(node_indices=node_indices.astype(np.int32),
               exchange_gather_indices=gi, exchange_unique_indices=ui)
+  if plan is not None:
+    cplan = coarse_plan(plan, coarse_keys(el_full, celems, nc, d, pf, pc))
+    kw = dict(axis_name=mesh.axis_name, neighbor_plan=cplan,
+              exchange_gather_indices=(
+                  np.concatenate(cplan.indices).astype(np.int32)
+                  if cplan.indices else None))
   cmesh = Mesh.create(
       node_coords=coords, elements=celems.astype(np.int32),
       gridpoints_1d=Nodes1D.create(pc + 1, NodeType.GAUSS_LOBATTO_LEGENDRE),
@@ -357,13 +470,25 @@ class PMultigridPreconditioner:
   (`sfem_ell_chebyshev`, the spectrum bounds from Lanczos at setup).  No host
   synchronisation: `capturable`.  The result lives in a buffer of the
   preconditioner, valid until the next call.
+
+  On a block partition (the mesh has a `neighbor_plan`; collocated GLL
+  `HelmholtzOperator` only) M maps consistent vectors to consistent vectors
+  (`consistent`) and is the V-cycle of the whole mesh; `group` is the process
+  group of the exchanges and reductions.  Its exchanges go through the host
+  transport: not `capturable`.
+
+  `bounds`: None, or the spectrum estimates to use instead of computing them,
+  as `spectral_bounds()` returns them (e.g. from the preconditioner of the
+  same problem on one rank): {'lam_max': one per smoothed level, 'coarse':
+  (lmin, lmax) of the coarsest level's polynomial}.
   """
 
   capturable = True
   stops_on_residual = True
+  consistent = True        # consistent vectors in, consistent vectors out
 
   def __init__(self, op, lambda0=0.0, lambda1=1.0, *, orders=None,
-               smoother_degree=2, coarse_steps=None):
+               smoother_degree=2, coarse_steps=None, bounds=None, group=None):
     from swirl_fem_amd.core import operators
     if not isinstance(op, (operators.HelmholtzOperator,
                            operators.TwoGridHelmholtzOperator)):
@@ -372,6 +497,12 @@ class PMultigridPreconditioner:
     fes = op.fespace
     mesh = fes.mesh
     _check_mesh(mesh)
+    self.plan, self.group = mesh.neighbor_plan, group
+    if self.plan is not None:
+      if not isinstance(op, operators.HelmholtzOperator):
+        raise NotImplementedError('p-multigrid on a partitioned mesh takes a '
+                                  'collocated HelmholtzOperator')
+      self.capturable = False
     p = mesh.order
     orders = default_orders(p) if orders is None else [int(o) for o in orders]
     if (orders[0] != p or orders[-1] != 1 or
@@ -388,18 +519,118 @@ class PMultigridPreconditioner:
     for i, pc in enumerate(orders[1:]):
       self.levels.append(self._coarse_level(self.levels[-1], pc,
                                             i == len(orders) - 2))
-    for lev in self.levels[:-1]:
-      lev.lam_max = self._lanczos_max(lev)
+    if bounds is not None and len(bounds['lam_max']) != len(orders) - 1:
+      raise ValueError(f"bounds: {len(bounds['lam_max'])} lam_max values for "
+                       f'{len(orders) - 1} smoothed levels')
+    for i, lev in enumerate(self.levels[:-1]):
+      lev.lam_max = (float(bounds['lam_max'][i]) if bounds is not None
+                     else self._lanczos_max(lev))
       lev.cheb = _cheb_coefficients(SMOOTHER_LOW * lev.lam_max,
                                     SMOOTHER_HIGH * lev.lam_max, self.degree)
-    self._coarse_setup(self.levels[-1], coarse_steps)
+    coarse = None if bounds is None else tuple(bounds['coarse'])
+    if self.plan is None:
+      self._coarse_setup(self.levels[-1], coarse_steps, coarse)
+    else:
+      self._coarse_setup_partitioned(self.levels[-1], coarse_steps, coarse)
+
+  def spectral_bounds(self):
+    """The spectrum estimates this preconditioner uses (the `bounds` argument
+    that reproduces them)."""
+    return {'lam_max': [lev.lam_max for lev in self.levels[:-1]],
+            'coarse': tuple(self.coarse_bounds)}
+
+  # ------------------------------------------------------------ partitions
+  def _exchange_(self, u, mesh):
+    """QQ^T in place (nothing without a partition)."""
+    if mesh.neighbor_plan is None:
+      return u
+    from swirl_fem_amd.distributed import comm
+    return comm.neighbor_exchange_(u, mesh.neighbor_plan, self.group)
+
+  def _allreduce(self, t):
+    from swirl_fem_amd.distributed import comm
+    return comm.all_reduce_sum_(t, self.group)
+
+  def _gdots(self, lev, pairs):
+    """Global inner products of consistent fp64 vectors (one all-reduce):
+    the local dot minus the interface terms weighted by 1 - 1/holders."""
+    idx, w = lev.mesh.neighbor_plan.interface_weights(self.device)
+    vals = torch.stack([torch.dot(a, b) - (w * a[idx] * b[idx]).sum()
+                        for a, b in pairs])
+    return self._allreduce(vals).tolist()
+
+  def _start_vector(self, lev, mask):
+    """A fixed pseudo-random vector (fp64, consistent): on a partition a
+    hash of the node coordinates, so that every rank starts Lanczos from the
+    restriction of one global vector; else the seeded generator of one rank."""
+    n = lev.mesh.num_nodes
+    if lev.mesh.neighbor_plan is None:
+      g = torch.Generator().manual_seed(12345)
+      v = torch.rand(n, generator=g, dtype=torch.float64).to(self.device) - 0.5
+      return v * mask
+    q = np.round(lev.mesh.node_coords.double().cpu().numpy() *
+                 2.0 ** 20).astype(np.int64)
+    h = np.zeros(n, dtype=np.uint64)
+    for a, m in zip(range(q.shape[1]), (0x9E3779B97F4A7C15, 0xC2B2AE3D27D4EB4F,
+                                         0x165667B19E3779F9)):
+      h = (h ^ (q[:, a].astype(np.uint64) * np.uint64(m))) * np.uint64(
+          0xFF51AFD7ED558CCD)
+      h ^= h >> np.uint64(33)
+    v = torch.as_tensor((h >> np.uint64(11)).astype(np.float64) / 2.0 ** 53 -
+                        0.5, device=self.device) * mask
+    # average the copies of shared nodes (equal unless coordinates computed
+    # in different elements round differently)
+    idx, w = lev.mesh.neighbor_plan.interface_weights(self.device)
+    v[idx] = v[idx] * (1.0 - w)
+    return self._exchange_(v, lev.mesh)
+
+  def _lanczos(self, lev, apply_fn, sq, steps, check=None):
+    """Ritz values of D^-1/2 A D^-1/2 (`apply_fn(u, out)` = A u, `sq` =
+    D^-1/2, 0 on Dirichlet rows) after at most `steps` Lanczos steps with the
+    global inner product; `check(k, ritz)` may end it early."""
+    n = sq.numel()
+    partitioned = lev.mesh.neighbor_plan is not None
+    dot = ((lambda a, b: self._gdots(lev, [(a, b)])[0]) if partitioned
+           else (lambda a, b: float(torch.dot(a, b))))
+    v = self._start_vector(lev, (sq > 0).double())
+    v = v / math.sqrt(dot(v, v))
+    v_prev = torch.zeros_like(v)
+    alphas, betas = [], []
+    beta = 0.0
+    ax = torch.empty(n, dtype=self.dtype, device=self.device)
+    interior = int((sq > 0).sum())
+    if partitioned:
+      t = torch.tensor([float(interior)], dtype=torch.float64,
+                       device=self.device)
+      interior = int(self._allreduce(t).item())    # (an upper bound)
+    for k in range(min(steps, interior)):
+      apply_fn((sq * v).to(self.dtype).contiguous(), ax)
+      w = sq * ax.double()
+      alpha = dot(w, v)
+      w = w - alpha * v - beta * v_prev
+      alphas.append(alpha)
+      beta = math.sqrt(max(dot(w, w), 0.0))
+      if beta <= 1e-14 * abs(alpha):
+        break
+      betas.append(beta)
+      v_prev, v = v, w / beta
+      if check is not None and check(k + 1, alphas, betas):
+        break
+    k = len(alphas)
+    T = np.diag(alphas) + np.diag(betas[:k - 1], 1) + np.diag(betas[:k - 1], -1)
+    return np.linalg.eigvalsh(T)
 
   # ---------------------------------------------------------------- setup
   def _fine_level(self, op, dirichlet):
     from swirl_fem_amd.core import operators
     fes, mesh = op.fespace, op.fespace.mesh
     l0, l1 = self.lambda0, self.lambda1
-    if isinstance(op, operators.HelmholtzOperator):
+    if isinstance(op, operators.HelmholtzOperator) and self.plan is not None:
+      # a partition: the operator CG solves with (the exchange adds with
+      # atomics, so the fixed-order coloured copy would buy nothing here)
+      apply_fn = lambda u, out: self._exchange_(op.apply(u, l0, l1, out=out),
+                                                mesh)
+    elif isinstance(op, operators.HelmholtzOperator):
       colored = fes.helmholtz_operator(dirichlet, assembly='colored')
       self._fine_colored = colored
       apply_fn = lambda u, out: colored.apply(u, l0, l1, out=out)
@@ -439,16 +670,21 @@ class PMultigridPreconditioner:
         cmesh, Quadrature1D.create(pc + 1, NodeType.GAUSS_LOBATTO_LEGENDRE))
     l0, l1 = self.lambda0, self.lambda1
     # (the coarsest level only assembles its element matrices)
-    cop = fes.helmholtz_operator(cdir, assembly='auto' if coarsest
-                                 else 'colored')
+    cop = fes.helmholtz_operator(cdir, assembly='auto' if (
+        coarsest or self.plan is not None) else 'colored')
     dinv = self._dinv(cop.diagonal(l0, l1))
-    lev = _Level(cmesh, cop, lambda u, out: cop.apply(u, l0, l1, out=out),
-                 cdir, dinv)
+    lev = _Level(cmesh, cop, lambda u, out: self._exchange_(
+        cop.apply(u, l0, l1, out=out), cmesh), cdir, dinv)
     lev.fespace = fes
     offsets, slots = cmesh.assembly_plan().csr()
+    owner = owner_bits(fel, fmesh.num_nodes)
+    rowner = owner
+    if fmesh.neighbor_plan is not None:
+      rowner = owner_bits(fel, fmesh.num_nodes, torch.as_tensor(
+          rank_owned(fmesh.neighbor_plan, fmesh.num_nodes)))
     fine.transfer = dict(
         cidx=encode_rows(celems, cdir), fidx=encode_rows(fel, fine.dirichlet),
-        owner=owner_bits(fel, fmesh.num_nodes),
+        owner=owner, restrict_owner=rowner,
         mat=torch.as_tensor(interpolation_1d(pc, pf), dtype=self.dtype,
                             device=self.device).contiguous(),
         local=torch.zeros(celems.numel(), dtype=self.dtype,
@@ -459,6 +695,9 @@ class PMultigridPreconditioner:
   def _lanczos_max(self, lev):
     """Largest eigenvalue of D^-1 A (interior rows) from LANCZOS_STEPS steps
     of Lanczos on D^-1/2 A D^-1/2 from a fixed start vector."""
+    if lev.mesh.neighbor_plan is not None:
+      sq = lev.dinv.double().sqrt()
+      return float(self._lanczos(lev, lev.apply, sq, LANCZOS_STEPS).max())
     sq = lev.dinv.double().sqrt()
     n = sq.numel()
     g = torch.Generator().manual_seed(12345)
@@ -484,11 +723,11 @@ class PMultigridPreconditioner:
     T = np.diag(alphas) + np.diag(betas[:k - 1], 1) + np.diag(betas[:k - 1], -1)
     return float(np.linalg.eigvalsh(T).max())
 
-  def _coarse_setup(self, lev, steps):
-    """The order-1 matrix in ELL form (Dirichlet rows and columns zero) and
-    the bounds of its Jacobi-scaled spectrum."""
+  def _local_matrix(self, lev):
+    """The order-1 matrix of this rank's elements (CSR, fp64; Dirichlet rows
+    and columns zero).  On a partition its interface rows are this rank's
+    share only."""
     import scipy.sparse as sp
-    import scipy.sparse.linalg as spla
     mesh = lev.mesh
     E, n = mesh.elements.shape
     N = mesh.num_nodes
@@ -509,6 +748,119 @@ class PMultigridPreconditioner:
       keep = (~lev.dirichlet).cpu().numpy().astype(np.float64)
       A = (sp.diags(keep) @ A @ sp.diags(keep)).tocsr()
       A.eliminate_zeros()
+    return A
+
+  def _store_ell(self, lev, A, dinv):
+    """ELL form of A (column-major) and the coarse work vectors."""
+    N = A.shape[0]
+    width = int(np.diff(A.indptr).max()) if A.nnz else 1
+    ecols = np.repeat(np.arange(N)[:, None], width, axis=1)
+    evals = np.zeros((N, width))
+    row = np.repeat(np.arange(N), np.diff(A.indptr))
+    slot = np.arange(A.nnz) - np.repeat(A.indptr[:-1], np.diff(A.indptr))
+    ecols[row, slot] = A.indices
+    evals[row, slot] = A.data
+    lev.ell_cols = torch.as_tensor(ecols.T.copy(), dtype=torch.int32,
+                                   device=self.device).contiguous()
+    lev.ell_vals = torch.as_tensor(evals.T.copy(), dtype=self.dtype,
+                                   device=self.device).contiguous()
+    lev.ell_dinv = torch.as_tensor(dinv, dtype=self.dtype, device=self.device)
+    lev.ell_work = torch.zeros(3 * N, dtype=self.dtype, device=self.device)
+
+  def _steps_for(self, steps):
+    if steps is None:
+      kappa = self.coarse_bounds[1] / self.coarse_bounds[0]
+      steps = math.ceil(0.5 * math.sqrt(kappa) *
+                        math.log(2.0 / COARSE_REDUCTION))
+      steps = max(2, min(COARSE_MAX_STEPS, steps))
+    return int(steps)
+
+  def _coarse_setup_partitioned(self, lev, steps, bounds):
+    """The rank-local order-1 matrix in ELL form, the assembled (exchanged)
+    diagonal, the interface / interior row lists of the overlapped step, and
+    the bounds of the Jacobi-scaled spectrum of the global matrix.
+
+    The bounds come from Lanczos on D^-1/2 A D^-1/2 with global inner
+    products, run until both extreme Ritz values change by less than
+    COARSE_LANCZOS_RTOL over COARSE_LANCZOS_CHECK steps (at most
+    COARSE_LANCZOS_MAX).  That is enough because the two bounds matter
+    differently: the largest Ritz value converges first (a well-separated
+    end of the spectrum: error ~ exp(-2 k sqrt(gap))), and the 5 % margin
+    above it keeps the polynomial positive; the smallest needs about
+    sqrt(kappa) steps (~100 for the order-1 matrix of a 128^3-element box),
+    and an estimate that is still too large leaves the polynomial positive
+    definite -- it only weakens the coarse solve (see `_coarse_setup`)."""
+    A = self._local_matrix(lev)
+    N = A.shape[0]
+    diag = self._exchange_(torch.as_tensor(A.diagonal(), dtype=torch.float64,
+                                           device=self.device), lev.mesh)
+    dinv = torch.where(diag > 0, 1.0 / torch.where(diag > 0, diag,
+                                                   torch.ones_like(diag)),
+                       torch.zeros_like(diag))
+    self._store_ell(lev, A, dinv.cpu().numpy())
+    iface = np.zeros(N, dtype=bool)
+    iface[lev.mesh.neighbor_plan.interface_nodes('cpu').numpy()] = True
+    lev.rows_iface = torch.as_tensor(np.nonzero(iface)[0].astype(np.int32),
+                                     device=self.device)
+    lev.rows_inner = torch.as_tensor(np.nonzero(~iface)[0].astype(np.int32),
+                                     device=self.device)
+    if bounds is None:
+      last = {}
+
+      def check(k, alphas, betas):
+        if k % COARSE_LANCZOS_CHECK:
+          return False
+        T = (np.diag(alphas) + np.diag(betas[:k - 1], 1) +
+             np.diag(betas[:k - 1], -1))
+        ev = np.linalg.eigvalsh(T)
+        prev, last['ev'] = last.get('ev'), (ev[0], ev[-1])
+        return prev is not None and all(
+            abs(a - b) <= COARSE_LANCZOS_RTOL * abs(b)
+            for a, b in zip(last['ev'], prev))
+
+      apply_fn = lambda u, out: self._coarse_matvec(lev, u, out)
+      ev = self._lanczos(lev, apply_fn, dinv.sqrt(), COARSE_LANCZOS_MAX, check)
+      lmin, lmax = float(ev[0]), float(ev[-1])
+      if not lmin > 1e-12 * lmax:
+        raise NotImplementedError(
+            'p-multigrid needs a positive definite operator (the coarse '
+            'matrix is singular: no Dirichlet nodes and lambda0 = 0?)')
+      bounds = (0.9 * lmin, 1.05 * lmax)
+    self.coarse_bounds = tuple(float(b) for b in bounds)
+    self.coarse_steps = self._steps_for(steps)
+    lev.coarse_cheb = _cheb_coefficients(*self.coarse_bounds,
+                                         self.coarse_steps)
+
+  def _coarse_matvec(self, lev, x, out):
+    """out = QQ^T A_loc x: interface rows, exchange posted, interior rows,
+    exchange finished."""
+    from swirl_fem_amd.distributed import comm
+    _ops.ell_spmv(lev.ell_cols, lev.ell_vals, x, out, rows=lev.rows_iface)
+    handle = comm.neighbor_exchange_start(out, lev.mesh.neighbor_plan,
+                                          self.group)
+    _ops.ell_spmv(lev.ell_cols, lev.ell_vals, x, out, rows=lev.rows_inner)
+    return comm.neighbor_exchange_finish(handle, out)
+
+  def _coarse_partitioned(self, lev, b):
+    """The polynomial of `sfem_ell_chebyshev` (same bounds and steps) on the
+    global order-1 matrix, one overlapped product per step."""
+    x, d, ax, dinv = lev.x, lev.d, lev.ax, lev.ell_dinv
+    for k, (a, c) in enumerate(lev.coarse_cheb):
+      if k == 0:
+        _ops.cheb_step(x, d, None, b, dinv, None, 0.0, c, _ops.CHEB_FIRST)
+        continue
+      self._coarse_matvec(lev, x, ax)
+      _ops.cheb_step(x, d, ax, b, dinv, None, a, c, _ops.CHEB_GENERAL)
+    return x
+
+  def _coarse_setup(self, lev, steps, bounds=None):
+    """The order-1 matrix in ELL form (Dirichlet rows and columns zero) and
+    the bounds of its Jacobi-scaled spectrum (`bounds`: given instead)."""
+    import scipy.sparse as sp
+    import scipy.sparse.linalg as spla
+    mesh = lev.mesh
+    N = mesh.num_nodes
+    A = self._local_matrix(lev)
     diag = A.diagonal()
     interior = np.nonzero(diag > 0)[0]
     if interior.size == 0:
@@ -516,7 +868,9 @@ class PMultigridPreconditioner:
     Ai = A[interior][:, interior]
     dm = 1.0 / np.sqrt(Ai.diagonal())
     S = sp.diags(dm) @ Ai @ sp.diags(dm)
-    if S.shape[0] <= 400:
+    if bounds is not None:
+      lmin, lmax = None, None
+    elif S.shape[0] <= 400:
       ev = np.linalg.eigvalsh(S.toarray())
       lmin, lmax = float(ev[0]), float(ev[-1])
     else:
@@ -532,41 +886,30 @@ class PMultigridPreconditioner:
         got = np.sort(exc.eigenvalues)
         lmin = (float(got[0]) if got.size else
                 lmax / (4.0 * S.shape[0] ** (2.0 / mesh.ndim)))
-    if not lmin > 1e-12 * lmax:
+    if bounds is not None:
+      self.coarse_bounds = tuple(float(b) for b in bounds)
+    elif not lmin > 1e-12 * lmax:
       raise NotImplementedError(
           'p-multigrid needs a positive definite operator (the coarse matrix '
           'is singular: no Dirichlet nodes and lambda0 = 0?)')
-    self.coarse_bounds = (0.9 * lmin, 1.05 * lmax)
-    if steps is None:
-      kappa = self.coarse_bounds[1] / self.coarse_bounds[0]
-      steps = math.ceil(0.5 * math.sqrt(kappa) *
-                        math.log(2.0 / COARSE_REDUCTION))
-      steps = max(2, min(COARSE_MAX_STEPS, steps))
-    self.coarse_steps = int(steps)
-    width = int(np.diff(A.indptr).max()) if A.nnz else 1
-    ecols = np.repeat(np.arange(N)[:, None], width, axis=1)
-    evals = np.zeros((N, width))
-    row = np.repeat(np.arange(N), np.diff(A.indptr))
-    slot = np.arange(A.nnz) - np.repeat(A.indptr[:-1], np.diff(A.indptr))
-    ecols[row, slot] = A.indices
-    evals[row, slot] = A.data
-    lev.ell_cols = torch.as_tensor(ecols.T.copy(), dtype=torch.int32,
-                                   device=self.device).contiguous()
-    lev.ell_vals = torch.as_tensor(evals.T.copy(), dtype=self.dtype,
-                                   device=self.device).contiguous()
+    else:
+      self.coarse_bounds = (0.9 * lmin, 1.05 * lmax)
+    self.coarse_steps = self._steps_for(steps)
     dinv = np.zeros(N)
     dinv[interior] = 1.0 / diag[interior]
-    lev.ell_dinv = torch.as_tensor(dinv, dtype=self.dtype, device=self.device)
-    lev.ell_work = torch.zeros(3 * N, dtype=self.dtype, device=self.device)
+    self._store_ell(lev, A, dinv)
 
   # ----------------------------------------------------------------- apply
   def restrict(self, l, r, out):
     """out (level l + 1) = P^T r (level l)."""
     t = self.levels[l].transfer
-    _ops.pmg_restrict(r, t['local'], t['cidx'], t['fidx'], t['owner'],
-                      t['mat'], self.levels[l].mesh.ndim, t['pc'], t['pf'])
-    return _ops.scatter_csr(t['local'], t['offsets'], t['slots'], out.numel(),
-                            out=out)
+    _ops.pmg_restrict(r, t['local'], t['cidx'], t['fidx'],
+                      t['restrict_owner'], t['mat'], self.levels[l].mesh.ndim,
+                      t['pc'], t['pf'])
+    _ops.scatter_csr(t['local'], t['offsets'], t['slots'], out.numel(),
+                     out=out)
+    # (a partition: this rank's share of P^T r, summed over the ranks)
+    return self._exchange_(out, self.levels[l + 1].mesh)
 
   def prolong(self, l, xc, out, add=False):
     """out (level l) = P xc (level l + 1); add: out += P xc."""
@@ -591,6 +934,8 @@ class PMultigridPreconditioner:
   def _cycle(self, l, b):
     lev = self.levels[l]
     if l == len(self.levels) - 1:
+      if self.plan is not None:
+        return self._coarse_partitioned(lev, b)
       lo, hi = self.coarse_bounds
       return _ops.ell_chebyshev(lev.ell_cols, lev.ell_vals, lev.ell_dinv, b,
                                 self.coarse_steps, lo, hi, work=lev.ell_work,
