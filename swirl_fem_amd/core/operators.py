@@ -394,6 +394,54 @@ def _attach_clusters(fespace, enc, multiplicity, parts):
   return out
 
 
+def colored_launch_order(colors, num_colors, group, num_groups):
+  """Launches of coloured assembly: [(group, element ids int64)], one per
+  non-empty (colour, group) pair, colour-major.  `colors` (E,) from
+  `AssemblyPlan.coloring`, `group` (E,) the launch group (geometry kind) of
+  every element, -1 for none.
+
+  The kernel stores the first toucher of a node (the slot of least colour)
+  and adds every other slot to what is there, so all launches of colour c
+  must run before any of colour c + 1.  Within a colour the groups share no
+  node and may go in any order.  (Group-major order ran an affine element of
+  colour 3 before the multilinear element of colour 0 that first touches a
+  shared node: its sum was read from a stale value and then overwritten.)"""
+  colors = colors.to(torch.int64)
+  group = group.to(torch.int64)
+  out = []
+  for c in range(num_colors):
+    for g in range(num_groups):
+      lst = torch.nonzero((colors == c) & (group == g)).reshape(-1)
+      if lst.numel():
+        out.append((g, lst))
+  return out
+
+
+def first_toucher_violations(elements, first, launches):
+  """Slots of `elements` (E, n) that are not their node's first toucher
+  (`first`, from `AssemblyPlan.coloring`) but whose element runs no later
+  than the first toucher's in `launches` (`colored_launch_order`): 0 when
+  the coloured assembly is correct."""
+  el = elements.to(torch.int64)
+  E = el.shape[0]
+  launch = torch.full((E,), -1, dtype=torch.int64, device=el.device)
+  for i, (_, lst) in enumerate(launches):
+    launch[lst.to(device=el.device, dtype=torch.int64)] = i
+  ok = el >= 0
+  if not bool(ok.any()):
+    return 0
+  if bool((launch[ok.any(dim=1)] < 0).any()):
+    raise RuntimeError('coloured assembly: an element is in no launch')
+  slot_launch = launch[:, None].expand_as(el)
+  num_nodes = int(el[ok].max()) + 1
+  first_launch = torch.full((num_nodes,), -1, dtype=torch.int64,
+                            device=el.device)
+  first_launch.scatter_reduce_(0, el[first & ok], slot_launch[first & ok],
+                               'amax')
+  later = ok & ~first
+  return int((slot_launch[later] <= first_launch[el[later]]).sum())
+
+
 @dataclasses.dataclass(eq=False)
 class HelmholtzOperator:
   fespace: object
@@ -484,26 +532,25 @@ class HelmholtzOperator:
     enc = _ops.encode_elements(mesh.elements, mask, plan.multiplicity)
     zero_range = plan.zero_range
     if assembly == 'colored':
-      # One launch per (geometry kind, colour class): elements of a class share
+      # One launch per (colour class, geometry kind): elements of a class share
       # no node, shared slots read-modify-write `out` in colour order (no
       # atomics, no zero-fill of the shared range, bitwise reproducible).
+      # The launches are colour-major, so that every node's first toucher
+      # (its plain store) runs before the other elements that add to it.
       colors, num_colors, first = plan.coloring()
       slot_shared = ((mesh.elements >= 0) & ~first).to(torch.uint8).contiguous()
       enc = _ops.encode_elements(mesh.elements, mask, None, slot_shared)
-      colored_parts = []
-      for part in parts:
-        in_part = (torch.ones(E, dtype=torch.bool, device=fespace.device)
-                   if 'elem_list' not in part else None)
-        if in_part is None:
-          in_part = torch.zeros(E, dtype=torch.bool, device=fespace.device)
-          in_part[part['elem_list'].to(torch.int64)] = True
-        for c in range(num_colors):
-          lst = torch.nonzero(in_part & (colors == c)).reshape(-1)
-          if lst.numel():
-            colored_parts.append(dict(
-                part, elem_list=lst.to(torch.int32).contiguous(),
-                colored=True))
-      parts = colored_parts
+      group = torch.full((E,), -1, dtype=torch.int64, device=fespace.device)
+      for g, part in enumerate(parts):
+        group[part['elem_list'].to(torch.int64)
+              if 'elem_list' in part else slice(None)] = g
+      launches = colored_launch_order(colors, num_colors, group, len(parts))
+      bad = first_toucher_violations(mesh.elements, first, launches)
+      if bad:
+        raise RuntimeError(f'coloured assembly: {bad} shared slots would be '
+                           'added before their node\'s first store')
+      parts = [dict(parts[g], elem_list=lst.to(torch.int32).contiguous(),
+                    colored=True) for g, lst in launches]
       unref = torch.nonzero(plan.multiplicity == 0).reshape(-1)
       zero_range = ((int(unref.min()), int(unref.max()) + 1)
                     if unref.numel() else (0, 0))

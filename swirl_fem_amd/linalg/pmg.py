@@ -31,7 +31,11 @@ operator itself, and default assembly on the coarse levels), a two-grid one
 element-locally with a fixed-order sum (`sfem_scatter_csr`), so that every
 sum in the V-cycle has a fixed order and the preconditioner is bitwise
 reproducible.  Coarse levels are collocated GLL `HelmholtzOperator`s with the
-same (lambda0, lambda1), coloured assembly.
+same (lambda0, lambda1), coloured assembly.  Coloured assembly launches colour
+by colour across the geometry kinds (`operators.colored_launch_order`): it was
+once launched kind by kind, which on meshes mixing affine and multilinear
+elements added some shared slots before their node's first store and left
+the one-rank V-cycle about 24 % off the operator there.
 
 `CGRunner` recognises the preconditioner through `stops_on_residual`: it then
 stops on the true-residual norm r.r <= max(tol^2 b.b, atol^2) instead of the

@@ -23,9 +23,15 @@ def element_matrices(coords, elements, P, quad, l0, l1):
   fes = O.FESpace(coords, elements, (P, 'gll'), quad)
   wdet = fes.jacdets * fes.weights[None, :]
   phys = np.einsum('qid,eqjd->eqij', fes.G, fes.invjacs)     # (E, Q, n, d)
-  K = l1 * np.einsum('eq,eqid,eqjd->eij', wdet, phys, phys)
+  # sum over (q, d) as one batched matrix product (BLAS)
+  E, Q, n, d = phys.shape
+  rows = phys.transpose(0, 2, 1, 3).reshape(E, n, Q * d)
+  wrows = (phys * wdet[:, :, None, None]).transpose(0, 2, 1, 3).reshape(
+      E, n, Q * d)
+  K = l1 * np.matmul(wrows, rows.transpose(0, 2, 1))
   if l0:
-    K = K + l0 * np.einsum('eq,qi,qj->eij', wdet, fes.M, fes.M)
+    K = K + l0 * np.einsum('eq,qi,qj->eij', wdet, fes.M, fes.M,
+                           optimize=True)
   return K
 
 

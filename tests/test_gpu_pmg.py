@@ -14,6 +14,7 @@ from swirl_fem_amd.core.interpolation import NodeType, Quadrature1D
 from swirl_fem_amd.linalg import pmg
 from swirl_fem_amd.linalg.cg import CGRunner, cg
 from swirl_fem_amd.linalg.pmg import PMultigridPreconditioner
+from tests import geometry_cases as G
 from tests import pmg_reference as R
 
 pytestmark = pytest.mark.gpu
@@ -165,6 +166,54 @@ def test_smoother_and_vcycle_match_numpy():
   ref = R.smooth(H.levels[0], b.numpy(), np.zeros(len(b)), H.cheb[0])
   assert np.abs(_np(x) - ref).max() < 1e-12 * np.abs(ref).max()
   z = M(bd)
+  ref = H.vcycle(b.numpy())
+  assert np.abs(_np(z) - ref).max() < 1e-11 * np.abs(ref).max()
+
+
+def _level_reference(mesh, dirichlet, l0, l1, u):
+  """fp64 oracle of l0 B + l1 A on a level's own (GLL-collocated) mesh."""
+  from oracle import sfem_oracle as O
+  P = mesh.order + 1
+  ofes = O.FESpace(_np(mesh.node_coords), mesh.elements.cpu().numpy(),
+                   (P, 'gll'), (P, 'gll'))
+  ul = ofes.gather(u)
+  out = ofes.scatter(l0 * ofes.mass_local(ul) + l1 * ofes.stiffness_local(ul))
+  return out if dirichlet is None else out * ~dirichlet.cpu().numpy()
+
+
+@pytest.mark.parametrize('name,n,P', [('block_jitter', 4, 5),
+                                      ('block_jitter', 3, 9),
+                                      ('three_kinds', 3, 5)])
+def test_mixed_geometry_levels_and_vcycle(name, n, P):
+  """Meshes that mix affine, multilinear (and curved) elements: the coloured
+  fine-level copy and every coarse operator against the oracle on that
+  level's mesh, and the V-cycle against the NumPy restatement."""
+  case = getattr(G, name)(n, 3, P)
+  rp = case.rp
+  mesh = rp.finalize(device=DEV)
+  bm = mesh.physical_masks['boundary']
+  fes = FiniteElementSpace.create(
+      mesh, Quadrature1D.create(P, NodeType.GAUSS_LOBATTO_LEGENDRE))
+  op = fes.helmholtz_operator(bm)
+  case.check_counts(op)
+  l0, l1 = 0.3, 1.0
+  M = PMultigridPreconditioner(op, l0, l1)
+  assert M._fine_colored.num_affine == op.num_affine > 0
+  g = torch.Generator().manual_seed(7)
+  levels = [(M._fine_colored, mesh, bm)] + [
+      (lev.op, lev.mesh, lev.dirichlet) for lev in M.levels[1:]]
+  for i, (lop, lmesh, ldir) in enumerate(levels):
+    u = torch.randn(lmesh.num_nodes, generator=g, dtype=torch.float64)
+    ref = _level_reference(lmesh, ldir, l0, l1, u.numpy())
+    got = lop.apply(u.to(DEV), l0, l1,
+                    out=torch.full((lmesh.num_nodes,), 7.5,
+                                   dtype=torch.float64, device=DEV))
+    err = np.abs(_np(got) - ref).max() / np.abs(ref).max()
+    assert err < 1e-10, (name, P, i, lmesh.order, err)
+  H = _reference(rp, mesh, M, bm, l0, l1)
+  b = torch.randn(mesh.num_nodes, generator=g, dtype=torch.float64)
+  b = b * (~bm.cpu())
+  z = M(b.to(DEV))
   ref = H.vcycle(b.numpy())
   assert np.abs(_np(z) - ref).max() < 1e-11 * np.abs(ref).max()
 

@@ -112,13 +112,14 @@ def _rank_problem(rank, n, P, dtype, jitter, f, lookup):
   return part, op, ids, b_loc
 
 
-def test_vcycle_on_partitions_equals_whole_box():
+@pytest.mark.parametrize('jitter', [0.0, 0.1])
+def test_vcycle_on_partitions_equals_whole_box(jitter):
   """The same V-cycle: the whole box's spectrum estimates injected, the
-  same coarse steps; applied to one global vector, to 1e-10 in fp64.  Affine
-  blocks: the one-rank V-cycle smooths with a coloured-assembly copy of the
-  operator, which on multilinear elements does not reproduce the operator's
-  apply, while the partitioned one applies the operator itself."""
-  n, P, jitter = 2, 5, 0.0
+  same coarse steps; applied to one global vector, to 1e-10 in fp64.  The
+  one-rank V-cycle smooths with a coloured-assembly copy of the operator, the
+  partitioned one applies the operator itself; the jittered box mixes affine
+  and multilinear elements."""
+  n, P = 2, 5
   whole, gop, _, _, lookup = _whole(n, P, torch.float64, jitter)
   Mg = PMultigridPreconditioner(gop, L0, L1, coarse_steps=12)
   bounds = Mg.spectral_bounds()
@@ -243,13 +244,16 @@ def test_partitioned_pmg_and_jacobi_solves(P):
   tol = 1e-10
   res = _solve_case(2, P, torch.float64, tol, 0.1, [None, 'jacobi', 'pmg'])
   plain, jac, mg = res[None], res['jacobi'], res['pmg']
-  # the reference: one-rank plain CG (the one-rank pMG smooths with a
-  # coloured copy of the operator, which is not exact on these multilinear
-  # elements -- see test_vcycle_on_partitions_equals_whole_box)
+  # the reference: one-rank plain CG
   xs = plain['single'][0]
   for kind in (None, 'jacobi', 'pmg'):
     err = np.abs(res[kind]['x'] - xs).max() / np.abs(xs).max()
     assert err <= 1e-8, (kind, err)
+  # ... and the one-rank pMG solve, which meets the tolerance itself
+  xm = mg['single'][0]
+  err = np.abs(mg['x'] - xm).max() / np.abs(xm).max()
+  assert err <= 1e-8, err
+  assert mg['single'][2] <= 1.1 * tol, mg['single'][2]
   assert mg['iters'] <= mg['single'][1] + 2, (mg['iters'], mg['single'][1])
   assert 4 * mg['iters'] <= plain['iters'], (mg['iters'], plain['iters'])
   assert mg['residual'] <= 1.1 * tol, mg['residual']
