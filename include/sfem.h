@@ -895,6 +895,35 @@ int sfem_ell_spmv(const int32_t* cols, const void* vals, const void* x,
                   void* y, int64_t n, int width, int64_t row_begin,
                   int64_t row_end, const int32_t* rows, int64_t num_rows,
                   int dtype, sfem_stream_t stream);
+/* ---------------------------------------------------- boundary facets ---
+ * Integrals over the facets of a physical group (core/fespace.py
+ * boundary_points / boundary_covector; the call site is the inhomogeneous
+ * Dirichlet / Neumann data that the reference leaves as a TODO,
+ * swirl_fem/examples/poisson.py:79-90, served by examples/helmholtz.py).
+ * A facet is a (d-1)-dimensional isoparametric element with its own nodes,
+ * integrated with the space's 1D rule in each facet direction.  One wave per
+ * facet; (p1, q) pairs with q = p1 or p1 + 1, 2 <= p1 <= 13, are compiled
+ * with fixed sizes, others (p1 <= 16, q <= 16) run with run-time sizes.
+ *   coords (N, ndim), facets (F, p1^(ndim-1)) int32 node ids in [0, N),
+ *       lexicographic on the facet;
+ *   bmat (q, p1) row-major: B, the 1D interpolation from the nodes to the
+ *       points; dmat (q, p1): D_q = B D; weights (q): the 1D rule.
+ * sfem_boundary_geom:     xq (F, q^(ndim-1), ndim) the physical points;
+ *                         wj (F, q^(ndim-1)) = w_s w_t |x_s x x_t| (ndim 3)
+ *                         or w_s |x_s| (ndim 2);
+ * sfem_boundary_covector: out_local (F, p1^(ndim-1)) = (B (x) B)^T (wj g),
+ *                         g the values at the points (F, q^(ndim-1)), or
+ *                         (nodal != 0) nodal values (N,) gathered through
+ *                         `facets` and interpolated by B (x) B; summed per
+ *                         node by sfem_scatter_csr in a fixed order.         */
+int sfem_boundary_geom(const void* coords, const int32_t* facets,
+                       int64_t num_facets, const void* bmat, const void* dmat,
+                       const void* weights, int ndim, int p1, int q, void* xq,
+                       void* wj, int dtype, sfem_stream_t stream);
+int sfem_boundary_covector(const void* g, int nodal, const int32_t* facets,
+                           int64_t num_facets, const void* wj,
+                           const void* bmat, int ndim, int p1, int q,
+                           void* out_local, int dtype, sfem_stream_t stream);
 /* y = a*x + b*y (plain fused vector update used outside the CG core)         */
 int sfem_axpby(double a, const void* x, double b, void* y, int64_t count,
                int dtype, sfem_stream_t stream);

@@ -202,6 +202,10 @@ SIGNATURES = {
     'sfem_pmg_dot2': [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i32, c_i32, c_ptr],
     'sfem_pmg_cg_scalars': [c_ptr, c_i32, c_ptr, c_i64, c_dbl, c_dbl, c_dbl,
                             c_ptr],
+    'sfem_boundary_geom': [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i32,
+                           c_i32, c_i32, c_ptr, c_ptr, c_i32, c_ptr],
+    'sfem_boundary_covector': [c_ptr, c_i32, c_ptr, c_i64, c_ptr, c_ptr,
+                               c_i32, c_i32, c_i32, c_ptr, c_i32, c_ptr],
     'sfem_ell_spmv': [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_i64, c_i64,
                       c_ptr, c_i64, c_i32, c_ptr],
     'sfem_abi_version': [],

@@ -1382,3 +1382,49 @@ def pmg_cg_scalars(scalars, phase, partials, n, maxiter, tol, atol):
     _lib.check(_lib.load().sfem_pmg_cg_scalars(
         _ptr(scalars), int(phase), _ptr(partials), int(n), float(maxiter),
         float(tol), float(atol), _stream(dev)), 'sfem_pmg_cg_scalars')
+
+
+# ---------------------------------------------------------- boundary facets
+def boundary_geom(coords, facets, bmat, dmat, weights):
+  """(xq (F, Q^(d-1), d), wJ (F, Q^(d-1))) of the facets, see
+  `sfem_boundary_geom`.  `facets` (F, (P+1)^(d-1)) int32 ids in [0, N)."""
+  dev = _dev(coords, facets, bmat, dmat, weights)
+  if any(t.dtype != coords.dtype for t in (bmat, dmat, weights)):
+    raise ValueError('boundary_geom: one dtype for coords and the matrices')
+  d = coords.shape[-1]
+  q, p1 = bmat.shape
+  F, nq = facets.shape[0], q ** (d - 1)
+  if facets.dtype != torch.int32 or facets.shape[1] != p1 ** (d - 1):
+    raise ValueError(f'boundary_geom: facets must be (F, {p1 ** (d - 1)}) '
+                     'int32')
+  xq = torch.empty((F, nq, d), dtype=coords.dtype, device=dev)
+  wj = torch.empty((F, nq), dtype=coords.dtype, device=dev)
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_boundary_geom(
+        _ptr(coords), _ptr(facets), F, _ptr(bmat), _ptr(dmat), _ptr(weights),
+        d, p1, q, _ptr(xq), _ptr(wj), _dtype_code(coords), _stream(dev)),
+        'sfem_boundary_geom')
+  return xq, wj
+
+
+def boundary_covector(g, nodal, facets, wj, bmat, ndim):
+  """Facet-local (B (x) B)^T (wJ g), (F, (P+1)^(d-1)); g nodal (N,) when
+  `nodal`, else (F, Q^(d-1)) at the points (`sfem_boundary_covector`)."""
+  g = g.contiguous()
+  dev = _dev(g, facets, wj, bmat)
+  if wj.dtype != g.dtype or bmat.dtype != g.dtype:
+    raise ValueError('boundary_covector: one dtype for g, wJ and B')
+  q, p1 = bmat.shape
+  F = facets.shape[0]
+  if tuple(wj.shape) != (F, q ** (ndim - 1)):
+    raise ValueError('boundary_covector: wJ does not match the facets')
+  if not nodal and tuple(g.shape) != tuple(wj.shape):
+    raise ValueError(f'boundary_covector: point values must be '
+                     f'{tuple(wj.shape)}, got {tuple(g.shape)}')
+  out = torch.empty((F, p1 ** (ndim - 1)), dtype=g.dtype, device=dev)
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_boundary_covector(
+        _ptr(g), int(bool(nodal)), _ptr(facets), F, _ptr(wj), _ptr(bmat),
+        int(ndim), p1, q, _ptr(out), _dtype_code(g), _stream(dev)),
+        'sfem_boundary_covector')
+  return out

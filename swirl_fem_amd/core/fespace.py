@@ -18,6 +18,11 @@ How it runs here
     produces in the reference (:466-471).
   * The collocated mass / stiffness / Helmholtz operators have a fused
     gather->apply->scatter kernel, reached through `helmholtz_operator`.
+  * Boundary integrals over the facets of a physical group
+    (`Mesh.boundary_facets`): `boundary_points` / `boundary_covector` run
+    `sfem_boundary_geom` / `sfem_boundary_covector` with the space's 1D rule
+    in each facet direction, and `sfem_scatter_csr` sums the facet values per
+    node in a fixed order.
 """
 
 from __future__ import annotations
@@ -344,6 +349,97 @@ class FiniteElementSpace:
         self.is_collocated)
     return out.reshape((E, self.mesh.num_nodes_per_element) + value_shape)
 
+  # ------------------------------------------------------ boundary facets
+  def _boundary_plan(self, group: str) -> dict:
+    """Per group: facet rows, facet points and weights, the CSR of the facet
+    slots per node (built once, on the host)."""
+    key = ('boundary', group)
+    if key in self._cache:
+      return self._cache[key]
+    mesh = self.mesh
+    if mesh.axis_name is not None or mesh.neighbor_plan is not None:
+      raise NotImplementedError('boundary integrals on a partitioned mesh')
+    if mesh._cache.get('replicas', 1) > 1:
+      raise NotImplementedError('boundary integrals on an ensemble '
+                                '(Mesh.replicate)')
+    if group not in mesh.boundary_facets:
+      if group in mesh.physical_masks:
+        raise ValueError(f'physical group {group!r} has no facets: its node '
+                         'array is not (F, (P+1)^(d-1)) facet rows')
+      raise KeyError(f'unknown physical group {group!r}; the mesh has '
+                     f'{sorted(mesh.physical_masks)}')
+    facets = mesh.boundary_facets[group].to(torch.int32).contiguous()
+    host = facets.cpu().numpy().astype(np.int64)
+    n = mesh.num_nodes
+    if host.size and (host.min() < 0 or host.max() >= n):
+      raise ValueError(f'physical group {group!r}: node ids outside [0, {n})')
+    d = mesh.ndim
+    plan = {'facets': facets}
+    if d == 1:
+      plan['xq'] = mesh.node_coords[facets[:, 0].long()].reshape(-1, 1, 1)
+      plan['wj'] = torch.ones((facets.shape[0], 1), dtype=self.dtype,
+                              device=self.device)
+    else:
+      i1, g1 = self._matrices()
+      w = torch.as_tensor(self.quadrature.weights, dtype=self.dtype,
+                          device=self.device)
+      plan['xq'], plan['wj'] = _ops.boundary_geom(
+          mesh.node_coords.contiguous(), facets, i1, g1, w)
+      offsets, slots = boundary_csr(host, n)
+      plan['offsets'] = torch.as_tensor(offsets, device=self.device)
+      plan['slots'] = torch.as_tensor(slots, device=self.device)
+    self._cache[key] = plan
+    return plan
+
+  def boundary_points(self, group: str):
+    """`(x_q (F, Q^(d-1), d), wJ (F, Q^(d-1)))`: the quadrature points on the
+    facets of `group` and their weights times the facet Jacobian
+    (w_s w_t |x_s x x_t| on faces, w_s |x_s| on edges; 1 at 1D points)."""
+    plan = self._boundary_plan(group)
+    return plan['xq'], plan['wj']
+
+  def boundary_covector(self, group: str, g) -> torch.Tensor:
+    """The assembled `(N,)` vector `int_group g phi_i dGamma`.
+
+    `g`: a scalar; an `(N,)` nodal tensor (interpolated on each facet); the
+    values `(F, Q^(d-1))` at the facet points of `boundary_points`; or a
+    callable that takes the `(M, d)` point coordinates and returns `(M,)`.
+    Periodic images are summed by the mesh's exchange.
+    """
+    plan = self._boundary_plan(group)
+    mesh, facets = self.mesh, plan['facets']
+    xq, wj = plan['xq'], plan['wj']
+    nodal = False
+    if callable(g):
+      g = torch.as_tensor(g(xq.reshape(-1, mesh.ndim)), dtype=self.dtype,
+                          device=self.device)
+      if g.numel() != wj.numel():
+        raise ValueError(f'the callable returned {tuple(g.shape)} values for '
+                         f'{wj.numel()} points')
+      g = g.reshape(wj.shape)
+    else:
+      g = torch.as_tensor(g, dtype=self.dtype, device=self.device)
+      if g.dim() == 0:
+        g = g.expand(wj.shape)
+      elif tuple(g.shape) == (mesh.num_nodes,):
+        nodal = True
+      elif tuple(g.shape) != tuple(wj.shape):
+        raise ValueError(f'g must be a scalar, ({mesh.num_nodes},) nodal '
+                         f'values or {tuple(wj.shape)} point values; got '
+                         f'{tuple(g.shape)}')
+    g = g.contiguous()
+    if mesh.ndim == 1:
+      ids = facets[:, 0].long()
+      out = torch.zeros(mesh.num_nodes, dtype=self.dtype, device=self.device)
+      out[ids] = g[ids] if nodal else g[:, 0]
+    else:
+      i1, _ = self._matrices()
+      local = _ops.boundary_covector(g, nodal, facets, wj.contiguous(), i1,
+                                     mesh.ndim)
+      out = _ops.scatter_csr(local.reshape(-1), plan['offsets'],
+                             plan['slots'], mesh.num_nodes)
+    return mesh.exchange(out)
+
   # -------------------------------------------------------- fused operators
   def helmholtz_operator(self, dirichlet_mask=None, geometry='auto',
                          assembly='auto'):
@@ -374,6 +470,16 @@ class FiniteElementSpace:
                                               assembly)
     self._cache[key] = (dirichlet_mask, op)
     return op
+
+
+def boundary_csr(facets: np.ndarray, num_nodes: int):
+  """CSR of the facet slots per node: `(offsets (N+1,) int64, slots int32)`,
+  slots ascending per node, so `sfem_scatter_csr` sums in a fixed order."""
+  flat = np.asarray(facets, np.int64).reshape(-1)
+  slots = np.argsort(flat, kind='stable').astype(np.int32)
+  offsets = np.zeros(num_nodes + 1, dtype=np.int64)
+  offsets[1:] = np.cumsum(np.bincount(flat, minlength=num_nodes))
+  return offsets, slots
 
 
 def _device_matrices(interpolator, dtype, device, cache):

@@ -6,7 +6,9 @@ API follows the reference `swirl_fem/core/mesh.py` (`Mesh` fields :75-88,
 
 HBM layout: `node_coords (N, d)` real, `elements (E, n)` int32 (lexicographic
 node order inside an element, axis 0 slowest), `node_indices (N,)` int32,
-`physical_masks[name] (N,)` bool, `exchange_gather_indices (S,)` int32.
+`physical_masks[name] (N,)` bool, `exchange_gather_indices (S,)` int32,
+`boundary_facets[name] (F, (P+1)^(d-1))` int32 (the facets of a physical group,
+lexicographic node order on the facet; unpartitioned meshes only).
 Setup products that the kernels need (shared/owned classification of element
 slots, CSR inverse map for the deterministic assembly) are built lazily and
 cached on the instance (`assembly_plan`).
@@ -56,6 +58,10 @@ class Mesh:
   axis_name: str | None = None
   # this rank's neighbour lists when partitioned (build-side addition)
   neighbor_plan: object | None = None
+  # facets of each physical group, `(F, (P+1)^(d-1))` int32 node ids (in 1D
+  # `(F, 1)`: the boundary points); empty on partitions and ensembles
+  boundary_facets: Mapping[str, torch.Tensor] = dataclasses.field(
+      default_factory=dict)
   _cache: dict = dataclasses.field(default_factory=dict, repr=False,
                                    compare=False)
 
@@ -64,7 +70,7 @@ class Mesh:
              gridpoints_1d: Nodes1D | None = None, physical_masks=None,
              exchange_gather_indices=None, exchange_unique_indices=None,
              axis_name: str | None = None, *, neighbor_plan=None,
-             device=None, dtype=None) -> 'Mesh':
+             boundary_facets=None, device=None, dtype=None) -> 'Mesh':
     """Creates a `Mesh`; arrays are placed on `device` (default: the GPU)."""
     device = torch.device(device) if device is not None else default_device()
     ndim = node_coords.shape[-1]
@@ -102,7 +108,9 @@ class Mesh:
         exchange_gather_indices=_as_tensor(exchange_gather_indices,
                                            torch.int32, device),
         exchange_unique_indices=exchange_unique_indices,
-        axis_name=axis_name, neighbor_plan=neighbor_plan)
+        axis_name=axis_name, neighbor_plan=neighbor_plan,
+        boundary_facets={k: _as_tensor(v, torch.int32, device)
+                         for k, v in (boundary_facets or {}).items()})
 
   def replace(self, **kw) -> 'Mesh':
     kw.setdefault('_cache', {})
@@ -138,7 +146,7 @@ class Mesh:
         physical_masks={k: v.repeat(members)
                         for k, v in self.physical_masks.items()},
         exchange_gather_indices=gi, exchange_unique_indices=ui,
-        _cache={'replicas': members})
+        boundary_facets={}, _cache={'replicas': members})
 
   # ------------------------------------------------------------- properties
   @property

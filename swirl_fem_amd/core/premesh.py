@@ -2,7 +2,8 @@
 
 API follows the reference `swirl_fem/core/premesh.py` (`Premesh` :38-71,
 `create` :73-115, `finalize` :141-222).  `finalize()` builds the device `Mesh`
-(periodic de-duplication, exchange indices, boundary masks).  For a partitioned
+(periodic de-duplication, exchange indices, boundary masks and, unpartitioned,
+the boundary facets of every physical group).  For a partitioned
 premesh the reference regroups elements per partition, renumbers nodes locally
 and `pmap`-places one partition per device (:170-222); here one *process* owns
 one partition, so `finalize(axis_name)` returns this rank's `Mesh` (rank taken
@@ -26,6 +27,29 @@ from swirl_fem_amd.core.interpolation import NodeType
 def _mask(facets: np.ndarray, node_indices: np.ndarray) -> np.ndarray:
   """Boolean mask of which `node_indices` occur in `facets`."""
   return np.isin(node_indices, np.unique(np.asarray(facets).reshape(-1)))
+
+
+def boundary_facets(physical_groups: Mapping[str, np.ndarray], ndim: int,
+                    num_points: int, num_nodes: int) -> dict:
+  """The facets of each physical group that can be read as facets.
+
+  In 2D / 3D a group is `(F, num_points^(ndim-1))` node rows (lexicographic on
+  the facet, as the builders, the Gmsh reader and the refiner write them); a
+  group of any other shape, or with ids outside [0, num_nodes), gets none.
+  In 1D every distinct id of a group is a boundary point: `(F, 1)`.
+  """
+  out = {}
+  for name, group in physical_groups.items():
+    a = np.asarray(group)
+    if a.size == 0 or not np.issubdtype(a.dtype, np.integer):
+      continue
+    if a.min() < 0 or a.max() >= num_nodes:
+      continue
+    if ndim == 1:
+      out[name] = np.unique(a.reshape(-1)).astype(np.int32).reshape(-1, 1)
+    elif a.ndim == 2 and a.shape[1] == num_points ** (ndim - 1):
+      out[name] = a.astype(np.int32)
+  return out
 
 
 def _default_gridpoints(num_nodes_per_element: int, ndim: int) -> Nodes1D:
@@ -140,8 +164,10 @@ class Premesh:
     from swirl_fem_amd.core.mesh import Mesh
     arrays = self.finalize_all(axis_name)
     if not self.is_partitioned():
+      facets = boundary_facets(self.physical_groups, self.ndim,
+                               self.gridpoints_1d.num_points, self.num_nodes)
       return Mesh.create(gridpoints_1d=self.gridpoints_1d, device=device,
-                         dtype=dtype, **arrays)
+                         dtype=dtype, boundary_facets=facets, **arrays)
 
     from swirl_fem_amd.distributed import comm
     if rank is None:

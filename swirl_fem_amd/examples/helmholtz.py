@@ -1,0 +1,186 @@
+"""Helmholtz / Poisson solves with inhomogeneous Dirichlet and Neumann data.
+
+    lambda0 u - lambda1 lap u = f   in the mesh,
+    u = g_D on Dirichlet groups,   du/dn = g_N on Neumann groups,
+    du/dn = 0 on the rest of the boundary.
+
+The boundary data the reference's `solve_poisson` docstring promises and
+leaves as a TODO (swirl_fem/examples/poisson.py:79-90); `solve_poisson`
+itself keeps the reference's homogeneous-only contract.  Quadrature, forms,
+operators and preconditioners are those of `examples/poisson.py`.
+
+Method: lift and solve for the homogeneous remainder.  u_D holds the Dirichlet
+values on the Dirichlet nodes and 0 elsewhere; w solves the masked system
+
+    K w = mask (B f + lambda1 b_N - (lambda0 B + lambda1 A) u_D),
+
+with K the operator of `solve_poisson` (Dirichlet rows and columns removed)
+and b_N the sum of `FiniteElementSpace.boundary_covector(group, g_N)` over the
+Neumann groups; u = w + u_D.  (lambda0 B + lambda1 A) u_D is applied by an
+operator without a mask, so that it reads the Dirichlet values.
+
+On a mesh with periodic images the unknowns are the lowest-numbered node of
+each class: K = R QQ^T A QQ^T R^T with R the restriction to those nodes
+(QQ^T copies a class's only nonzero value to all its images), which keeps K
+symmetric for CG; the result is copied back to the images.
+"""
+
+from __future__ import annotations
+
+from typing import Mapping, Tuple
+
+import torch
+
+from swirl_fem_amd.core.fespace import FiniteElementSpace
+from swirl_fem_amd.core.fespace import grad
+from swirl_fem_amd.core.interpolation import NodeType
+from swirl_fem_amd.core.interpolation import Quadrature1D
+from swirl_fem_amd.core.mesh import Mesh
+from swirl_fem_amd.examples.poisson import BCType
+from swirl_fem_amd.examples.poisson import BCValue
+from swirl_fem_amd.linalg.cg import cg
+
+# pylint: disable=invalid-name
+
+
+def _nodal_values(mesh: Mesh, value, dtype, device) -> torch.Tensor:
+  """A `BCValue` as `(N,)` nodal values: a scalar, an `(N,)` array, or a
+  callable on the `(N, d)` node coordinates."""
+  if callable(value):
+    value = value(mesh.node_coords)
+  v = torch.as_tensor(value, dtype=dtype, device=device)
+  if v.dim() == 0:
+    return v.expand(mesh.num_nodes)
+  if tuple(v.shape) != (mesh.num_nodes,):
+    raise ValueError(f'a Dirichlet value must be a scalar, ({mesh.num_nodes},) '
+                     f'nodal values or a callable; got {tuple(v.shape)}')
+  return v
+
+
+def solve_helmholtz(mesh: Mesh, forcing,
+                    boundary_conditions: Mapping[str, Tuple[BCType, BCValue]],
+                    *, lambda0: float = 0.0, lambda1: float = 1.0,
+                    rtol: float = 1e-5, atol: float = 0.,
+                    return_info: bool = False, preconditioner=None):
+  """Solves `lambda0 u - lambda1 lap u = forcing` with boundary data.
+
+  `boundary_conditions` maps physical group names to `(BCType, BCValue)`:
+  DIRICHLET sets u = value on the group's nodes, NEUMANN sets du/dn = value
+  (outward normal) on its facets.  A value is a scalar, an `(N,)` nodal array
+  (only the group's nodes are read) or a callable on coordinates: `(N, d)`
+  node coordinates for Dirichlet data, `(M, d)` facet quadrature points for
+  Neumann data.  Where Dirichlet groups share a node, the later group in the
+  mapping sets its value.  `forcing` is nodal.
+
+  `preconditioner`: None, 'jacobi' or 'pmg', as in `solve_poisson` (on a
+  mesh without periodic images).  `rtol` is relative to the norm of the
+  lifted right-hand side; `info` is CG's.
+  """
+  if preconditioner not in (None, 'jacobi', 'pmg'):
+    raise ValueError(f'unknown preconditioner {preconditioner!r}')
+  if mesh.axis_name is not None or mesh.neighbor_plan is not None:
+    raise NotImplementedError('solve_helmholtz on a partitioned mesh')
+  if mesh._cache.get('replicas', 1) > 1:
+    raise NotImplementedError('solve_helmholtz on an ensemble '
+                              '(Mesh.replicate)')
+  lambda0, lambda1 = float(lambda0), float(lambda1)
+  quadrature = Quadrature1D.create(
+      num_points=mesh.order + (mesh.ndim + 1) // 2,
+      quadrature_type=NodeType.GAUSS_LEGENDRE)
+  fespace = FiniteElementSpace.create(mesh, quadrature)
+  dtype, device = fespace.dtype, fespace.device
+
+  dirichlet = torch.zeros(mesh.num_nodes, dtype=torch.bool, device=device)
+  u_D = torch.zeros(mesh.num_nodes, dtype=dtype, device=device)
+  neumann = []
+  for group, (bctype, value) in boundary_conditions.items():
+    if bctype == BCType.DIRICHLET:
+      if group not in mesh.physical_masks:
+        raise KeyError(f'unknown physical group {group!r}')
+      m = mesh.physical_masks[group]
+      u_D = torch.where(m, _nodal_values(mesh, value, dtype, device), u_D)
+      dirichlet = dirichlet | m
+    elif bctype == BCType.NEUMANN:
+      neumann.append((group, value))
+    else:
+      raise ValueError(f'unsupported boundary condition type {bctype!r} on '
+                       f'{group!r}: DIRICHLET or NEUMANN')
+  has_dirichlet = bool(dirichlet.any())
+  if lambda0 == 0.0 and not has_dirichlet:
+    raise ValueError('lambda0 = 0 with no Dirichlet node: the problem is '
+                     'singular (u is determined up to a constant)')
+
+  gi = mesh.exchange_gather_indices
+  periodic = gi is not None and gi.numel() > 0
+  keep = (~dirichlet).to(dtype)
+  if periodic:
+    if preconditioner is not None:
+      raise NotImplementedError(f'preconditioner={preconditioner!r} on a mesh '
+                                'with periodic images')
+    ids = torch.arange(mesh.num_nodes, device=device)
+    master = (mesh.node_indices.to(ids.dtype) == ids).to(dtype)
+    u_D = mesh.exchange(u_D * master)        # one value per periodic class
+    keep = keep * master
+
+  # (lambda0 B + lambda1 A) with and without the Dirichlet rows
+  from swirl_fem_amd.core import operators
+  M = None
+  mask = dirichlet if has_dirichlet else None
+  if (fespace.is_collocated and operators.supports_fused(fespace) is None) or (
+      not fespace.is_collocated and
+      operators.supports_two_grid(fespace) is None):
+    op = fespace.helmholtz_operator(mask)
+    full = fespace.helmholtz_operator(None)
+    K = lambda u: op.apply(u, lambda0, lambda1)
+    H = lambda u, l0, l1: full.apply(u, l0, l1)
+    if preconditioner == 'jacobi':
+      from swirl_fem_amd.linalg.jacobi import JacobiPreconditioner
+      M = JacobiPreconditioner(op, lambda0, lambda1)
+    elif preconditioner == 'pmg':
+      from swirl_fem_amd.linalg.pmg import PMultigridPreconditioner
+      M = PMultigridPreconditioner(op, lambda0, lambda1)
+  elif preconditioner is not None:
+    raise NotImplementedError(
+        f"preconditioner={preconditioner!r} needs the fused operator: "
+        f"{operators.supports_two_grid(fespace)}")
+  else:
+    def l(u, v):
+      return lambda x: u(x) * v(x)
+
+    def a(u, v):
+      return lambda x: torch.vdot(grad(u)(x), grad(v)(x))
+
+    def H(u, l0, l1):
+      uf = fespace.scalar_function(mesh.gather(u))
+      v = fespace.scalar_function(None)
+      out = torch.zeros_like(u)
+      if l0 != 0.0:
+        out = out + l0 * mesh.scatter(fespace.local_covector(l, (uf, v)))
+      if l1 != 0.0:
+        out = out + l1 * mesh.scatter(fespace.local_covector(a, (uf, v)))
+      return out
+
+    K = lambda u: H(u, lambda0, lambda1) * keep
+
+  forcing = torch.as_tensor(forcing, dtype=dtype, device=device)
+  rhs = H(forcing, 1.0, 0.0)
+  if has_dirichlet:
+    rhs = rhs - H(u_D, lambda0, lambda1)
+  rhs = mesh.exchange(rhs)
+  for group, value in neumann:
+    rhs = rhs + lambda1 * fespace.boundary_covector(group, value)
+  b = rhs * keep
+
+  A = K
+  if periodic:
+    A = lambda x: mesh.exchange(K(mesh.exchange(x))) * keep
+  w, info = cg(A, b, tol=rtol, atol=atol, M=M)
+  if periodic:
+    w = mesh.exchange(w)
+  u = w + u_D
+  if return_info:
+    return u, info
+  return u
+
+
+__all__ = ['BCType', 'solve_helmholtz']
