@@ -266,11 +266,13 @@ def build_layer_plan(facet_parts, num_elements, num_nodes, P):
   Writers of a facet: every element that holds it, except -- inside a chain
   segment -- the element that hands its last face (and that face's edges and
   vertices) on to its successor, which stores the sum.  Layer = rank of the
-  writer among the writers of the facet (0 = the nodal vector itself).  The
-  refiner numbers vertices, then edge, face and element interiors, so the
-  nodes with k + 1 or more writers are a prefix [0, n_k): layer k is an array
-  of n_k values (config 2: n_1 = 37 % of N, n_2 = n_3 = 5 %, n_4.. = 0.3 %).
-  Slots nobody writes (a facet with fewer writers than the layer's other
+  writer among the writers of the facet (0 = the nodal vector itself).  Layer
+  k is an array over the nodes [0, n_k), n_k = 1 + the largest node id that
+  one of its writers stores.  The refiner numbers vertices, then edge, face
+  and element interiors, so there the nodes with k + 1 or more writers come
+  first and n_k is short (config 2: n_1 = 37 % of N, n_2 = n_3 = 5 %,
+  n_4.. = 0.3 %); other numberings whose facets are affine maps of node ids
+  reach this path as well, and there n_k can approach N.  Slots nobody writes (a facet with fewer writers than the layer's other
   facets) stay zero from the allocation.
 
   Returns None when the launches do not cover every element from a facet table
@@ -348,18 +350,24 @@ def build_layer_plan(facet_parts, num_elements, num_nodes, P):
   written = int((writer.to(torch.int64) * count[None]).sum())
   parts = [dict(q, layered_table=tab2, layered_chains=use_chains and
                 'chains' in q) for q in facet_parts]
-  # which chunks of each layer are written at all (only shared facets reach a
-  # layer beyond the nodal vector: at most (P - 2)^2 <= 100 nodes, so a block
-  # touches the chunks of its two ends and no other)
+  # which chunks of each layer are written at all: every chunk of a writer's
+  # id range [lo, hi), marked through a difference array summed over the
+  # layer's chunks.  A superset of the chunks it stores into, exact when a
+  # facet spans fewer than `chunk` ids (refiner numbering: one run of at most
+  # (P - 2)^2 ids).  A facet of a lexicographic numbering spans ~M^2 ids with
+  # gaps, and its nodes fall into chunks between those of its two ends.
   chunk = _lib.SFEM_LAYER_CHUNK
   flat_layer, flat_w = layer, writer.reshape(-1)
   lo_f, hi_f = lo.reshape(-1), hi.reshape(-1)
   bytes_, moffs, read = [], [], 0
   for k, ln in enumerate(lens, start=1):
-    m = torch.zeros((ln + chunk - 1) // chunk, dtype=torch.uint8, device=dev)
+    nc = (ln + chunk - 1) // chunk
     sel = flat_w & (flat_layer == k)
-    m[lo_f[sel] // chunk] = 1
-    m[(hi_f[sel] - 1) // chunk] = 1
+    first, last = lo_f[sel] // chunk, (hi_f[sel] - 1) // chunk
+    d = torch.zeros(nc + 1, dtype=torch.int64, device=dev)
+    d.index_add_(0, first, torch.ones_like(first))
+    d.index_add_(0, last + 1, -torch.ones_like(last))
+    m = (torch.cumsum(d, 0)[:nc] > 0).to(torch.uint8)
     moffs.append(sum(b.numel() for b in bytes_))
     bytes_.append(m)
     read += min(int(m.sum()) * chunk, ln)
