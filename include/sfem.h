@@ -924,6 +924,35 @@ int sfem_boundary_covector(const void* g, int nodal, const int32_t* facets,
                            int64_t num_facets, const void* wj,
                            const void* bmat, int ndim, int p1, int q,
                            void* out_local, int dtype, sfem_stream_t stream);
+/* The facet mass operator of a Robin term (core/fespace.py boundary_mass):
+ * M_f = (B (x) B)^T diag(aw) (B (x) B), aw (F, q^(ndim-1)) = alpha wJ at the
+ * points, formed once by the caller.  Same sizes, pairs and launch shape as
+ * the covector.  `facets` may store a node as ~id (a Dirichlet node): that
+ * slot reads 0 and its output is 0, so the term loses the Dirichlet rows and
+ * columns, like the masked volume operator.
+ * sfem_boundary_mass_apply: out_local (F, p1^(ndim-1)) = scale M_f u_f, u_f
+ *                           gathered from u (N,) through `facets`;
+ * sfem_boundary_mass_diag:  out_local (F, p1^(ndim-1)) = scale diag(M_f) =
+ *                           scale sum_q aw_q prod_c B(q_c, i_c)^2;
+ * sfem_boundary_add_rows:   out[rows[r]] += sum over s in [offsets[r],
+ *                           offsets[r+1]) of local[slots[s]], summed in slot
+ *                           order, for r < num_rows (rows int32, distinct;
+ *                           offsets int64 (num_rows + 1); slots int32).  Only
+ *                           the listed rows are read or written: the Robin
+ *                           term costs O(boundary), with no atomics.         */
+int sfem_boundary_mass_apply(const void* u, const int32_t* facets,
+                             int64_t num_facets, const void* aw,
+                             const void* bmat, int ndim, int p1, int q,
+                             double scale, void* out_local, int dtype,
+                             sfem_stream_t stream);
+int sfem_boundary_mass_diag(const int32_t* facets, int64_t num_facets,
+                            const void* aw, const void* bmat, int ndim, int p1,
+                            int q, double scale, void* out_local, int dtype,
+                            sfem_stream_t stream);
+int sfem_boundary_add_rows(const void* local, const int32_t* rows,
+                           const int64_t* offsets, const int32_t* slots,
+                           int64_t num_rows, void* out, int dtype,
+                           sfem_stream_t stream);
 /* y = a*x + b*y (plain fused vector update used outside the CG core)         */
 int sfem_axpby(double a, const void* x, double b, void* y, int64_t count,
                int dtype, sfem_stream_t stream);

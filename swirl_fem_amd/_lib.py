@@ -206,6 +206,12 @@ SIGNATURES = {
                            c_i32, c_i32, c_ptr, c_ptr, c_i32, c_ptr],
     'sfem_boundary_covector': [c_ptr, c_i32, c_ptr, c_i64, c_ptr, c_ptr,
                                c_i32, c_i32, c_i32, c_ptr, c_i32, c_ptr],
+    'sfem_boundary_mass_apply': [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i32,
+                                 c_i32, c_i32, c_dbl, c_ptr, c_i32, c_ptr],
+    'sfem_boundary_mass_diag': [c_ptr, c_i64, c_ptr, c_ptr, c_i32, c_i32,
+                                c_i32, c_dbl, c_ptr, c_i32, c_ptr],
+    'sfem_boundary_add_rows': [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i32,
+                               c_ptr],
     'sfem_ell_spmv': [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_i64, c_i64,
                       c_ptr, c_i64, c_i32, c_ptr],
     'sfem_abi_version': [],

@@ -1428,3 +1428,61 @@ def boundary_covector(g, nodal, facets, wj, bmat, ndim):
         int(ndim), p1, q, _ptr(out), _dtype_code(g), _stream(dev)),
         'sfem_boundary_covector')
   return out
+
+
+def boundary_mass(u, facets, aw, bmat, ndim, scale=1.0, diag=False, out=None):
+  """Facet-local scale (B (x) B)^T (aw (B (x) B) u_f), (F, (P+1)^(d-1)), or
+  with `diag` the facet-local diagonal of that operator (u unread).  Slots of
+  `facets` stored as ~id read 0 and write 0 (`sfem_boundary_mass_apply`,
+  `sfem_boundary_mass_diag`)."""
+  dev = _dev(facets, aw, bmat)
+  if bmat.dtype != aw.dtype or (not diag and u.dtype != aw.dtype):
+    raise ValueError('boundary_mass: one dtype for u, aw and B')
+  q, p1 = bmat.shape
+  F = facets.shape[0]
+  if (facets.dtype != torch.int32 or
+      tuple(facets.shape) != (F, p1 ** (ndim - 1))):
+    raise ValueError(f'boundary_mass: facets must be (F, {p1 ** (ndim - 1)}) '
+                     'int32')
+  if tuple(aw.shape) != (F, q ** (ndim - 1)):
+    raise ValueError('boundary_mass: aw does not match the facets')
+  shape = (F, p1 ** (ndim - 1))
+  if out is None:
+    out = torch.empty(shape, dtype=aw.dtype, device=dev)
+  elif (tuple(out.shape) != shape or out.dtype != aw.dtype or
+        not out.is_contiguous()):
+    raise ValueError(f'boundary_mass: `out` must be a dense {shape} tensor')
+  with torch.cuda.device(dev):
+    if diag:
+      _lib.check(_lib.load().sfem_boundary_mass_diag(
+          _ptr(facets), F, _ptr(aw), _ptr(bmat), int(ndim), p1, q,
+          float(scale), _ptr(out), _dtype_code(aw), _stream(dev)),
+          'sfem_boundary_mass_diag')
+    else:
+      if not u.is_contiguous() or u.dim() != 1:
+        raise ValueError('boundary_mass: u must be a dense (N,) vector')
+      _lib.check(_lib.load().sfem_boundary_mass_apply(
+          _ptr(u), _ptr(facets), F, _ptr(aw), _ptr(bmat), int(ndim), p1, q,
+          float(scale), _ptr(out), _dtype_code(aw), _stream(dev)),
+          'sfem_boundary_mass_apply')
+  return out
+
+
+def boundary_add_rows(local, rows, offsets, slots, out):
+  """out[rows[r]] += sum of local[slots[offsets[r]:offsets[r+1]]] in slot
+  order, in place; other entries of `out` untouched
+  (`sfem_boundary_add_rows`)."""
+  dev = _dev(local, rows, offsets, slots, out)
+  if (local.dtype != out.dtype or not local.is_contiguous() or
+      not out.is_contiguous() or out.dim() != 1):
+    raise ValueError('boundary_add_rows: dense values and an (N,) `out` of '
+                     'one dtype')
+  if (rows.dtype != torch.int32 or slots.dtype != torch.int32 or
+      offsets.dtype != torch.int64 or offsets.numel() != rows.numel() + 1):
+    raise ValueError('boundary_add_rows: rows / slots int32, offsets int64 '
+                     '(rows + 1)')
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_boundary_add_rows(
+        _ptr(local), _ptr(rows), _ptr(offsets), _ptr(slots), rows.numel(),
+        _ptr(out), _dtype_code(out), _stream(dev)), 'sfem_boundary_add_rows')
+  return out

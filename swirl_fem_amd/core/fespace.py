@@ -23,6 +23,10 @@ How it runs here
     `sfem_boundary_geom` / `sfem_boundary_covector` with the space's 1D rule
     in each facet direction, and `sfem_scatter_csr` sums the facet values per
     node in a fixed order.
+  * `boundary_mass` is the facet mass operator of a Robin term,
+    `<alpha u, v>` over a group: `sfem_boundary_mass_apply` on each facet,
+    then `sfem_boundary_add_rows` adds the facet values into the operator's
+    output on the group's nodes only, in a fixed order.
 """
 
 from __future__ import annotations
@@ -440,6 +444,55 @@ class FiniteElementSpace:
                              plan['slots'], mesh.num_nodes)
     return mesh.exchange(out)
 
+  def boundary_mass(self, group: str, alpha,
+                    dirichlet_mask=None) -> 'BoundaryMassOperator':
+    """The facet mass operator `<alpha u, v>` over the facets of `group`
+    (the operator term of a Robin condition du/dn + alpha u = g).
+
+    `alpha` >= 0 takes the forms of `boundary_covector`'s `g`: a scalar, `(N,)`
+    nodal values (interpolated to the points once), `(F, Q^(d-1))` point
+    values or a callable on the `(M, d)` points.  `dirichlet_mask` (N,) bool:
+    those rows and columns are removed, as in the masked volume operator.
+    """
+    mesh = self.mesh
+    if not callable(alpha):
+      a = torch.as_tensor(alpha, dtype=self.dtype)
+      if a.dim() == 0 and not bool(a >= 0):
+        raise ValueError(f'alpha must be >= 0, got {float(a)}')
+      if a.dim() != 0 and bool((a < 0).any()):
+        raise ValueError('alpha has negative values')
+    plan = self._boundary_plan(group)
+    facets, xq, wj = plan['facets'], plan['xq'], plan['wj']
+    if callable(alpha):
+      a = torch.as_tensor(alpha(xq.reshape(-1, mesh.ndim)), dtype=self.dtype,
+                          device=self.device)
+      if a.numel() != wj.numel():
+        raise ValueError(f'the callable returned {tuple(a.shape)} values for '
+                         f'{wj.numel()} points')
+      a = a.reshape(wj.shape)
+    else:
+      a = torch.as_tensor(alpha, dtype=self.dtype, device=self.device)
+      if a.dim() == 0:
+        a = a.expand(wj.shape)
+      elif tuple(a.shape) == (mesh.num_nodes,):
+        a = a[facets.long()]                              # (F, (P+1)^(d-1))
+        if mesh.ndim == 3:
+          p1 = mesh.gridpoints_1d.num_points
+          a = a.reshape(-1, p1, p1)
+        if mesh.ndim > 1:
+          i1, _ = self._matrices()
+          a = (torch.einsum('qi,rj,fij->fqr', i1, i1, a) if mesh.ndim == 3
+               else torch.einsum('qi,fi->fq', i1, a))
+        a = a.reshape(wj.shape)
+      elif tuple(a.shape) != tuple(wj.shape):
+        raise ValueError(f'alpha must be a scalar, ({mesh.num_nodes},) nodal '
+                         f'values or {tuple(wj.shape)} point values; got '
+                         f'{tuple(a.shape)}')
+    if bool((a < 0).any()):
+      raise ValueError('alpha has negative values')
+    return BoundaryMassOperator(self, facets, wj, (a * wj).contiguous(),
+                                dirichlet_mask)
+
   # -------------------------------------------------------- fused operators
   def helmholtz_operator(self, dirichlet_mask=None, geometry='auto',
                          assembly='auto'):
@@ -470,6 +523,126 @@ class FiniteElementSpace:
                                               assembly)
     self._cache[key] = (dirichlet_mask, op)
     return op
+
+
+class BoundaryMassOperator:
+  """`scale * M u` with M the facet mass matrix `(B (x) B)^T diag(aw) (B (x) B)`
+  of every facet, summed over the facets' nodes.
+
+  `facets` (F, (P+1)^(d-1)) int32 node ids, `wj` (F, Q^(d-1)) the facet
+  weights at the points of the space's rule, `aw` alpha times them;
+  `dirichlet_mask`: the rows and columns removed (a facet slot of a
+  Dirichlet node is stored as ~id, `pmg.encode_rows`).  `apply` costs
+  O(boundary): one wave per facet,
+  then one thread per non-Dirichlet node of the group adds that node's facet
+  values in a fixed order into the output.  No exchange: a caller on a mesh
+  with periodic images sums them with its own.  In 1D a facet is a point and
+  the term is alpha u there.
+  """
+
+  def __init__(self, fespace, facets, wj, aw, dirichlet_mask=None):
+    mesh = fespace.mesh
+    self.fespace, self.ndim = fespace, mesh.ndim
+    self.facets = facets.to(torch.int32).contiguous()
+    self.wj = wj
+    self.aw = aw.to(fespace.dtype).contiguous()
+    self.dirichlet = dirichlet_mask
+    host = self.facets.cpu().numpy()
+    dmask = (None if dirichlet_mask is None else
+             dirichlet_mask.cpu().numpy().astype(bool))
+    rows, offsets, slots = boundary_rows(host, mesh.num_nodes, dmask)
+    dev = fespace.device
+    self.rows = torch.as_tensor(rows, device=dev)
+    self.offsets = torch.as_tensor(offsets, device=dev)
+    self.slots = torch.as_tensor(slots, device=dev)
+    if dirichlet_mask is None:
+      self.encoded = self.facets
+    else:
+      self.encoded = torch.where(dirichlet_mask.to(dev)[self.facets.long()],
+                                 ~self.facets, self.facets).contiguous()
+    if self.ndim == 1:
+      # the alpha of every row (the sum over the point facets at its node)
+      aw1 = self.aw[:, 0].double().cpu().numpy()
+      ra = np.array([aw1[slots[offsets[r]:offsets[r + 1]]].sum()
+                     for r in range(rows.size)])
+      self._row_alpha = torch.as_tensor(ra, dtype=fespace.dtype, device=dev)
+      self._rows_long = self.rows.long()
+    else:
+      self.bmat = fespace._matrices()[0]
+      self._local = torch.empty(self.facets.shape, dtype=fespace.dtype,
+                                device=dev)
+
+  @property
+  def num_nodes(self) -> int:
+    return self.fespace.mesh.num_nodes
+
+  def total_weight(self) -> float:
+    """sum(alpha wJ) over the group: > 0 iff alpha > 0 on a set of positive
+    measure."""
+    return float(self.aw.double().sum())
+
+  def apply(self, u, scale=1.0, out=None):
+    """out += scale M u on the group's nodes (every other entry untouched);
+    a fresh vector when `out` is None."""
+    if out is None:
+      out = torch.zeros(self.num_nodes, dtype=u.dtype, device=u.device)
+    if self.ndim == 1:
+      r = self._rows_long
+      out[r] += scale * self._row_alpha * u[r]
+      return out
+    _ops.boundary_mass(u.contiguous(), self.encoded, self.aw, self.bmat,
+                       self.ndim, scale, out=self._local)
+    return _ops.boundary_add_rows(self._local, self.rows, self.offsets,
+                                  self.slots, out)
+
+  def diagonal(self) -> torch.Tensor:
+    """The assembled (N,) diagonal of M (0 off the group and on Dirichlet
+    rows)."""
+    out = torch.zeros(self.num_nodes, dtype=self.aw.dtype,
+                      device=self.aw.device)
+    if self.ndim == 1:
+      out[self._rows_long] = self._row_alpha
+      return out
+    loc = _ops.boundary_mass(None, self.encoded, self.aw, self.bmat,
+                             self.ndim, 1.0, diag=True)
+    return _ops.boundary_add_rows(loc, self.rows, self.offsets, self.slots,
+                                  out)
+
+  def local_matrices(self) -> torch.Tensor:
+    """(F, n, n) facet matrices (Dirichlet rows and columns zero) for host
+    assembly with the rows of `facets`: unit vectors through the kernel."""
+    F, n = self.facets.shape
+    dev, dt = self.aw.device, self.aw.dtype
+    if self.ndim == 1:
+      keep = self.encoded[:, 0] >= 0
+      return (self.aw[:, 0] * keep).reshape(F, 1, 1)
+    ids = torch.arange(F * n, dtype=torch.int32, device=dev).reshape(F, n)
+    ids = torch.where(self.encoded >= 0, ids, ~ids).contiguous()
+    cols = []
+    for j in range(n):
+      u = torch.zeros(F * n, dtype=dt, device=dev)
+      u[j::n] = 1.0
+      cols.append(_ops.boundary_mass(u, ids, self.aw, self.bmat, self.ndim))
+    return torch.stack(cols, dim=-1)
+
+
+def boundary_rows(facets: np.ndarray, num_nodes: int,
+                  dirichlet: np.ndarray | None = None):
+  """The compact CSR of `sfem_boundary_add_rows`: `(rows (R,) int32,
+  offsets (R+1,) int64, slots int32)` over the distinct nodes of `facets`
+  that are not `dirichlet`, ascending, with each row's facet slots ascending
+  (a fixed summation order)."""
+  flat = np.asarray(facets, np.int64).reshape(-1)
+  if flat.size and (flat.min() < 0 or flat.max() >= num_nodes):
+    raise ValueError(f'facet node ids outside [0, {num_nodes})')
+  order = np.argsort(flat, kind='stable')
+  rows, counts = np.unique(flat[order], return_counts=True)
+  keep = (np.ones(rows.size, dtype=bool) if dirichlet is None else
+          ~np.asarray(dirichlet, bool)[rows])
+  slots = order[np.repeat(keep, counts)]
+  offsets = np.zeros(int(keep.sum()) + 1, dtype=np.int64)
+  offsets[1:] = np.cumsum(counts[keep])
+  return (rows[keep].astype(np.int32), offsets, slots.astype(np.int32))
 
 
 def boundary_csr(facets: np.ndarray, num_nodes: int):

@@ -17,6 +17,13 @@
 // sfem_boundary_covector: c_f = (B (x) B)^T (wJ g) with g given at the points,
 //   or gathered at the facet nodes and interpolated by B (x) B here.  The
 //   element-local c_f are summed per node by sfem_scatter_csr (no atomics).
+// sfem_boundary_mass_apply: the facet mass operator of a Robin term,
+//   r_f = scale (B (x) B)^T (aw (B (x) B) u_f), u_f gathered through the facet
+//   rows; a slot stored as ~id (a Dirichlet node) reads 0 and writes 0.
+// sfem_boundary_mass_diag: the facet-local diagonal of the same operator,
+//   scale (B.B (x) B.B)^T aw (B.B the entrywise square), same slot rule.
+// sfem_boundary_add_rows: out[rows[r]] += the facet-local values of the row's
+//   slots, summed in slot order: touches the group's nodes only, no atomics.
 #include "sfem_common.h"
 
 namespace sfem {
@@ -189,6 +196,143 @@ boundary_covector_kernel(const T* __restrict__ g, int nodal,
   for (int t = lane; t < nf; t += 64) out[f * nf + t] = res[t];
 }
 
+// Robin facet mass: one wave per facet, as boundary_covector_kernel.  diag:
+// the transposed pass of B.B on scale aw instead (u unread).
+template <typename T, int K, int P1, int Q>
+__global__ void __launch_bounds__(64)
+boundary_mass_kernel(const T* __restrict__ u,
+                     const int32_t* __restrict__ facets,
+                     const T* __restrict__ aw, const T* __restrict__ bmat,
+                     T scale, int diag, T* __restrict__ out, int p1_rt,
+                     int q_rt) {
+  const int p1 = P1 ? P1 : p1_rt;
+  const int q = Q ? Q : q_rt;
+  const int nf = K == 1 ? p1 : p1 * p1;
+  const int nq = K == 1 ? q : q * q;
+  const int big = p1 > q ? p1 : q;
+  const int cap = K == 1 ? big : big * big;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  T* b = reinterpret_cast<T*>(smem_raw);           // [q][p1]
+  T* bt = b + q * p1;                              // [p1][q]
+  T* buf0 = bt + q * p1;
+  T* buf1 = buf0 + cap;
+  const int lane = threadIdx.x;
+  const int64_t f = blockIdx.x;
+  for (int t = lane; t < q * p1; t += 64) {
+    const int o = t / q, i = t - o * q;
+    const T v = bmat[i * p1 + o];
+    b[t] = bmat[t];
+    bt[t] = diag ? v * v : v;
+  }
+  T* h;
+  if (diag) {
+    h = buf0;
+    for (int t = lane; t < nq; t += 64) h[t] = scale * aw[f * nq + t];
+  } else {
+    for (int t = lane; t < nf; t += 64) {
+      const int32_t id = facets[f * nf + t];
+      buf0[t] = id >= 0 ? u[id] : T(0);
+    }
+    __syncthreads();
+    h = bnd_tensor<T, K, P1, Q>(buf0, buf1, b, p1, q, lane);
+    for (int t = lane; t < nq; t += 64) h[t] *= scale * aw[f * nq + t];
+  }
+  __syncthreads();
+  T* other = h == buf0 ? buf1 : buf0;
+  const T* res = bnd_tensor<T, K, Q, P1>(h, other, bt, q, p1, lane);
+  for (int t = lane; t < nf; t += 64)
+    out[f * nf + t] = facets[f * nf + t] >= 0 ? res[t] : T(0);
+}
+
+template <typename T, int K, int P1, int Q>
+int launch_mass(const void* u, const int32_t* facets, const void* aw,
+                const void* bmat, double scale, int diag, void* out,
+                int64_t F, int p1, int q, hipStream_t st) {
+  const size_t big = p1 > q ? p1 : q;
+  const size_t lds = (2 * (size_t)q * p1 + 2 * bnd_pow((int)big, K)) *
+                     sizeof(T);
+  if (lds > 64 * 1024) return SFEM_EUNSUPPORTED;
+  hipLaunchKernelGGL((boundary_mass_kernel<T, K, P1, Q>), dim3((unsigned)F),
+                     dim3(64), lds, st, (const T*)u, facets, (const T*)aw,
+                     (const T*)bmat, (T)scale, diag, (T*)out, p1, q);
+  return SFEM_OK;
+}
+
+// the compiled (P+1, Q) pairs of dispatch_boundary
+template <typename T, int K>
+int dispatch_mass(const void* u, const int32_t* facets, const void* aw,
+                  const void* bmat, double scale, int diag, void* out,
+                  int64_t F, int p1, int q, hipStream_t st) {
+#define SFEM_MASS_PAIR(N)                                                    \
+  if (p1 == N && q == N)                                                     \
+    return launch_mass<T, K, N, N>(u, facets, aw, bmat, scale, diag, out, F, \
+                                   p1, q, st);                               \
+  if (p1 == N && q == N + 1)                                                 \
+    return launch_mass<T, K, N, N + 1>(u, facets, aw, bmat, scale, diag,     \
+                                       out, F, p1, q, st);
+  SFEM_MASS_PAIR(2) SFEM_MASS_PAIR(3) SFEM_MASS_PAIR(4) SFEM_MASS_PAIR(5)
+  SFEM_MASS_PAIR(6) SFEM_MASS_PAIR(7) SFEM_MASS_PAIR(8) SFEM_MASS_PAIR(9)
+  SFEM_MASS_PAIR(10) SFEM_MASS_PAIR(11) SFEM_MASS_PAIR(12) SFEM_MASS_PAIR(13)
+#undef SFEM_MASS_PAIR
+  return launch_mass<T, K, 0, 0>(u, facets, aw, bmat, scale, diag, out, F, p1,
+                                 q, st);
+}
+
+int boundary_mass(const void* u, const int32_t* facets, int64_t F,
+                  const void* aw, const void* bmat, int ndim, int p1, int q,
+                  double scale, int diag, void* out, int dtype,
+                  sfem_stream_t stream) {
+  const char* who = diag ? "sfem_boundary_mass_diag"
+                         : "sfem_boundary_mass_apply";
+  SFEM_REQUIRE(F >= 0 && F <= 0x7fffffff, "%s: bad facet count", who);
+  SFEM_REQUIRE(ndim == 2 || ndim == 3, "%s: ndim=%d (2 or 3)", who, ndim);
+  SFEM_REQUIRE(p1 >= 2 && p1 <= BND_MAX_POINTS && q >= 1 &&
+                   q <= BND_MAX_POINTS,
+               "%s: need 2 <= P+1 <= %d and 1 <= Q <= %d, got %d, %d", who,
+               BND_MAX_POINTS, BND_MAX_POINTS, p1, q);
+  SFEM_REQUIRE(dtype == SFEM_F32 || dtype == SFEM_F64,
+               "%s: unknown dtype %d", who, dtype);
+  if (F == 0) return SFEM_OK;
+  SFEM_REQUIRE(facets && aw && bmat && out && (diag || u),
+               "%s: null pointer", who);
+  hipStream_t st = as_stream(stream);
+  int rc;
+  if (dtype == SFEM_F64)
+    rc = ndim == 3 ? dispatch_mass<double, 2>(u, facets, aw, bmat, scale, diag,
+                                              out, F, p1, q, st)
+                   : dispatch_mass<double, 1>(u, facets, aw, bmat, scale, diag,
+                                              out, F, p1, q, st);
+  else
+    rc = ndim == 3 ? dispatch_mass<float, 2>(u, facets, aw, bmat, scale, diag,
+                                             out, F, p1, q, st)
+                   : dispatch_mass<float, 1>(u, facets, aw, bmat, scale, diag,
+                                             out, F, p1, q, st);
+  if (rc != SFEM_OK) {
+    set_error("%s: P+1=%d, Q=%d, ndim=%d does not fit in LDS", who, p1, q,
+              ndim);
+    return rc;
+  }
+  SFEM_LAUNCH_CHECK();
+  return SFEM_OK;
+}
+
+// One thread per listed row: the row's slots summed in order, then added.
+template <typename T>
+__global__ void __launch_bounds__(256)
+boundary_add_rows_kernel(const T* __restrict__ local,
+                         const int32_t* __restrict__ rows,
+                         const int64_t* __restrict__ offsets,
+                         const int32_t* __restrict__ slots,
+                         T* __restrict__ out, int64_t num_rows) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= num_rows) return;
+  const int64_t s1 = offsets[r + 1];
+  T acc = T(0);
+  for (int64_t s = offsets[r]; s < s1; ++s) acc += local[slots[s]];
+  const int32_t v = rows[r];
+  out[v] = out[v] + acc;
+}
+
 template <typename T, int K, int P1, int Q>
 int launch_boundary(bool covector, const void* in, int nodal,
                     const int32_t* facets, const void* bmat, const void* dmat,
@@ -308,4 +452,47 @@ extern "C" int sfem_boundary_covector(const void* g, int nodal,
                                       sfem_stream_t stream) {
   return boundary(true, g, nodal, facets, bmat, nullptr, nullptr, wj,
                   out_local, nullptr, num_facets, ndim, p1, q, dtype, stream);
+}
+
+extern "C" int sfem_boundary_mass_apply(const void* u, const int32_t* facets,
+                                        int64_t num_facets, const void* aw,
+                                        const void* bmat, int ndim, int p1,
+                                        int q, double scale, void* out_local,
+                                        int dtype, sfem_stream_t stream) {
+  return boundary_mass(u, facets, num_facets, aw, bmat, ndim, p1, q, scale, 0,
+                       out_local, dtype, stream);
+}
+
+extern "C" int sfem_boundary_mass_diag(const int32_t* facets,
+                                       int64_t num_facets, const void* aw,
+                                       const void* bmat, int ndim, int p1,
+                                       int q, double scale, void* out_local,
+                                       int dtype, sfem_stream_t stream) {
+  return boundary_mass(nullptr, facets, num_facets, aw, bmat, ndim, p1, q,
+                       scale, 1, out_local, dtype, stream);
+}
+
+extern "C" int sfem_boundary_add_rows(const void* local, const int32_t* rows,
+                                      const int64_t* offsets,
+                                      const int32_t* slots, int64_t num_rows,
+                                      void* out, int dtype,
+                                      sfem_stream_t stream) {
+  SFEM_REQUIRE(num_rows >= 0, "sfem_boundary_add_rows: bad row count");
+  SFEM_REQUIRE(dtype == SFEM_F32 || dtype == SFEM_F64,
+               "sfem_boundary_add_rows: unknown dtype %d", dtype);
+  if (num_rows == 0) return SFEM_OK;
+  SFEM_REQUIRE(local && rows && offsets && slots && out,
+               "sfem_boundary_add_rows: null pointer");
+  hipStream_t st = as_stream(stream);
+  const dim3 grid((unsigned)((num_rows + 255) / 256)), block(256);
+  if (dtype == SFEM_F64)
+    hipLaunchKernelGGL(boundary_add_rows_kernel<double>, grid, block, 0, st,
+                       (const double*)local, rows, offsets, slots,
+                       (double*)out, num_rows);
+  else
+    hipLaunchKernelGGL(boundary_add_rows_kernel<float>, grid, block, 0, st,
+                       (const float*)local, rows, offsets, slots, (float*)out,
+                       num_rows);
+  SFEM_LAUNCH_CHECK();
+  return SFEM_OK;
 }

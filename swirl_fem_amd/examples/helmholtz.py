@@ -1,7 +1,9 @@
-"""Helmholtz / Poisson solves with inhomogeneous Dirichlet and Neumann data.
+"""Helmholtz / Poisson solves with inhomogeneous Dirichlet, Neumann and Robin
+data.
 
     lambda0 u - lambda1 lap u = f   in the mesh,
     u = g_D on Dirichlet groups,   du/dn = g_N on Neumann groups,
+    du/dn + alpha u = g_R on Robin groups (alpha >= 0),
     du/dn = 0 on the rest of the boundary.
 
 The boundary data the reference's `solve_poisson` docstring promises and
@@ -18,6 +20,12 @@ with K the operator of `solve_poisson` (Dirichlet rows and columns removed)
 and b_N the sum of `FiniteElementSpace.boundary_covector(group, g_N)` over the
 Neumann groups; u = w + u_D.  (lambda0 B + lambda1 A) u_D is applied by an
 operator without a mask, so that it reads the Dirichlet values.
+
+A Robin group adds lambda1 <alpha u, v> to the operator
+(`FiniteElementSpace.boundary_mass`, masked like K: where it shares nodes with
+a Dirichlet group, Dirichlet wins), lambda1 <g_R, v> to the right-hand side
+and -lambda1 M_R u_D (unmasked) to the lift.  The Jacobi diagonal and every
+p-multigrid level carry the term.
 
 On a mesh with periodic images the unknowns are the lowest-numbered node of
 each class: K = R QQ^T A QQ^T R^T with R the restriction to those nodes
@@ -66,11 +74,14 @@ def solve_helmholtz(mesh: Mesh, forcing,
 
   `boundary_conditions` maps physical group names to `(BCType, BCValue)`:
   DIRICHLET sets u = value on the group's nodes, NEUMANN sets du/dn = value
-  (outward normal) on its facets.  A value is a scalar, an `(N,)` nodal array
-  (only the group's nodes are read) or a callable on coordinates: `(N, d)`
-  node coordinates for Dirichlet data, `(M, d)` facet quadrature points for
-  Neumann data.  Where Dirichlet groups share a node, the later group in the
-  mapping sets its value.  `forcing` is nodal.
+  (outward normal) on its facets, ROBIN with the value `(alpha, g)` sets
+  du/dn + alpha u = g there (alpha >= 0).  A value is a scalar, an `(N,)` nodal
+  array (only the group's nodes are read) or a callable on coordinates:
+  `(N, d)` node coordinates for Dirichlet data, `(M, d)` facet quadrature
+  points for Neumann and Robin data (alpha and g alike; alpha may also be
+  given at the `(F, Q^(d-1))` points of `boundary_points`).  Where Dirichlet
+  groups share a node, the later group in the mapping sets its value.
+  `forcing` is nodal.
 
   `preconditioner`: None, 'jacobi' or 'pmg', as in `solve_poisson` (on a
   mesh without periodic images).  `rtol` is relative to the norm of the
@@ -93,6 +104,7 @@ def solve_helmholtz(mesh: Mesh, forcing,
   dirichlet = torch.zeros(mesh.num_nodes, dtype=torch.bool, device=device)
   u_D = torch.zeros(mesh.num_nodes, dtype=dtype, device=device)
   neumann = []
+  robin = []
   for group, (bctype, value) in boundary_conditions.items():
     if bctype == BCType.DIRICHLET:
       if group not in mesh.physical_masks:
@@ -102,13 +114,27 @@ def solve_helmholtz(mesh: Mesh, forcing,
       dirichlet = dirichlet | m
     elif bctype == BCType.NEUMANN:
       neumann.append((group, value))
+    elif bctype is BCType.ROBIN:
+      if not (isinstance(value, (tuple, list)) and len(value) == 2):
+        raise ValueError(f'a ROBIN value is a pair (alpha, g); got {value!r} '
+                         f'on {group!r}')
+      alpha = value[0]
+      if not callable(alpha) and torch.as_tensor(alpha).dim() == 0 and not (
+          float(alpha) >= 0.0):
+        raise ValueError(f'Robin alpha must be >= 0, got {alpha!r} on '
+                         f'{group!r}')
+      robin.append((group, alpha, value[1]))
     else:
       raise ValueError(f'unsupported boundary condition type {bctype!r} on '
-                       f'{group!r}: DIRICHLET or NEUMANN')
+                       f'{group!r}: DIRICHLET, NEUMANN or ROBIN')
   has_dirichlet = bool(dirichlet.any())
-  if lambda0 == 0.0 and not has_dirichlet:
-    raise ValueError('lambda0 = 0 with no Dirichlet node: the problem is '
-                     'singular (u is determined up to a constant)')
+  singular = ValueError('lambda0 = 0 with no Dirichlet node and no Robin '
+                        'alpha > 0: the problem is singular (u is determined '
+                        'up to a constant)')
+  if lambda0 == 0.0 and not has_dirichlet and all(
+      not callable(a) and torch.as_tensor(a).dim() == 0 and float(a) == 0.0
+      for _, a, _ in robin):
+    raise singular
 
   gi = mesh.exchange_gather_indices
   periodic = gi is not None and gi.numel() > 0
@@ -126,19 +152,42 @@ def solve_helmholtz(mesh: Mesh, forcing,
   from swirl_fem_amd.core import operators
   M = None
   mask = dirichlet if has_dirichlet else None
+  # the Robin terms <alpha u, v>: masked (in K) and whole (for the lift)
+  rmass = [fespace.boundary_mass(g, a, mask) for g, a, _ in robin]
+  rfull = ([fespace.boundary_mass(g, a) for g, a, _ in robin]
+           if has_dirichlet else rmass)
+  if lambda0 == 0.0 and not has_dirichlet and not sum(
+      r.total_weight() for r in rmass) > 0.0:
+    raise singular
+
+  def add_robin(u, out):
+    for r in rmass:
+      r.apply(u, lambda1, out=out)
+    return out
   if (fespace.is_collocated and operators.supports_fused(fespace) is None) or (
       not fespace.is_collocated and
       operators.supports_two_grid(fespace) is None):
     op = fespace.helmholtz_operator(mask)
     full = fespace.helmholtz_operator(None)
-    K = lambda u: op.apply(u, lambda0, lambda1)
+    if rmass:
+      K = lambda u: add_robin(u, op.apply(u, lambda0, lambda1))
+    else:
+      K = lambda u: op.apply(u, lambda0, lambda1)
     H = lambda u, l0, l1: full.apply(u, l0, l1)
     if preconditioner == 'jacobi':
       from swirl_fem_amd.linalg.jacobi import JacobiPreconditioner
-      M = JacobiPreconditioner(op, lambda0, lambda1)
+      if rmass:
+        diag = op.diagonal(lambda0, lambda1)
+        for r in rmass:
+          diag = diag + lambda1 * r.diagonal()
+        M = JacobiPreconditioner(diag)
+      else:
+        M = JacobiPreconditioner(op, lambda0, lambda1)
     elif preconditioner == 'pmg':
       from swirl_fem_amd.linalg.pmg import PMultigridPreconditioner
-      M = PMultigridPreconditioner(op, lambda0, lambda1)
+      M = PMultigridPreconditioner(
+          op, lambda0, lambda1,
+          boundary_terms=[(r, lambda1) for r in rmass] or None)
   elif preconditioner is not None:
     raise NotImplementedError(
         f"preconditioner={preconditioner!r} needs the fused operator: "
@@ -160,15 +209,19 @@ def solve_helmholtz(mesh: Mesh, forcing,
         out = out + l1 * mesh.scatter(fespace.local_covector(a, (uf, v)))
       return out
 
-    K = lambda u: H(u, lambda0, lambda1) * keep
+    K = lambda u: add_robin(u, H(u, lambda0, lambda1)) * keep
 
   forcing = torch.as_tensor(forcing, dtype=dtype, device=device)
   rhs = H(forcing, 1.0, 0.0)
   if has_dirichlet:
     rhs = rhs - H(u_D, lambda0, lambda1)
+    for r in rfull:
+      r.apply(u_D, -lambda1, out=rhs)
   rhs = mesh.exchange(rhs)
   for group, value in neumann:
     rhs = rhs + lambda1 * fespace.boundary_covector(group, value)
+  for group, _, g in robin:
+    rhs = rhs + lambda1 * fespace.boundary_covector(group, g)
   b = rhs * keep
 
   A = K

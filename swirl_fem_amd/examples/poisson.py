@@ -36,6 +36,9 @@ class BCType(enum.Enum):
   """Types of boundary conditions."""
   DIRICHLET = 'dirichlet'
   NEUMANN = 'neumann'
+  # du/dn + alpha u = g: the value is the pair (alpha, g)
+  # (examples/helmholtz.py; solve_poisson takes homogeneous data only)
+  ROBIN = 'robin'
 
 
 def solve_poisson(mesh: Mesh, forcing,

@@ -42,6 +42,16 @@ stops on the true-residual norm r.r <= max(tol^2 b.b, atol^2) instead of the
 reference's r.Mr (an energy norm when M ~ A^-1), with inner products summed in
 a fixed order.
 
+Robin terms (`boundary_terms`: `fespace.boundary_mass` operators with their
+scales): the finest level adds them to its apply and diagonal.
+A coarse level gets the same groups on its own nodes: each fine facet is
+matched to its (element, local face) by its corner ids (`coarse_facets`), the
+face's coarse nodes are taken from the coarse element rows, and the coarse
+alpha wJ is the facet mean of the fine alpha, sum(alpha wJ) / sum(wJ), times
+the coarse wJ.  The coarsest level's assembled matrix adds the facet matrices,
+so its spectrum bounds see them.  Without the term a pure Robin problem with
+lambda0 = 0 has singular coarse operators.
+
 Block partitions (`distributed.blocks.build_block_partition`, world > 1): every
 rank builds the hierarchy of its own block, and every vector of the V-cycle is
 *consistent* (equal on all ranks that hold a node), as in the partitioned CG:
@@ -341,6 +351,41 @@ def owner_bits(elements: torch.Tensor, num_nodes: int,
   return w.to(torch.int32).contiguous()
 
 
+def coarse_facets(fine_facets: np.ndarray, fine_corners: np.ndarray,
+                  celems: np.ndarray, ndim: int, pf: int,
+                  pc: int) -> np.ndarray:
+  """(F, (pc + 1)^(d-1)) coarse node rows of the facets (F, (pf + 1)^(d-1))
+  of the fine mesh: each fine facet is matched to the (element, local face)
+  whose corners it has (`fine_corners` (E, 2^d): the fine ids of the element
+  vertices in lexicographic order), and gets that face's coarse nodes from
+  `celems` in the element's lexicographic face order (its orientation may
+  differ from the fine facet's)."""
+  k = ndim - 1
+  fac = np.asarray(fine_facets, np.int64)
+  fine_corners = np.asarray(fine_corners, np.int64)
+  E = fine_corners.shape[0]
+  cl = _lex((2,) * ndim)
+  faces = np.stack([np.nonzero(cl[:, a] == s)[0] for a in range(ndim)
+                    for s in (0, 1)])                       # (2d, 2^k)
+  fkeys = np.sort(fine_corners[:, faces], axis=-1).reshape(-1, 2 ** k)
+  qkeys = np.sort(fac[:, _flat(_lex((2,) * k) * pf, pf + 1)], axis=-1)
+  ids, n_ids = _number_rows(np.concatenate([fkeys, qkeys]))
+  pos = np.full(n_ids, -1, dtype=np.int64)
+  pos[ids[:fkeys.shape[0]]] = np.arange(fkeys.shape[0])
+  face = pos[ids[fkeys.shape[0]:]]
+  if (face < 0).any():
+    raise ValueError('a boundary facet is not a face of any element')
+  e, fa = face // (2 * ndim), face % (2 * ndim)
+  cel = np.asarray(celems).reshape((E,) + (pc + 1,) * ndim)
+  out = np.empty((fac.shape[0], (pc + 1) ** k), dtype=np.int64)
+  for t in range(2 * ndim):
+    sel = np.nonzero(fa == t)[0]
+    if sel.size:
+      side = np.take(cel[e[sel]], 0 if t % 2 == 0 else pc, axis=1 + t // 2)
+      out[sel] = side.reshape(sel.size, -1)
+  return out
+
+
 def coarse_mesh(mesh, pc: int):
   """(coarse Mesh of order pc, coarse element index rows (E, (pc+1)^d) int64
   device tensor) derived from `mesh` (order > pc)."""
@@ -454,6 +499,7 @@ class _Level:
         torch.zeros(N, dtype=dt, device=dev) for _ in range(5))
     self.cheb = None
     self.lam_max = None
+    self.boundary = []          # [(BoundaryMassOperator, scale)]
     # transfer from the next coarser level (set by the hierarchy)
     self.transfer = None
 
@@ -481,6 +527,10 @@ class PMultigridPreconditioner:
   group of the exchanges and reductions.  Its exchanges go through the host
   transport: not `capturable`.
 
+  `boundary_terms`: None, or [(BoundaryMassOperator, scale)]: Robin terms
+  `scale * M` that the operator CG solves with adds to `op` (built with the
+  same Dirichlet mask); every level carries them (one partition only).
+
   `bounds`: None, or the spectrum estimates to use instead of computing them,
   as `spectral_bounds()` returns them (e.g. from the preconditioner of the
   same problem on one rank): {'lam_max': one per smoothed level, 'coarse':
@@ -492,7 +542,8 @@ class PMultigridPreconditioner:
   consistent = True        # consistent vectors in, consistent vectors out
 
   def __init__(self, op, lambda0=0.0, lambda1=1.0, *, orders=None,
-               smoother_degree=2, coarse_steps=None, bounds=None, group=None):
+               smoother_degree=2, coarse_steps=None, bounds=None, group=None,
+               boundary_terms=None):
     from swirl_fem_amd.core import operators
     if not isinstance(op, (operators.HelmholtzOperator,
                            operators.TwoGridHelmholtzOperator)):
@@ -502,6 +553,10 @@ class PMultigridPreconditioner:
     mesh = fes.mesh
     _check_mesh(mesh)
     self.plan, self.group = mesh.neighbor_plan, group
+    self.boundary_terms = [(b, float(s)) for b, s in (boundary_terms or [])]
+    if self.boundary_terms and self.plan is not None:
+      raise NotImplementedError('p-multigrid with Robin terms on a '
+                                'partitioned mesh')
     if self.plan is not None:
       if not isinstance(op, operators.HelmholtzOperator):
         raise NotImplementedError('p-multigrid on a partitioned mesh takes a '
@@ -645,8 +700,20 @@ class PMultigridPreconditioner:
         loc = op.apply_local(mesh.gather(u), l0, l1)
         return _ops.scatter_csr(loc.reshape(-1), offsets, slots,
                                 mesh.num_nodes, out=out)
-    dinv = self._dinv(op.diagonal(l0, l1))
-    return _Level(mesh, op, apply_fn, dirichlet, dinv)
+    diag = op.diagonal(l0, l1)
+    if self.boundary_terms:
+      base, terms = apply_fn, self.boundary_terms
+
+      def apply_fn(u, out):
+        base(u, out)
+        for b, s in terms:
+          b.apply(u, s, out=out)
+        return out
+      for b, s in terms:
+        diag = diag + s * b.diagonal()
+    lev = _Level(mesh, op, apply_fn, dirichlet, self._dinv(diag))
+    lev.boundary = self.boundary_terms
+    return lev
 
   def _dinv(self, d):
     interior = d != 0
@@ -676,9 +743,21 @@ class PMultigridPreconditioner:
     # (the coarsest level only assembles its element matrices)
     cop = fes.helmholtz_operator(cdir, assembly='auto' if (
         coarsest or self.plan is not None) else 'colored')
-    dinv = self._dinv(cop.diagonal(l0, l1))
-    lev = _Level(cmesh, cop, lambda u, out: self._exchange_(
-        cop.apply(u, l0, l1, out=out), cmesh), cdir, dinv)
+    cterms = self._coarse_terms(fine, fes, celems, cdir)
+    diag = cop.diagonal(l0, l1)
+    if cterms:
+      def apply_fn(u, out):
+        cop.apply(u, l0, l1, out=out)
+        for b, s in cterms:
+          b.apply(u, s, out=out)
+        return out
+      for b, s in cterms:
+        diag = diag + s * b.diagonal()
+    else:
+      apply_fn = lambda u, out: self._exchange_(cop.apply(u, l0, l1, out=out),
+                                                cmesh)
+    lev = _Level(cmesh, cop, apply_fn, cdir, self._dinv(diag))
+    lev.boundary = cterms
     lev.fespace = fes
     offsets, slots = cmesh.assembly_plan().csr()
     owner = owner_bits(fel, fmesh.num_nodes)
@@ -695,6 +774,33 @@ class PMultigridPreconditioner:
                           device=self.device),
         offsets=offsets, slots=slots, pc=pc + 1, pf=pf + 1)
     return lev
+
+  def _coarse_terms(self, fine, fes, celems, cdir):
+    """The Robin terms of the fine level on the coarse space `fes`."""
+    from swirl_fem_amd.core.fespace import BoundaryMassOperator
+    if not fine.boundary:
+      return []
+    fmesh, cmesh = fine.mesh, fes.mesh
+    d, pf, pc = fmesh.ndim, fmesh.order, cmesh.order
+    corners = torch.as_tensor(_flat(_lex((2,) * d) * pf, pf + 1),
+                              device=self.device)
+    fcorners = fmesh.elements[:, corners].cpu().numpy()
+    chost = celems.cpu().numpy()
+    i1, g1 = fes._matrices()
+    w = torch.as_tensor(fes.quadrature.weights, dtype=self.dtype,
+                        device=self.device)
+    out = []
+    for b, s in fine.boundary:
+      cf = coarse_facets(b.facets.cpu().numpy(), fcorners, chost, d, pf, pc)
+      cf = torch.as_tensor(cf, dtype=torch.int32, device=self.device)
+      _, wj = _ops.boundary_geom(cmesh.node_coords.contiguous(), cf, i1, g1, w)
+      den = b.wj.double().sum(dim=1)
+      mean = torch.where(den > 0, b.aw.double().sum(dim=1) /
+                         torch.where(den > 0, den, torch.ones_like(den)),
+                         torch.zeros_like(den))
+      aw = (mean[:, None].to(self.dtype) * wj).contiguous()
+      out.append((BoundaryMassOperator(fes, cf, wj, aw, cdir), s))
+    return out
 
   def _lanczos_max(self, lev):
     """Largest eigenvalue of D^-1 A (interior rows) from LANCZOS_STEPS steps
@@ -746,6 +852,14 @@ class PMultigridPreconditioner:
     rows = np.repeat(el[:, :, None], n, axis=2).reshape(-1)
     cols = np.repeat(el[:, None, :], n, axis=1).reshape(-1)
     A = sp.csr_matrix((K.reshape(-1), (rows, cols)), shape=(N, N))
+    for b, s in lev.boundary:          # Robin facet matrices
+      Kf = s * b.local_matrices().double().cpu().numpy()
+      fr = b.facets.cpu().numpy().astype(np.int64)
+      nf = fr.shape[1]
+      A = A + sp.csr_matrix((Kf.reshape(-1), (
+          np.repeat(fr[:, :, None], nf, axis=2).reshape(-1),
+          np.repeat(fr[:, None, :], nf, axis=1).reshape(-1))), shape=(N, N))
+    A = A.tocsr()
     A.sum_duplicates()
     # periodic images: the fine operator keeps them apart, so does this one
     if lev.dirichlet is not None:
