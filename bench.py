@@ -10,10 +10,14 @@ For N > 1 every rank owns one 64^3 block of a (px,py,pz)-blocked mesh (weak
 scaling; 8 GPUs = the 128^3, 2 M element mesh) and the shared-DOF exchange runs
 over RCCL.
 
-Prints ONE JSON line (rank 0): metric GDOF/s per CG iteration (whole job), the
-roofline of the dominant kernel (fused gather-apply-scatter, HBM-bound) and the
-CPU baseline (oracle = reference algorithm restated, timed on the host cores on
-a bounded sample).
+Prints ONE JSON line (rank 0): metric GDOF/s per CG iteration (whole job).  A
+plain run does only what that figure needs: set-up, warm-up, the timed steps,
+--dump-outputs if asked for, the line.  `--full` adds what takes runs of its
+own: the --repeats batches, the roofline of the dominant kernel (fused
+gather-apply-scatter, HBM-bound) and of the stored-factor path, per-rank apply
+and exchange times, the device stream figure, the comparison with the committed
+single-GPU time (`strong_ref`) and the CPU baseline (oracle = reference
+algorithm restated, timed on the host cores on a bounded sample).
 """
 
 from __future__ import annotations
@@ -221,9 +225,15 @@ def main():
   ap.add_argument('--warmup', type=int, default=10)
   ap.add_argument('--n', '--elems', dest='n', type=int, default=64, help='elements per dim per GPU')
   ap.add_argument('--p', type=int, default=7, help='polynomial order')
-  ap.add_argument('--no-cpu-baseline', action='store_true')
+  ap.add_argument('--full', action='store_true',
+                  help='besides the headline: the --repeats batches, kernel '
+                       'rooflines, per-rank apply / exchange times, the '
+                       'stream figure, strong_ref and the CPU baseline')
+  ap.add_argument('--no-cpu-baseline', action='store_true',
+                  help='--full: skip the CPU baseline')
   ap.add_argument('--no-general', action='store_true',
-                  help='skip timing the stored-factor kernel beside the default')
+                  help='--full: skip timing the stored-factor kernel beside '
+                       'the default')
   ap.add_argument('--geometry', default='auto',
                   choices=['auto', 'multilinear', 'stored'],
                   help="'auto': affine / multilinear elements evaluate their "
@@ -269,13 +279,14 @@ def main():
   ap.add_argument('--graph', action='store_true',
                   help='N=1: replay each CG iteration as one HIP graph launch')
   ap.add_argument('--repeats', type=int, default=4,
-                  help='further timed batches of --steps iterations after the '
-                       'one `value` is computed from; their ms per step go to '
-                       'config.repeat_ms_per_step (box-to-box and run-to-run '
-                       'spread of a 30 ms measurement)')
+                  help='--full: further timed batches of --steps iterations '
+                       'after the one `value` is computed from; their ms per '
+                       'step go to config.repeat_ms_per_step (box-to-box and '
+                       'run-to-run spread of a 30 ms measurement)')
   ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                   help='after the timed iterations (the --repeats batches '
-                       'included), write the CG iterate x (in the --dtype '
+                       'included, which run for it without --full too), '
+                       'write the CG iterate x (in the --dtype '
                        'precision; a fixed seeded sample of positions where '
                        'it exceeds 32 MB) and the residual r.r (float64) as '
                        'DIR/<name>.npy, so that two builds can be compared')
@@ -486,7 +497,10 @@ def rank_main(args, world, rank, device):
   ms_per_step = 1e3 * elapsed / args.steps
   value = N_global / (elapsed / args.steps) / 1e9
   repeat_ms = []
-  for _ in range(max(0, args.repeats)):
+  # --dump-outputs writes the iterate after the repeat batches: a plain run
+  # that dumps runs them too, so that it writes what a --full run writes
+  for _ in range(max(0, args.repeats) if args.full or args.dump_outputs
+                 else 0):
     barrier()
     t1 = time.perf_counter()
     for _ in range(args.steps):
@@ -500,116 +514,119 @@ def rank_main(args, world, rank, device):
   if args.dump_outputs:
     dump_outputs(args.dump_outputs, run, world, rank)
 
-  # ---- roofline of the dominant kernel: HIP events around ONE apply as the
-  # solver issues it -- the fused kernel and whatever it needs around it (the
-  # clearing of the atomically accumulated node range, when there is one)
-  u = run.p
-  from swirl_fem_amd import _ops
-
-  def time_apply(operator):
-    for _ in range(3):
-      operator.apply(u, args.mass_coeff, 1.0, out=out_buf)
-    torch.cuda.synchronize()
-    pairs = [(torch.cuda.Event(enable_timing=True),
-              torch.cuda.Event(enable_timing=True))
-             for _ in range(args.steps)]
-    for e0, e1 in pairs:
-      e0.record()
-      operator.apply(u, args.mass_coeff, 1.0, out=out_buf)
-      e1.record()
-    torch.cuda.synchronize()
-    return float(np.mean([x.elapsed_time(y) for x, y in pairs]))
-
-  # what the solver issues: with layered assembly (`CGRunner.layered`) the
-  # apply stores into an extended vector, nothing is cleared, no atomics
   layered = getattr(run, 'layered', None)
-  if layered is not None:
-    class _LayeredApply:       # same call shape as `HelmholtzOperator.apply`
-      def __init__(self, operator):
-        self.op, self.ext = operator, operator.new_extended()
-      def apply(self, v, l0, l1, out=None):
-        return self.op.apply_layered(v, self.ext, l0, l1)
-    solver_apply = _LayeredApply(op)
-  else:
-    solver_apply = op
-  kern_ms = time_apply(solver_apply)
-  # back-to-back applies (no event between them)
-  s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(
-      enable_timing=True)
-  s0.record()
-  for _ in range(args.steps):
-    solver_apply.apply(u, args.mass_coeff, 1.0, out=out_buf)
-  s1.record()
-  torch.cuda.synchronize()
-  apply_ms = s0.elapsed_time(s1) / args.steps
-  if layered is not None:
-    del solver_apply
-  per_rank = None
-  if world > 1:
-    # per-rank figures: local apply (above) and the interface exchange alone
-    from swirl_fem_amd.distributed import comm
-    w = torch.zeros_like(b)
-    for _ in range(3):
-      comm.neighbor_exchange_(w, part.plan)
-    barrier()
+  if args.full:
+    # ---- roofline of the dominant kernel: HIP events around ONE apply as the
+    # solver issues it -- the fused kernel and whatever it needs around it (the
+    # clearing of the atomically accumulated node range, when there is one)
+    u = run.p
+    from swirl_fem_amd import _ops
+
+    def time_apply(operator):
+      for _ in range(3):
+        operator.apply(u, args.mass_coeff, 1.0, out=out_buf)
+      torch.cuda.synchronize()
+      pairs = [(torch.cuda.Event(enable_timing=True),
+                torch.cuda.Event(enable_timing=True))
+               for _ in range(args.steps)]
+      for e0, e1 in pairs:
+        e0.record()
+        operator.apply(u, args.mass_coeff, 1.0, out=out_buf)
+        e1.record()
+      torch.cuda.synchronize()
+      return float(np.mean([x.elapsed_time(y) for x, y in pairs]))
+
+    # what the solver issues: with layered assembly (`CGRunner.layered`) the
+    # apply stores into an extended vector, nothing is cleared, no atomics
+    if layered is not None:
+      class _LayeredApply:       # same call shape as `HelmholtzOperator.apply`
+        def __init__(self, operator):
+          self.op, self.ext = operator, operator.new_extended()
+        def apply(self, v, l0, l1, out=None):
+          return self.op.apply_layered(v, self.ext, l0, l1)
+      solver_apply = _LayeredApply(op)
+    else:
+      solver_apply = op
+    kern_ms = time_apply(solver_apply)
+    # back-to-back applies (no event between them)
+    s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(
+        enable_timing=True)
     s0.record()
     for _ in range(args.steps):
-      comm.neighbor_exchange_(w, part.plan)
+      solver_apply.apply(u, args.mass_coeff, 1.0, out=out_buf)
     s1.record()
     torch.cuda.synchronize()
-    exchange_ms = s0.elapsed_time(s1) / args.steps
-    mine = torch.tensor([apply_ms, exchange_ms, float(part.plan.num_shared)],
-                        dtype=torch.float64, device=device)
-    every = comm.all_gather(mine)
-    per_rank = {'apply_ms': [float(t[0]) for t in every],
-                'exchange_ms': [float(t[1]) for t in every],
-                'interface_values': [int(t[2]) for t in every]}
-    del w
-  # the same mesh through the general-geometry path (6 stored factors per
-  # point are READ): the kernel whose traffic the stored-factor model describes
-  general = None
-  if world == 1 and args.geometry == 'auto' and not args.no_general:
-    op_g = fes.helmholtz_operator(mesh.physical_masks.get('boundary'),
-                                  geometry='stored')
-    general = time_apply(op_g)
-    stored_bytes = op_g.bytes_per_apply(args.mass_coeff)
-    stored_kernel = op_g.kernel_name(args.mass_coeff, 1.0)
-    del op_g
-  # device stream figure beside the vendor peak: y = a x + b y over
-  # N-vectors, 3 passes
-  xs, ys = torch.randn_like(b), torch.randn_like(b)
-  for _ in range(3):
-    _ops.axpby(1.0, xs, 0.5, ys)
-  s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(
-      enable_timing=True)
-  s0.record()
-  for _ in range(20):
-    _ops.axpby(1.0, xs, 0.5, ys)
-  s1.record()
-  torch.cuda.synchronize()
-  stream_gbs = 3 * xs.numel() * sizeof / (s0.elapsed_time(s1) / 20 * 1e-3) / 1e9
-  del xs, ys
+    apply_ms = s0.elapsed_time(s1) / args.steps
+    if layered is not None:
+      del solver_apply
+    per_rank = None
+    if world > 1:
+      # per-rank figures: local apply (above) and the interface exchange alone
+      from swirl_fem_amd.distributed import comm
+      w = torch.zeros_like(b)
+      for _ in range(3):
+        comm.neighbor_exchange_(w, part.plan)
+      barrier()
+      s0.record()
+      for _ in range(args.steps):
+        comm.neighbor_exchange_(w, part.plan)
+      s1.record()
+      torch.cuda.synchronize()
+      exchange_ms = s0.elapsed_time(s1) / args.steps
+      mine = torch.tensor([apply_ms, exchange_ms, float(part.plan.num_shared)],
+                          dtype=torch.float64, device=device)
+      every = comm.all_gather(mine)
+      per_rank = {'apply_ms': [float(t[0]) for t in every],
+                  'exchange_ms': [float(t[1]) for t in every],
+                  'interface_values': [int(t[2]) for t in every]}
+      del w
+    # the same mesh through the general-geometry path (6 stored factors per
+    # point are READ): the kernel whose traffic the stored-factor model
+    # describes
+    general = None
+    if world == 1 and args.geometry == 'auto' and not args.no_general:
+      op_g = fes.helmholtz_operator(mesh.physical_masks.get('boundary'),
+                                    geometry='stored')
+      general = time_apply(op_g)
+      stored_bytes = op_g.bytes_per_apply(args.mass_coeff)
+      stored_kernel = op_g.kernel_name(args.mass_coeff, 1.0)
+      del op_g
+    # device stream figure beside the vendor peak: y = a x + b y
+    # over N-vectors, 3 passes
+    xs, ys = torch.randn_like(b), torch.randn_like(b)
+    for _ in range(3):
+      _ops.axpby(1.0, xs, 0.5, ys)
+    s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(
+        enable_timing=True)
+    s0.record()
+    for _ in range(20):
+      _ops.axpby(1.0, xs, 0.5, ys)
+    s1.record()
+    torch.cuda.synchronize()
+    stream_gbs = (3 * xs.numel() * sizeof /
+                  (s0.elapsed_time(s1) / 20 * 1e-3) / 1e9)
+    del xs, ys
+    traffic, traffic_sha = measured_traffic(args.n, args.p, args.dtype,
+                                            args.geometry, args.jitter)
+    # the same GLOBAL mesh on one GPU (committed measurement), so that an N > 1
+    # line reads directly as north_star's strong-scaling speed-up
+    strong_ref = None
+    if world > 1 and not periodic_dims and not args.jitter:
+      gdim = (args.n if args.scaling == 'strong'
+              else (args.n * grid_b[0] if len(set(grid_b)) == 1 else None))
+      ref = STRONG_REF.get((gdim, args.p, args.dtype))
+      if ref is not None:
+        strong_ref = {'global_elements': gdim ** 3, 'n_gpus': 1,
+                      'ms_per_step': ref[0], 'source': ref[1],
+                      'speedup_vs_strong_ref': ref[0] / ms_per_step}
+
   ngeo = 7 if args.mass_coeff else 6
   model_bytes = algorithmic_bytes_per_apply(E, n, N_local, sizeof=sizeof,
                                             ngeo=ngeo)
   kernel_bytes = op.bytes_per_apply(args.mass_coeff,
                                     layered=layered is not None)
   layer_reads = 0 if layered is None else sizeof * layered.read
-  achieved = kernel_bytes / (kern_ms * 1e-3) / 1e9
-  traffic, traffic_sha = measured_traffic(args.n, args.p, args.dtype,
-                                          args.geometry, args.jitter)
   passes = run.vector_passes if hasattr(run, 'vector_passes') else 8
-  # the same GLOBAL mesh on one GPU (committed measurement), so that an N > 1
-  # line reads directly as north_star's strong-scaling speed-up
-  strong_ref = None
-  if world > 1 and not periodic_dims and not args.jitter:
-    gdim = (args.n if args.scaling == 'strong'
-            else (args.n * grid_b[0] if len(set(grid_b)) == 1 else None))
-    ref = STRONG_REF.get((gdim, args.p, args.dtype))
-    if ref is not None:
-      strong_ref = {'global_elements': gdim ** 3, 'n_gpus': 1,
-                    'ms_per_step': ref[0], 'source': ref[1],
-                    'speedup_vs_strong_ref': ref[0] / ms_per_step}
 
   verify = None
   if args.verify:
@@ -665,10 +682,7 @@ def rank_main(args, world, rank, device):
             if world > 1 else None,
             'world_size_seen': comm.get_world_size() if world > 1 else 1,
             'verify': verify,
-            'per_rank': per_rank,
-            'strong_ref': strong_ref,
-            'apply_only_gdofs': N_local * world / (apply_ms * 1e-3) / 1e9,
-            'apply_ms': apply_ms, 'setup_s': setup_s,
+            'setup_s': setup_s,
             'repeat_ms_per_step': repeat_ms,
             'median_ms_per_step': float(np.median([ms_per_step] + repeat_ms)),
             'assembly': (
@@ -696,44 +710,6 @@ def rank_main(args, world, rank, device):
                                         op.num_multilinear, op.num_curved)),
             'mesh_jitter': args.jitter,
         },
-        'roofline': {
-            'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS,
-            'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
-            'traffic': traffic,
-            'traffic_profiled_at': traffic_sha,
-            'traffic_source': 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes '
-                              'of this command (%s; FETCH_SIZE doubled as '
-                              'MI355X_MICROARCH.md prescribes); null when the '
-                              'workload was not profiled or the kernel sources '
-                              '(sha256 in traffic_profiled_at) have changed '
-                              'since' % TRAFFIC_FILE,
-            'kernel': op.kernel_name(args.mass_coeff, 1.0,
-                                     layered=layered is not None),
-            'kernel_ms': kern_ms,
-            'kernel_ms_covers': 'one apply as the solver issues it: the fused '
-                                'kernel plus the clearing of the atomically '
-                                'accumulated node range it needs, if any '
-                                '(layered assembly: none)',
-            'bytes_per_launch': kernel_bytes,
-            'bytes_model': ('layered assembly: out is s x (N + values stored '
-                            'to further layers) instead of s N; ' if layered
-                            is not None else '') +
-                           'u s N + out s N + connectivity (432 B per element '
-                           'from a facet table, + 4 B on a chain list; 4 n + '
-                           '2 S per element on index rows) + geometry (64 B '
-                           'per affine / box element, 24 reals per multilinear '
-                           'one, %d reals per point where factors are stored): '
-                           'HelmholtzOperator.bytes_per_apply' % ngeo,
-            'measured_stream_peak': stream_gbs,
-            'frac_of_measured_stream': achieved / stream_gbs,
-            # NOT an HBM fraction: the SURVEY 8(d) stored-6-factor model
-            # charges 6 factors per point to every element; on affine /
-            # multilinear elements this kernel never reads them, so the ratio
-            # may exceed 1.  It compares GDOF/s with the model's 85.9 GDOF/s.
-            'model_gdofs_ratio': model_bytes / (kern_ms * 1e-3) / 1e9 /
-                                 HBM_PEAK_GBS,
-            'model_bytes_per_launch': model_bytes,
-        },
     }
     cg_bytes = kernel_bytes + passes * sizeof * N_local + layer_reads
     res['roofline_cg_iteration'] = {
@@ -744,25 +720,71 @@ def rank_main(args, world, rank, device):
         'vector_passes': passes,
         'model_gdofs_ratio': (model_bytes + 11 * sizeof * N_local) /
                              (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-        'note': 'bytes this build moves per iteration: the apply above + %d '
+        'note': 'bytes this build moves per iteration: one apply + %d '
                 'N-vector passes (p.Ap and r.r fused into kernels that stream '
                 'the vectors anyway); model_gdofs_ratio is against SURVEY '
                 "8(d)'s stored-factor apply + 11 passes" % passes}
-    if general is not None:
-      res['roofline_stored_factors'] = {
-          'bound': 'hbm', 'achieved': stored_bytes / (general * 1e-3) / 1e9,
-          'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-          'frac': stored_bytes / (general * 1e-3) / 1e9 / HBM_PEAK_GBS,
-          'kernel_ms': general, 'bytes_per_launch': stored_bytes,
-          'kernel': stored_kernel,
-          'note': 'the same mesh with geometry=stored: every element reads '
-                  'its %d factors per point, as curved elements do (the '
-                  'SURVEY 8(d) byte model, with the connectivity this build '
-                  'reads instead of 4 E n)' % ngeo}
-    if world == 1 and not args.no_cpu_baseline:
-      res['cpu_baseline'] = cpu_baseline(P, ne=min(32, args.n) if args.p <= 7 else min(12, args.n))
-    else:
-      res['cpu_baseline'] = None
+    if args.full:
+      achieved = kernel_bytes / (kern_ms * 1e-3) / 1e9
+      res['config'].update({
+          'per_rank': per_rank,
+          'strong_ref': strong_ref,
+          'apply_only_gdofs': N_local * world / (apply_ms * 1e-3) / 1e9,
+          'apply_ms': apply_ms})
+      res['roofline'] = {
+          'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS,
+          'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
+          'traffic': traffic,
+          'traffic_profiled_at': traffic_sha,
+          'traffic_source': 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes '
+                            'of this command (%s; FETCH_SIZE doubled: gfx950 '
+                            'tallies a 128-B request as 64 B); null when the '
+                            'workload was not profiled or the kernel sources '
+                            '(sha256 in traffic_profiled_at) have changed '
+                            'since' % TRAFFIC_FILE,
+          'kernel': op.kernel_name(args.mass_coeff, 1.0,
+                                   layered=layered is not None),
+          'kernel_ms': kern_ms,
+          'kernel_ms_covers': 'one apply as the solver issues it: the fused '
+                              'kernel plus the clearing of the atomically '
+                              'accumulated node range it needs, if any '
+                              '(layered assembly: none)',
+          'bytes_per_launch': kernel_bytes,
+          'bytes_model': ('layered assembly: out is s x (N + values stored '
+                          'to further layers) instead of s N; ' if layered
+                          is not None else '') +
+                         'u s N + out s N + connectivity (432 B per element '
+                         'from a facet table, + 4 B on a chain list; 4 n + '
+                         '2 S per element on index rows) + geometry (64 B '
+                         'per affine / box element, 24 reals per multilinear '
+                         'one, %d reals per point where factors are stored): '
+                         'HelmholtzOperator.bytes_per_apply' % ngeo,
+          'measured_stream_peak': stream_gbs,
+          'frac_of_measured_stream': achieved / stream_gbs,
+          # NOT an HBM fraction: the SURVEY 8(d) stored-6-factor model
+          # charges 6 factors per point to every element; on affine /
+          # multilinear elements this kernel never reads them, so the ratio
+          # may exceed 1.  It compares GDOF/s with the model's 85.9 GDOF/s.
+          'model_gdofs_ratio': model_bytes / (kern_ms * 1e-3) / 1e9 /
+                               HBM_PEAK_GBS,
+          'model_bytes_per_launch': model_bytes,
+      }
+      if general is not None:
+        res['roofline_stored_factors'] = {
+            'bound': 'hbm', 'achieved': stored_bytes / (general * 1e-3) / 1e9,
+            'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+            'frac': stored_bytes / (general * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            'kernel_ms': general, 'bytes_per_launch': stored_bytes,
+            'kernel': stored_kernel,
+            'note': 'the same mesh with geometry=stored: every element reads '
+                    'its %d factors per point, as curved elements do (the '
+                    'SURVEY 8(d) byte model, with the connectivity this build '
+                    'reads instead of 4 E n)' % ngeo}
+      if world == 1 and not args.no_cpu_baseline:
+        res['cpu_baseline'] = cpu_baseline(
+            P, ne=min(32, args.n) if args.p <= 7 else min(12, args.n))
+      else:
+        res['cpu_baseline'] = None
     print(json.dumps(res), flush=True)
 
 

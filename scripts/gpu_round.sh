@@ -8,8 +8,8 @@ mkdir -p $O
 cd $R
 python -m pytest tests -m gpu -x -q -p no:cacheprovider > $O/pytest_gpu_$TAG.log 2>&1; echo "pytest rc=$?"; tail -3 $O/pytest_gpu_$TAG.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep smoke
-python bench.py --steps 50 --warmup 10 > $O/bench_$TAG.json 2> $O/bench_$TAG.err; echo "bench rc=$?"; cat $O/bench_$TAG.json
-python bench.py --steps 50 --warmup 10 --geometry stored --no-cpu-baseline > $O/bench_${TAG}_stored.json 2>> $O/bench_$TAG.err; echo "bench stored rc=$?"; cat $O/bench_${TAG}_stored.json
+python bench.py --full --steps 50 --warmup 10 > $O/bench_$TAG.json 2> $O/bench_$TAG.err; echo "bench rc=$?"; cat $O/bench_$TAG.json
+python bench.py --full --steps 50 --warmup 10 --geometry stored --no-cpu-baseline > $O/bench_${TAG}_stored.json 2>> $O/bench_$TAG.err; echo "bench stored rc=$?"; cat $O/bench_${TAG}_stored.json
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$TAG -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/prof_$TAG.log 2>&1; echo "rocprof rc=$?"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${TAG}_stored -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --geometry stored > $O/prof_${TAG}_stored.log 2>&1; echo "rocprof stored rc=$?"

@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 P11="--p 11 --n 64 --dtype f32 --mass-coeff 0.5"
 run() { # name, bench flags
   name=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${TAG}_$name -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-general "$@" > $O/prof_${TAG}_$name.log 2>&1; echo "stats $name rc=$?"
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${TAG}_$name -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-general "$@" > $O/prof_${TAG}_$name.log 2>&1; echo "stats $name rc=$?"
   for c in FETCH_SIZE WRITE_SIZE "TCC_EA0_ATOMIC_sum TCC_EA0_WRREQ_sum TCC_HIT_sum TCC_MISS_sum"; do
     key=$(echo $c | cut -d' ' -f1)
     rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_${TAG}_${name}_$key -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-general "$@" > /dev/null 2>&1; echo "pmc $name $key rc=$?"

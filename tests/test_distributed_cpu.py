@@ -387,8 +387,8 @@ def test_bench_two_ranks_on_the_gpu_as_a_plain_command():
   """The real thing on the GPU box: two ranks sharing the visible GPU (gloo
   transport, because RCCL refuses two ranks per device), kernels running."""
   res, line = _run_bench('--gpus', '2', '--backend', 'gloo', '--elems', '8',
-                         '--steps', '3', '--warmup', '1', '--no-cpu-baseline',
-                         '--no-general')
+                         '--steps', '3', '--warmup', '1', '--full',
+                         '--no-cpu-baseline', '--no-general')
   assert res.returncode == 0, res.stderr[-2000:]
   assert line['n_gpus'] == 2 and line['value'] > 0
   assert line['config']['world_size_seen'] == 2
@@ -424,6 +424,39 @@ def test_bench_dumps_what_the_timed_solver_computed(tmp_path):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_dumps_what_a_full_run_dumps(tmp_path):
+  """A plain run (no `--full`) times the same steps as a `--full` run and,
+  with `--dump-outputs`, runs the `--repeats` batches too, so that it writes
+  the same x and r.r; its line carries the headline without the figures that
+  `--full` measures in runs of their own."""
+  lines, dumps = {}, {}
+  for mode, flags in (('plain', ()), ('full', ('--full', '--no-cpu-baseline'))):
+    out = tmp_path / mode
+    res, line = _run_bench('--elems', '4', '--steps', '7', '--warmup', '2',
+                           '--repeats', '2', *flags, '--dump-outputs',
+                           str(out), SFEM_LAZY_X_MIN_MB='0')
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines[mode] = line
+    dumps[mode] = (np.load(out / 'x.npy'), np.load(out / 'residual.npy'))
+  plain, full = lines['plain'], lines['full']
+  for key in ('metric', 'unit', 'higher_is_better', 'dtype', 'steps',
+              'warmup'):
+    assert plain[key] == full[key], key
+  assert plain['value'] > 0 and plain['ms_per_step'] > 0
+  assert len(plain['config']['repeat_ms_per_step']) == 2
+  assert len(full['config']['repeat_ms_per_step']) == 2
+  for key in ('roofline', 'roofline_stored_factors', 'cpu_baseline'):
+    assert key not in plain, key
+    assert key in full, key
+  assert 'apply_ms' not in plain['config'] and full['config']['apply_ms'] > 0
+  assert full['roofline']['kernel_ms'] > 0 and full['cpu_baseline'] is None
+  (xp, rp), (xf, rf) = dumps['plain'], dumps['full']
+  assert xp.shape == xf.shape == ((4 * 7 + 1) ** 3,)
+  np.testing.assert_allclose(xp, xf, rtol=0, atol=1e-12 * np.abs(xf).max())
+  np.testing.assert_allclose(rp, rf, rtol=1e-10)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize('flags,blocks', [
     (('--elems', '16'), '2x2x2'),
     (('--elems', '16', '--periodic'), '2x2x2'),
@@ -440,9 +473,9 @@ def test_bench_eight_ranks_with_real_kernels_on_one_gpu(flags, blocks):
   # (SFEM_LAZY_X_MIN_MB=0: the lazy x update that the 64^3 blocks of the
   # real run take, on these small ones)
   res, line = _run_bench('--gpus', '8', '--backend', 'threads', *flags,
-                         '--steps', '3', '--warmup', '1', '--no-cpu-baseline',
-                         '--no-general', '--verify', timeout=900,
-                         SFEM_LAZY_X_MIN_MB='0')
+                         '--steps', '3', '--warmup', '1', '--full',
+                         '--no-cpu-baseline', '--no-general', '--verify',
+                         timeout=900, SFEM_LAZY_X_MIN_MB='0')
   assert line['config']['switches'] == {'SFEM_LAZY_X_MIN_MB': '0'}
   assert res.returncode == 0, res.stderr[-3000:]
   assert sum(l.startswith('{') for l in res.stdout.splitlines()) == 1
@@ -474,8 +507,9 @@ def test_bench_four_gloo_ranks_verify_on_the_gpu():
   launch path of the driver's scaling run, with the manufactured-solution
   check on the result."""
   res, line = _run_bench('--gpus', '4', '--backend', 'gloo', '--elems', '8',
-                         '--steps', '3', '--warmup', '1', '--no-cpu-baseline',
-                         '--no-general', '--verify', timeout=900)
+                         '--steps', '3', '--warmup', '1', '--full',
+                         '--no-cpu-baseline', '--no-general', '--verify',
+                         timeout=900)
   assert res.returncode == 0, res.stderr[-3000:]
   cfg = line['config']
   assert line['n_gpus'] == 4 and cfg['world_size_seen'] == 4
