@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SFEM_ABI_VERSION 7
+#define SFEM_ABI_VERSION 8
 
 enum { SFEM_F32 = 0, SFEM_F64 = 1 };
 enum {
@@ -194,6 +194,10 @@ int sfem_basis_eval_t(const void* c0, const void* c1, const void* interp1,
  *                         constant times the tensor quadrature weight.
  * `elem_list` (device int32, num_listed entries) restricts a launch to some
  * elements, so a mesh mixing the kinds is applied by one call per kind.       */
+/* Variable-coefficient modes (kappa / sigma / coef_mode of
+ * sfem_helmholtz_args and sfem_diag_args): off, one value per element, one
+ * value per quadrature point.                                               */
+enum { SFEM_COEF_NONE = 0, SFEM_COEF_ELEM = 1, SFEM_COEF_POINT = 2 };
 enum { SFEM_GEO_POINT = 0, SFEM_GEO_AFFINE = 1, SFEM_GEO_MULTILINEAR = 3,
        SFEM_GEO_BOX = 5 /* affine with diagonal J^-1 J^-T (Cartesian boxes):  */
                         /* facet-table applies only.  Helmholtz: needs        */
@@ -320,6 +324,19 @@ typedef struct sfem_helmholtz_args {
   /* the sum over the slots in index order (sfem_cg_scalars_n) is bitwise       */
   /* reproducible                                                               */
   int64_t dot_slots;
+  /* Variable coefficients (NULL / 0 = off): the operator becomes             */
+  /*   lambda0 B_c + lambda1 A_k,  B_c[i,j] = sum_q c_q W_q phi_i phi_j,      */
+  /*   A_k[i,j] = sum_q k_q grad phi_i . G_q grad phi_j.                      */
+  /* coef_mode SFEM_COEF_ELEM: kappa / sigma hold one value per element (E,); */
+  /* SFEM_COEF_POINT: (E, n) values at the element's points in slot order     */
+  /* (lexicographic, axis 0 slowest).  Indexed by element id, in the dtype of */
+  /* the field; a NULL array stands for 1, but not both.  Scalar fields       */
+  /* (ncomp = 1) on index rows only (no cluster, facet, layered or sorted     */
+  /* assembly), SFEM_GEO_AFFINE / _MULTILINEAR elements: curved elements take */
+  /* the coefficients folded into their stored factors (k G, c W).            */
+  const void* kappa;      /* diffusivity k (> 0)                              */
+  const void* sigma;      /* reaction coefficient c (>= 0)                    */
+  int32_t coef_mode;      /* SFEM_COEF_*                                      */
 } sfem_helmholtz_args;
 
 /* Compact connectivity of refiner-numbered meshes (reference numbering:
@@ -798,6 +815,12 @@ typedef struct sfem_diag_args {
   int Q;                    /* P..16 (ignored when collocated)                */
   int dtype;
   int geo_mode;             /* SFEM_GEO_POINT / _AFFINE / _MULTILINEAR        */
+  /* Variable coefficients as in sfem_helmholtz_args (NULL / 0 = off): G of   */
+  /* point q of element e is scaled by kappa, W by sigma; SFEM_COEF_POINT     */
+  /* arrays are (E, Q^d) at the quadrature points (P^d when collocated).      */
+  const void* kappa;
+  const void* sigma;
+  int coef_mode;
 } sfem_diag_args;
 int sfem_helmholtz_diag(const sfem_diag_args* args, sfem_stream_t stream);
 /* CG with M r = dinv (.) r folded into the two vector updates (z = M r is

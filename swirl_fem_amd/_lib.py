@@ -15,7 +15,7 @@ from swirl_fem_amd import switches
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SFEM_LIB: another build of the same library (kernel A/B experiments)
 LIB_PATH = switches.get('SFEM_LIB') or os.path.join(_HERE, 'libsfem_hip.so')
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 SFEM_F32, SFEM_F64 = 0, 1
 SFEM_CG_NSCALARS_NAMED = 16
@@ -54,6 +54,12 @@ class HelmholtzArgs(ctypes.Structure):
       ('facet_table', c_ptr), ('geo_const', c_ptr),
       ('chain_offsets', c_ptr), ('chain_elems', c_ptr), ('num_chains', c_i64),
       ('layered_extent', c_i64), ('dot_slots', c_i64),
+      # variable coefficients (None / 0 = off): kappa (diffusivity k) and
+      # sigma (reaction c), device arrays indexed by element id -- (E,) for
+      # coef_mode COEF_ELEM, (E, n) in slot order for COEF_POINT; None
+      # stands for 1.  Scalar fields, index rows, affine / multilinear
+      # launches only.
+      ('kappa', c_ptr), ('sigma', c_ptr), ('coef_mode', c_i32),
   ]
 
 
@@ -83,10 +89,14 @@ class DiagArgs(ctypes.Structure):
       ('bmat', c_ptr), ('dtil', c_ptr), ('weights', c_ptr), ('nodes', c_ptr),
       ('num_elements', c_i64), ('num_listed', c_i64), ('ndim', c_i32),
       ('P', c_i32), ('Q', c_i32), ('dtype', c_i32), ('geo_mode', c_i32),
+      # as in HelmholtzArgs; COEF_POINT arrays are (E, Q^d) at the quadrature
+      # points (P^d when collocated)
+      ('kappa', c_ptr), ('sigma', c_ptr), ('coef_mode', c_i32),
   ]
 
 
 GEO_POINT, GEO_AFFINE, GEO_MULTILINEAR, GEO_BOX = 0, 1, 3, 5
+COEF_NONE, COEF_ELEM, COEF_POINT = 0, 1, 2
 
 # name -> argument types (all functions return int unless noted)
 SIGNATURES = {

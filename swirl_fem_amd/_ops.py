@@ -523,7 +523,9 @@ def _helmholtz_args(u, out, enc, part, host, ndim, P, num_elements, num_nodes,
       chain_offsets=_dptr(ch[0] if ch is not None else None),
       chain_elems=_dptr(ch[1] if ch is not None else None),
       num_chains=0 if ch is None else ch[0].numel() - 1,
-      layered_extent=int(layered_extent), dot_slots=int(dot_slots))
+      layered_extent=int(layered_extent), dot_slots=int(dot_slots),
+      kappa=_dptr(part.get('kappa')), sigma=_dptr(part.get('sigma')),
+      coef_mode=int(part.get('coef_mode', _lib.COEF_NONE)))
 
 
 _CLUSTER_LIMITS = {}
@@ -571,6 +573,9 @@ def helmholtz_kernel_name(real, P, ndim, scalar, geo_mode, part, mass,
   if part.get('cluster') is not None:
     return 'sfem::helmholtz_cluster_kernel<%s, %d, %s, %d, %s>' % (
         real, P, b(scalar), geo_mode, b(mass))
+  if part.get('coef_mode'):
+    return ('sfem::helmholtz_kernel<%s, %d, %d, true, true, %d, false, %s, '
+            '%d>' % (real, P, ndim, geo_mode, b(mass), part['coef_mode']))
   tpe = P * P if ndim == 3 else P
   can_sort = ndim == 3 and tpe <= 64
   sort = (can_sort and part.get('shared_order') is not None and
@@ -1276,7 +1281,9 @@ def helmholtz_diag(parts, num_elements, ndim, P, dtil, weights, nodes,
           elem_list=_ptr(lst), bmat=_ptr(b_d), dtil=_ptr(dt_d),
           weights=_ptr(w_d), nodes=_ptr(x_d), num_elements=num_elements,
           num_listed=0 if lst is None else lst.numel(), ndim=ndim, P=P, Q=Q,
-          dtype=_DT[dtype], geo_mode=part['geo_mode'])
+          dtype=_DT[dtype], geo_mode=part['geo_mode'],
+          kappa=_ptr(part.get('kappa')), sigma=_ptr(part.get('sigma')),
+          coef_mode=int(part.get('coef_mode', _lib.COEF_NONE)))
       _lib.check(_lib.load().sfem_helmholtz_diag(ctypes.byref(args),
                                                  _stream(dev)),
                  'sfem_helmholtz_diag')

@@ -495,7 +495,7 @@ class FiniteElementSpace:
 
   # -------------------------------------------------------- fused operators
   def helmholtz_operator(self, dirichlet_mask=None, geometry='auto',
-                         assembly='auto'):
+                         assembly='auto', *, diffusivity=None, reaction=None):
     """Fused `out = mask * scatter((l0 B + l1 A)_local(gather(u)))`.
 
     `geometry`: 'auto' evaluates the geometric factors of affine / multilinear
@@ -503,8 +503,24 @@ class FiniteElementSpace:
     elements; 'stored' stores them for every element (same results to
     rounding).  `assembly`: how shared nodes are summed, see
     `operators.HelmholtzOperator.create`.
+
+    `diffusivity` k, `reaction` c: the operator becomes l0 B_c + l1 A_k with
+    B_c[i,j] = sum_q c_q W_q phi_i phi_j, A_k[i,j] = sum_q k_q grad phi_i .
+    G_q grad phi_j.  Each is a scalar, an (E,) tensor, an (E, Q^d) tensor at
+    the quadrature points (`quad_coords` order) or a callable (M, d) ->
+    (M,) evaluated there once (`operators.coefficient`); None means 1.  Such
+    operators are not cached.
     """
     from swirl_fem_amd.core import operators
+    if diffusivity is not None or reaction is not None:
+      if (not self.is_collocated and assembly in ('auto', 'atomic') and
+          operators.supports_two_grid(self) is None):
+        return operators.TwoGridHelmholtzOperator.create(
+            self, dirichlet_mask, 'stored' if geometry == 'stored' else 'auto',
+            diffusivity=diffusivity, reaction=reaction)
+      return operators.HelmholtzOperator.create(
+          self, dirichlet_mask, geometry, assembly, diffusivity=diffusivity,
+          reaction=reaction)
     # cached per (mask object, options); the entry keeps the mask alive so that
     # its id cannot be recycled by another tensor
     key = ('helmholtz', None if dirichlet_mask is None else id(dirichlet_mask),

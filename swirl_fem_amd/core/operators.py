@@ -450,6 +450,165 @@ def first_toucher_violations(elements, first, launches):
   return int((slot_launch[later] <= first_launch[el[later]]).sum())
 
 
+def coefficient(value, name, num_elements, npts, points, dtype, device):
+  """A diffusivity (`name` 'diffusivity': finite, > 0) or reaction coefficient
+  ('reaction': finite, >= 0) in normal form: None, a float, or
+  (mode, tensor) with mode `_lib.COEF_ELEM` and an (E,) tensor or
+  `_lib.COEF_POINT` and an (E, npts) tensor at the operator's points
+  (lexicographic, axis 0 slowest).  `value` is one of those, or a callable
+  that maps (M, d) coordinates to (M,) values: it is evaluated once at
+  `points()` (E, npts, d).  Anything else raises ValueError."""
+  from swirl_fem_amd import _lib
+  if value is None:
+    return None
+  positive = name == 'diffusivity'
+  what = '> 0' if positive else '>= 0'
+
+  def check(t):
+    if not bool(torch.isfinite(t).all()):
+      raise ValueError(f'{name}: values must be finite')
+    if bool((t <= 0).any() if positive else (t < 0).any()):
+      raise ValueError(f'{name}: values must be {what}')
+
+  if callable(value) and not isinstance(value, torch.Tensor):
+    x = points()
+    vals = value(x.reshape(-1, x.shape[-1]))
+    t = torch.as_tensor(vals, dtype=dtype, device=device)
+    if tuple(t.shape) != (num_elements * npts,):
+      raise ValueError(f'{name}: the callable returned shape '
+                       f'{tuple(t.shape)}, expected ({num_elements * npts},)')
+    t = t.reshape(num_elements, npts).contiguous()
+    check(t)
+    return (_lib.COEF_POINT, t)
+  if isinstance(value, (int, float, np.floating, np.integer)) and not \
+      isinstance(value, bool):
+    v = float(value)
+    check(torch.tensor(v, dtype=torch.float64))
+    return v
+  try:
+    t = torch.as_tensor(value)
+  except (TypeError, ValueError, RuntimeError):
+    t = torch.zeros((), dtype=torch.bool)
+  numeric = t.is_floating_point() or t.dtype in (torch.int32, torch.int64)
+  if t.dim() == 0 and numeric:
+    return coefficient(float(t), name, num_elements, npts, points, dtype,
+                       device)
+  if t.dim() == 0 or not (t.is_floating_point() or t.dtype in (
+      torch.int32, torch.int64)):
+    raise ValueError(f'{name}: expected a scalar, an (E,) or (E, Q^d) '
+                     'tensor or a callable')
+  t = t.to(dtype=dtype, device=device)
+  if tuple(t.shape) == (num_elements,):
+    mode = _lib.COEF_ELEM
+  elif tuple(t.shape) == (num_elements, npts):
+    mode = _lib.COEF_POINT
+  else:
+    raise ValueError(f'{name}: shape {tuple(t.shape)}; expected '
+                     f'({num_elements},) or ({num_elements}, {npts})')
+  t = t.contiguous()
+  check(t)
+  return (mode, t)
+
+
+def _fold_point_factors(geo, ndim, kp, cp):
+  """Stored factors (S, ng + 1, Q) with G scaled by kp and W by cp ((S, Q)
+  each, or None): pairs (G00, G01) (G02, G11) (G12, G22), W in 3D; (G00, G01)
+  (G11, W) in 2D (`sfem_helmholtz_setup`)."""
+  S, Q = geo.shape[0], geo.shape[2]
+  flat = geo.reshape(S, -1).clone()
+  if ndim == 3:
+    g = flat[:, :6 * Q].view(S, 3, Q, 2)
+    w = flat[:, 6 * Q:]
+    if kp is not None:
+      g.mul_(kp[:, None, :, None])
+  else:
+    pairs = flat.view(S, 2, Q, 2)
+    w = pairs[:, 1, :, 1]
+    if kp is not None:
+      pairs[:, 0].mul_(kp[:, :, None])
+      pairs[:, 1, :, 0].mul_(kp)
+  if cp is not None:
+    w.mul_(cp)
+  return flat.view(geo.shape).contiguous()
+
+
+def _coefficient_parts(parts, kappa, sigma, num_elements, npts, ndim):
+  """`parts` with the array coefficients attached: affine / multilinear
+  launches carry `kappa` / `sigma` / `coef_mode` (one mode for both: an (E,)
+  array next to a per-point one is expanded), curved launches get them folded
+  into a copy of their stored factors.  Scalars stay out (see `apply`)."""
+  from swirl_fem_amd import _lib
+  arrays = [c for c in (kappa, sigma) if isinstance(c, tuple)]
+  if not arrays:
+    return parts
+  mode = (_lib.COEF_POINT if any(c[0] == _lib.COEF_POINT for c in arrays)
+          else _lib.COEF_ELEM)
+
+  def full(c, m):
+    if not isinstance(c, tuple):
+      return None
+    if m == _lib.COEF_POINT and c[0] == _lib.COEF_ELEM:
+      return c[1][:, None].expand(num_elements, npts).contiguous()
+    return c[1]
+
+  K, C = full(kappa, mode), full(sigma, mode)
+  out = []
+  for part in parts:
+    if part['geo_mode'] == _GEO_POINT:
+      Kp, Cp = full(kappa, _lib.COEF_POINT), full(sigma, _lib.COEF_POINT)
+      if 'elem_list' in part:      # slots in ascending element order
+        lst = part['elem_list'].to(torch.int64)
+        Kp = None if Kp is None else Kp[lst]
+        Cp = None if Cp is None else Cp[lst]
+      part = dict(part, geo=_fold_point_factors(part['geo'], ndim, Kp, Cp))
+    else:
+      part = dict(part, kappa=K, sigma=C, coef_mode=mode)
+    out.append(part)
+  return out
+
+
+def _coefficient_bytes(part, s, npts, lambda0):
+  """Bytes a coefficient launch reads per element beyond the constant
+  operator: `s` per (E,) coefficient, `s npts` per per-point one (sigma only
+  with a mass term)."""
+  mode = part.get('coef_mode')
+  if not mode:
+    return 0
+  from swirl_fem_amd import _lib
+  per = s if mode == _lib.COEF_ELEM else s * npts
+  arrays = [part.get('kappa')] + ([part.get('sigma')] if lambda0 else [])
+  return per * sum(a is not None for a in arrays)
+
+
+def _scaled(coefs, lambda0, lambda1):
+  """lambda0, lambda1 times the scalar reaction / diffusivity, if any."""
+  if coefs is None:
+    return lambda0, lambda1
+  k, c = coefs
+  return (lambda0 * c if isinstance(c, float) else lambda0,
+          lambda1 * k if isinstance(k, float) else lambda1)
+
+
+def _check_coefficient_mesh(mesh, assembly):
+  """The refusals of operators with coefficients."""
+  if assembly == 'cluster':
+    raise NotImplementedError('coefficients run on index rows: no cluster '
+                              'assembly')
+  if mesh.axis_name is not None or mesh.neighbor_plan is not None:
+    raise NotImplementedError('coefficients on a partitioned mesh')
+
+
+def _check_scalar_field(u):
+  if u.dim() > 1 and u.shape[-1] != 1:
+    raise NotImplementedError('coefficients take scalar fields')
+
+
+def _point_coefficient(c):
+  """True if a normal-form coefficient holds per-point values."""
+  from swirl_fem_amd import _lib
+  return isinstance(c, tuple) and c[0] == _lib.COEF_POINT
+
+
 @dataclasses.dataclass(eq=False)
 class HelmholtzOperator:
   fespace: object
@@ -467,10 +626,16 @@ class HelmholtzOperator:
   _layer_plan: object = None          # LayerPlan, False = none (`layer_plan`)
   keep: torch.Tensor | None = None    # (N,) 1 inside, 0 on Dirichlet nodes
   _diag: tuple | None = None          # assembled (diag B, diag A), `diagonal`
+  # variable coefficients: (k, c) in the normal form of `coefficient`, or
+  # None; `coef_source` the (diffusivity, reaction) the caller passed
+  coefs: tuple | None = None
+  coef_source: tuple = (None, None)
+  _geo_parts: list | None = None      # the launches without coefficients
 
   @classmethod
   def create(cls, fespace, dirichlet_mask=None, geometry='auto',
-             assembly='auto') -> 'HelmholtzOperator':
+             assembly='auto', *, diffusivity=None,
+             reaction=None) -> 'HelmholtzOperator':
     """geometry: 'auto' (per element: affine / multilinear / stored factors),
     'multilinear' (no affine shortcut) or 'stored' (6 factors per point for
     every element, the general-geometry path).
@@ -482,7 +647,12 @@ class HelmholtzOperator:
     `core/clusters.py`: half the atomic traffic, but 1.04 vs 0.78 ms at
     config 2 -- the waves of a cluster wait for each other); 'colored': one
     launch per conflict-free colour class, no atomics, bitwise reproducible;
-    'auto': 'atomic' (or 'cluster' with SFEM_CLUSTER=1 in the environment)."""
+    'auto': 'atomic' (or 'cluster' with SFEM_CLUSTER=1 in the environment).
+
+    diffusivity k, reaction c (`coefficient`): the operator becomes
+    lambda0 B_c + lambda1 A_k.  With either one it runs on index rows
+    ('atomic' or 'colored' assembly, no facet tables or layers); scalar
+    fields on one unpartitioned mesh only."""
     why = supports_fused(fespace)
     if why is not None:
       raise NotImplementedError(f'fused Helmholtz kernel unavailable: {why}')
@@ -490,6 +660,18 @@ class HelmholtzOperator:
       raise ValueError(f'unknown geometry mode {geometry!r}')
     if assembly not in ('auto', 'cluster', 'atomic', 'colored'):
       raise ValueError(f'unknown assembly mode {assembly!r}')
+    coefs = None
+    if diffusivity is not None or reaction is not None:
+      mesh = fespace.mesh
+      _check_coefficient_mesh(mesh, assembly)
+      npts = mesh.num_nodes_per_element
+      points = mesh.element_coords
+      coefs = (coefficient(diffusivity, 'diffusivity', mesh.num_elements, npts,
+                           points, fespace.dtype, fespace.device),
+               coefficient(reaction, 'reaction', mesh.num_elements, npts,
+                           points, fespace.dtype, fespace.device))
+      if assembly == 'auto':
+        assembly = 'atomic'
     requested = assembly
     if assembly == 'auto':
       assembly = ('cluster' if _cluster_limits(fespace) is not None and
@@ -532,6 +714,10 @@ class HelmholtzOperator:
       else:
         part['geo_elem'] = coef
       parts.append(part)
+    geo_parts = parts
+    if coefs is not None:
+      parts = _coefficient_parts(parts, *coefs, E, mesh.num_nodes_per_element,
+                                 mesh.ndim)
     plan = mesh.assembly_plan()
     mask = None
     if dirichlet_mask is not None:
@@ -572,7 +758,7 @@ class HelmholtzOperator:
       else:
         assembly = 'atomic'
 
-    if (assembly == 'atomic' and mesh.ndim == 3 and
+    if (assembly == 'atomic' and mesh.ndim == 3 and coefs is None and
         mesh.gridpoints_1d.num_points <= 8 and      # one wave per element
         switches.get('SFEM_SORTED_SCATTER') != '0'):
       # 3D: most slots of an element are shared; issue their atomics in node
@@ -581,7 +767,7 @@ class HelmholtzOperator:
       if so is not None:
         parts = [dict(part, shared_order=so) for part in parts]
     facet_parts = None
-    if (assembly == 'atomic' and mesh.ndim == 3 and
+    if (assembly == 'atomic' and mesh.ndim == 3 and coefs is None and
         mesh.gridpoints_1d.num_points in FACET_P and
         switches.get('SFEM_FACET') != '0'):
       facet_parts = _facet_parts(fespace, parts, mask, plan.multiplicity, coef)
@@ -592,7 +778,10 @@ class HelmholtzOperator:
                zero_range=zero_range, num_affine=counts[_GEO_AFFINE],
                num_multilinear=counts[_GEO_MULTILINEAR],
                num_curved=counts[_GEO_POINT], facet_parts=facet_parts,
-               keep=None if mask is None else (mask == 0).to(fespace.dtype))
+               keep=None if mask is None else (mask == 0).to(fespace.dtype),
+               coefs=coefs, coef_source=(diffusivity, reaction),
+               _geo_parts=geo_parts,
+               _layer_plan=False if coefs is not None else None)
 
   def split(self, element_mask):
     """Two operators over the elements inside / outside `element_mask` (E,)
@@ -601,6 +790,8 @@ class HelmholtzOperator:
     overlaps with the interior elements (`distributed/solver.py`)."""
     if any(p.get('colored') for p in self.parts):
       raise NotImplementedError('split() of a coloured operator')
+    if self.coefs is not None:
+      raise NotImplementedError('split() of an operator with coefficients')
     mask = torch.as_tensor(element_mask, device=self.enc.device).to(torch.bool)
     E = self.enc.shape[0]
     if mask.shape != (E,):
@@ -653,6 +844,9 @@ class HelmholtzOperator:
     if u.shape[0] != mesh.num_nodes:
       raise ValueError(f'expected {mesh.num_nodes} nodal values, got '
                        f'{tuple(u.shape)}')
+    if self.coefs is not None:
+      _check_scalar_field(u)
+      lambda0, lambda1 = _scaled(self.coefs, lambda0, lambda1)
     u = u.to(self.fespace.dtype)
     if not (u.is_contiguous() or _ops.is_component_major(u)):
       u = u.contiguous()
@@ -757,12 +951,28 @@ class HelmholtzOperator:
     if self._diag is None:
       self._diag = _assembled_diagonal(self.fespace, self.parts, self.host,
                                        self.keep, None)
+    lambda0, lambda1 = _scaled(self.coefs, lambda0, lambda1)
     return _combine_diagonal(self._diag, lambda0, lambda1, assembled,
                              self.fespace.mesh)
+
+  def point_weights(self):
+    """W = w detJ (E, n) at the operator's points, without coefficients (the
+    weights of the coarse-level mean in `linalg/pmg.py`)."""
+    mesh = self.fespace.mesh
+    P = mesh.gridpoints_1d.num_points
+    mass, _ = _ops.helmholtz_diag(
+        self._geo_parts or self.parts, mesh.num_elements, mesh.ndim, P,
+        self.host['dmat'], self.host['weights'], self.host['nodes'], None,
+        want_stiff=False, dtype=self.fespace.dtype, device=self.fespace.device)
+    return mass
 
   def apply_local(self, u_local, lambda0=0.0, lambda1=1.0):
     """Element-local action (E, n[, nc]) -> (E, n[, nc]); no gather/scatter."""
     mesh = self.fespace.mesh
+    if self.coefs is not None:
+      if u_local.dim() == 3 and u_local.shape[-1] != 1:
+        raise NotImplementedError('coefficients take scalar fields')
+      lambda0, lambda1 = _scaled(self.coefs, lambda0, lambda1)
     return _ops.helmholtz_local(
         u_local.to(self.fespace.dtype), self.parts, self.host, mesh.ndim,
         mesh.gridpoints_1d.num_points, lambda0, lambda1)
@@ -779,7 +989,10 @@ class HelmholtzOperator:
     table (+ 4 per element of a chain list), or `4 n` per element of index
     rows plus `2 S` of sorted shared slots -- and the geometry it reads: 64
     bytes (affine / box constants) or `24 s` (multilinear coefficients) per
-    element, `(6 or 7) s n` for elements with stored factors.  `layered`
+    element, `(6 or 7) s n` for elements with stored factors (which
+    carry their coefficients folded in).  Coefficients of the other
+    elements add `s` (per element) or `s n` (per point) per element each;
+    the reaction only with a mass term.  `layered`
     (`apply_layered`): the field in once, and every slot the launches store
     (`LayerPlan.written`: the nodal values plus the further layers of shared
     facets) instead of the field out once."""
@@ -807,6 +1020,7 @@ class HelmholtzOperator:
         geo = 8 * s
       else:
         geo = 24 * s
+      geo += _coefficient_bytes(part, s, n, lambda0)
       total += count * (conn + geo)
     return total
 
@@ -823,7 +1037,8 @@ class HelmholtzOperator:
     for part in parts:
       gm = part['geo_mode']
       names.append(_ops.helmholtz_kernel_name(
-          real, P, mesh.ndim, ncomp == 1, gm, part, lambda0 != 0, layered))
+          real, P, mesh.ndim, ncomp == 1, gm, part,
+          _scaled(self.coefs, lambda0, lambda1)[0] != 0, layered))
     return ' + '.join(sorted(set(names)))
 
 
@@ -1443,10 +1658,17 @@ class TwoGridHelmholtzOperator:
   host: dict
   mask: torch.Tensor | None        # (N,) 1 inside, 0 on Dirichlet nodes
   _diag: tuple | None = None       # assembled (diag B, diag A), `diagonal`
+  # variable coefficients at the Q^d quadrature points, as in
+  # `HelmholtzOperator`
+  coefs: tuple | None = None
+  coef_source: tuple = (None, None)
+  _geo_parts: list | None = None
 
   @classmethod
-  def create(cls, fespace, dirichlet_mask=None,
-             geometry='auto') -> 'TwoGridHelmholtzOperator':
+  def create(cls, fespace, dirichlet_mask=None, geometry='auto', *,
+             diffusivity=None, reaction=None) -> 'TwoGridHelmholtzOperator':
+    """`diffusivity`, `reaction`: see `HelmholtzOperator.create`; per-point
+    values and callables live on the Q^d quadrature points."""
     why = supports_two_grid(fespace)
     if why is not None:
       raise NotImplementedError(f'two-grid Helmholtz unavailable: {why}')
@@ -1454,6 +1676,19 @@ class TwoGridHelmholtzOperator:
       raise ValueError(f'unknown geometry mode {geometry!r}')
     mesh = fespace.mesh
     E, dev = mesh.num_elements, fespace.device
+    coefs = None
+    if diffusivity is not None or reaction is not None:
+      _check_coefficient_mesh(mesh, 'atomic')
+      nq = fespace.quadrature.num_points ** mesh.ndim
+      # the values-only interpolation of the element coordinates, not
+      # `quad_coords` (which builds the whole geometry)
+      points = lambda: (mesh.element_coords() if fespace.is_collocated else
+                        fespace._basis(mesh.element_coords(), True,
+                                       False)[0])
+      coefs = (coefficient(diffusivity, 'diffusivity', E, nq, points,
+                           fespace.dtype, dev),
+               coefficient(reaction, 'reaction', E, nq, points,
+                           fespace.dtype, dev))
     w = torch.as_tensor(fespace.quadrature.weights_nd(mesh.ndim),
                         dtype=fespace.dtype, device=dev)
     from swirl_fem_amd.core.interpolation import NodeType
@@ -1494,7 +1729,24 @@ class TwoGridHelmholtzOperator:
     host = {'dmat': _quadrature_dmat(fespace),
             'weights': np.asarray(fespace.quadrature.weights),
             'nodes': np.asarray(fespace.quadrature.nodes.node_values)}
-    return cls(fespace=fespace, parts=parts, host=host, mask=mask)
+    geo_parts = parts
+    if coefs is not None:
+      parts = _coefficient_parts(parts, *coefs, E,
+                                 fespace.quadrature.num_points ** mesh.ndim,
+                                 mesh.ndim)
+    return cls(fespace=fespace, parts=parts, host=host, mask=mask,
+               coefs=coefs, coef_source=(diffusivity, reaction),
+               _geo_parts=geo_parts)
+
+  def point_weights(self):
+    """W = w detJ (E, Q^d) at the quadrature points, without coefficients."""
+    mesh = self.fespace.mesh
+    q = self.fespace.quadrature.num_points
+    mass, _ = _ops.helmholtz_diag(
+        self._geo_parts or self.parts, mesh.num_elements, mesh.ndim, q,
+        self.host['dmat'], self.host['weights'], self.host['nodes'], None,
+        want_stiff=False, dtype=self.fespace.dtype, device=self.fespace.device)
+    return mass
 
   def apply_local(self, u_local, lambda0=0.0, lambda1=1.0):
     """(E, n[, nc]) -> (E, n[, nc])."""
@@ -1504,6 +1756,10 @@ class TwoGridHelmholtzOperator:
     scalar = u_local.dim() == 2
     u3 = (u_local[..., None] if scalar else u_local).to(fes.dtype)
     nc = u3.shape[-1]
+    if self.coefs is not None:
+      if nc != 1:
+        raise NotImplementedError('coefficients take scalar fields')
+      lambda0, lambda1 = _scaled(self.coefs, lambda0, lambda1)
     q = fes.quadrature.num_points
     uq = u3 if fes.is_collocated else fes._basis(u3, True, False)[0]
     rq = _ops.helmholtz_local(uq.contiguous(), self.parts, self.host,
@@ -1547,6 +1803,7 @@ class TwoGridHelmholtzOperator:
       bmat = np.asarray(interp._interpolation_matrix_1d(), dtype=np.float64)
       self._diag = _assembled_diagonal(self.fespace, self.parts, self.host,
                                        self.mask, bmat)
+    lambda0, lambda1 = _scaled(self.coefs, lambda0, lambda1)
     return _combine_diagonal(self._diag, lambda0, lambda1, assembled,
                              self.fespace.mesh)
 

@@ -43,13 +43,43 @@ struct DiagParams {
   const T* nodes;    // (Q,)
   int64_t num_listed;
   int P, Q, geo_mode;
+  const T* kappa;    // coefficients (coef_mode SFEM_COEF_*), or null = 1
+  const T* sigma;
+  int coef_mode;
 };
 
-// G (upper triangle in g[a][b], a <= b) and W at point (q0, q1, q2).
+template <typename T, int DIM>
+__device__ void geo_factors(const DiagParams<T>& prm, int64_t e,
+                            int64_t slot, int q0, int q1, int q2,
+                            bool want_g, T (&g)[3][3], T& W);
+
+// G (upper triangle in g[a][b], a <= b) and W at point (q0, q1, q2), G scaled
+// by the diffusivity k and W by the reaction coefficient c of the point.
 template <typename T, int DIM>
 __device__ void point_factors(const DiagParams<T>& prm, int64_t e,
                               int64_t slot, int q0, int q1, int q2,
                               bool want_g, T (&g)[3][3], T& W) {
+  geo_factors<T, DIM>(prm, e, slot, q0, q1, q2, want_g, g, W);
+  if (prm.coef_mode == SFEM_COEF_NONE) return;
+  int64_t at = e;
+  if (prm.coef_mode == SFEM_COEF_POINT) {
+    const int Q = prm.Q;
+    const int64_t NQ = DIM == 3 ? (int64_t)Q * Q * Q : (int64_t)Q * Q;
+    at = e * NQ + (DIM == 3 ? ((int64_t)q0 * Q + q1) * Q + q2
+                            : (int64_t)q0 * Q + q1);
+  }
+  if (prm.sigma) W *= prm.sigma[at];
+  if (want_g && prm.kappa) {
+    const T k = prm.kappa[at];
+    for (int a = 0; a < DIM; ++a)
+      for (int b = a; b < DIM; ++b) g[a][b] *= k;
+  }
+}
+
+template <typename T, int DIM>
+__device__ void geo_factors(const DiagParams<T>& prm, int64_t e,
+                            int64_t slot, int q0, int q1, int q2,
+                            bool want_g, T (&g)[3][3], T& W) {
   const int Q = prm.Q;
   if (prm.geo_mode == GEO_POINT) {
     const int64_t NQ = DIM == 3 ? (int64_t)Q * Q * Q : (int64_t)Q * Q;
@@ -211,6 +241,9 @@ int launch_diag(const sfem_diag_args* a, hipStream_t stream) {
   prm.P = a->P;
   prm.Q = a->bmat ? a->Q : a->P;
   prm.geo_mode = a->geo_mode;
+  prm.kappa = (const T*)a->kappa;
+  prm.sigma = (const T*)a->sigma;
+  prm.coef_mode = a->coef_mode;
   const int n = a->ndim == 3 ? a->P * a->P * a->P : a->P * a->P;
   const unsigned grid = stream_grid(prm.num_listed * n, 256);
   if (a->ndim == 3)
@@ -250,6 +283,13 @@ int sfem_helmholtz_diag(const sfem_diag_args* a, sfem_stream_t stream) {
   SFEM_REQUIRE(a->geo_mode == GEO_POINT ? a->geo != nullptr
                                         : (a->geo_elem && a->nodes),
                "sfem_helmholtz_diag: missing geometry");
+  SFEM_REQUIRE(a->coef_mode == SFEM_COEF_NONE ||
+                   a->coef_mode == SFEM_COEF_ELEM ||
+                   a->coef_mode == SFEM_COEF_POINT,
+               "sfem_helmholtz_diag: unknown coef_mode %d", a->coef_mode);
+  SFEM_REQUIRE(a->coef_mode == SFEM_COEF_NONE || a->kappa || a->sigma,
+               "sfem_helmholtz_diag: coef_mode %d needs kappa or sigma",
+               a->coef_mode);
   if ((a->elem_list ? a->num_listed : a->num_elements) == 0) return SFEM_OK;
   int rc;
   if (a->dtype == SFEM_F64)

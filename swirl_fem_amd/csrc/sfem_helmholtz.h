@@ -82,6 +82,20 @@ struct HelmholtzParams {
   int shared_stride;
 };
 
+// Variable coefficients of helmholtz_coef_kernel (include/sfem.h: kappa,
+// sigma, coef_mode of sfem_helmholtz_args), indexed by element id.
+enum CoefMode { COEF_NONE = 0, COEF_ELEM = 1, COEF_POINT = 2 };
+template <typename T>
+struct HelmholtzCoefParams : HelmholtzParams<T> {
+  const T* kappa;        // diffusivity: (E,) or (E, N) slot order; null = 1
+  const T* sigma;        // reaction: the same form; null = 1
+  int coef_mode;         // COEF_ELEM / COEF_POINT
+};
+template <typename T, int COEF>
+struct HelmholtzPrm { typedef HelmholtzCoefParams<T> type; };
+template <typename T>
+struct HelmholtzPrm<T, COEF_NONE> { typedef HelmholtzParams<T> type; };
+
 __host__ __device__ constexpr int round_up(int a, int b) {
   return (a + b - 1) / b * b;
 }
@@ -875,11 +889,20 @@ __device__ __forceinline__ void scatter_shared_sorted(
 // MASS: lambda0 != 0 (decided at launch).  The pure stiffness kernels carry no
 // mass-term code: 15-20 VGPRs less, which is what lets the multilinear kernel
 // take the sorted path without spilling.
+// COEF: variable coefficients (CoefMode).  COEF_NONE is the constant-
+// coefficient operator with a HelmholtzParams argument; the coefficient
+// kernels (COEF_ELEM / COEF_POINT: scalar fields, affine and multilinear
+// elements, slot-order scatter -- curved elements take their coefficients
+// folded into the stored factors) take a HelmholtzCoefParams.
 template <typename T, int P, int DIM, bool GS, bool SCALAR, int GM,
-          bool SORTED = false, bool MASS = true>
+          bool SORTED = false, bool MASS = true, int COEF = COEF_NONE>
 __global__ void __launch_bounds__((HelmholtzTile<T, P, DIM>::BLOCK),
                                   (HelmholtzTile<T, P, DIM>::MINW))
-helmholtz_kernel(HelmholtzParams<T> prm, DMat<T, P> dm) {
+helmholtz_kernel(typename HelmholtzPrm<T, COEF>::type prm, DMat<T, P> dm) {
+  static_assert(COEF == COEF_NONE || (SCALAR && !SORTED && GM != GEO_POINT),
+                "coefficient kernels: scalar fields, slot-order scatter, "
+                "affine / multilinear elements");
+  using PRM = typename HelmholtzPrm<T, COEF>::type;
   // unpadded LDS rows for the light (affine) kernels at P = 8, see the tile
   constexpr bool PAD =
       !(GS && SCALAR && DIM == 3 && P == 8 && GM == GEO_AFFINE);
@@ -914,7 +937,7 @@ helmholtz_kernel(HelmholtzParams<T> prm, DMat<T, P> dm) {
           (const SFEM_CONSTANT_AS DMat<T, P>*)((                              \
               const SFEM_CONSTANT_AS char*)                                   \
                   __builtin_amdgcn_kernarg_segment_ptr() +                    \
-              sizeof(HelmholtzParams<T>)),                                    \
+              sizeof(PRM)),                                                   \
           X, Y);                                                              \
     else                                                                      \
       line_apply<T, P, TR>(dmat, X, Y);                                       \
@@ -935,14 +958,41 @@ helmholtz_kernel(HelmholtzParams<T> prm, DMat<T, P> dm) {
   ElemGeom<T, P, DIM, GM> geom;
 #if SFEM_KERNARG_PICK
   // the second kernel argument as memory: per-lane weights / nodes are loads
-  static_assert(sizeof(HelmholtzParams<T>) % alignof(DMat<T, P>) == 0, "");
+  static_assert(sizeof(PRM) % alignof(DMat<T, P>) == 0, "");
   geom.template init<true>(prm, dm, e, active, i, j, t,
-                           kernarg_dmat<T, P>(sizeof(HelmholtzParams<T>)));
+                           kernarg_dmat<T, P>(sizeof(PRM)));
 #else
   geom.init(prm, dm, e, active, i, j, t);
 #endif
   uint32_t slot_off_v = (uint32_t)t;
   const uint32_t& slot_off = slot_off_v;
+
+  // Variable coefficients: k scales the reference-space flux G g, c the mass
+  // weight W.  COEF_ELEM: one value per element (a wave-uniform load when an
+  // element fills whole waves); COEF_POINT: (E, N) values in slot order, read
+  // in the plane layout of the stored factors -- lane t of slice a reads point
+  // a * TPE + t, coalesced across the lanes.  A null array stands for 1.
+  [[maybe_unused]] T kel = T(1), cel = T(1);
+  [[maybe_unused]] const T* kpt = nullptr;
+  [[maybe_unused]] const T* cpt = nullptr;
+  if constexpr (COEF == COEF_ELEM) {
+    if (active) {
+      if (prm.kappa) kel = prm.kappa[e];
+      if (MASS && prm.sigma) cel = prm.sigma[e];
+    }
+  } else if constexpr (COEF == COEF_POINT) {
+    if (prm.kappa) kpt = prm.kappa + e * N;
+    if (MASS && prm.sigma) cpt = prm.sigma + e * N;
+  }
+  // value at the lane's node of slice a (active lanes only)
+  [[maybe_unused]] auto kappa_at = [&](int a) -> T {
+    if constexpr (COEF == COEF_POINT) return kpt ? kpt[slot_off + a * TPE] : T(1);
+    else return kel;
+  };
+  [[maybe_unused]] auto sigma_at = [&](int a) -> T {
+    if constexpr (COEF == COEF_POINT) return cpt ? cpt[slot_off + a * TPE] : T(1);
+    else return cel;
+  };
 
   uint32_t enc[P];
   if (GS) {
@@ -1030,11 +1080,22 @@ helmholtz_kernel(HelmholtzParams<T> prm, DMat<T, P> dm) {
             T o0, o1, o2;
             geom.apply_multilinear3(dm, a, has_mass, d0[a], s0[o], s1[o], o0,
                                     o1, o2, Wm);
+            if constexpr (COEF != COEF_NONE) {
+              const T kq = kappa_at(a);
+              o0 *= kq; o1 *= kq; o2 *= kq;
+              if (has_mass) Wm *= sigma_at(a);
+            }
             if (has_mass) acc[a] = prm.lambda0 * Wm * ua[a];
             w0[a] = o0; s0[o] = o1; s1[o] = o2;
             continue;
           }
           geom.factors(dm, a, true, FUSE_W && has_mass, G, Wm);
+          if constexpr (COEF != COEF_NONE) {
+            const T kq = kappa_at(a);
+#pragma unroll
+            for (int f = 0; f < 6; ++f) G[f] *= kq;
+            if (has_mass) Wm *= sigma_at(a);
+          }
           if (FUSE_W && has_mass) acc[a] = prm.lambda0 * Wm * ua[a];
           if (DIM == 3) {
             const T g0 = d0[a], g1 = s0[o], g2 = s1[o];
@@ -1095,6 +1156,7 @@ helmholtz_kernel(HelmholtzParams<T> prm, DMat<T, P> dm) {
         for (int a = 0; a < P; ++a) {
           T G[6], Wm;
           geom.factors(dm, a, false, true, G, Wm);
+          if constexpr (COEF != COEF_NONE) Wm *= sigma_at(a);
           acc[a] = prm.lambda0 * Wm * ua[a];
         }
       }
@@ -1182,6 +1244,42 @@ helmholtz_kernel(HelmholtzParams<T> prm, DMat<T, P> dm) {
 }
 
 template <typename T, int P, int DIM, bool GS>
+int launch_helmholtz_coef(const HelmholtzCoefParams<T>& prm,
+                          hipStream_t stream) {
+  using Tile = HelmholtzTile<T, P, DIM>;
+  const int64_t groups = (prm.num_elements + Tile::EPB - 1) / Tile::EPB;
+  if (groups > 0x7fffffff) {
+    set_error("helmholtz: too many workgroups (%lld)", (long long)groups);
+    return SFEM_EINVAL;
+  }
+  const DMat<T, P> dm =
+      make_dmat<T, P>(prm.dmat_host, prm.weights_host, prm.nodes_host);
+  const dim3 grid((unsigned)groups), block(Tile::BLOCK);
+  const bool mass = prm.lambda0 != T(0);
+#define SFEM_LAUNCH_COEF(GMV, MASSV, CM)                                      \
+  hipLaunchKernelGGL(                                                         \
+      (helmholtz_kernel<T, P, DIM, GS, true, GMV, false, MASSV, CM>), grid,   \
+      block, 0, stream, prm, dm)
+#define SFEM_LAUNCH_COEF_GM(GMV, CM)                                          \
+  do {                                                                        \
+    if (mass) SFEM_LAUNCH_COEF(GMV, true, CM);                                \
+    else SFEM_LAUNCH_COEF(GMV, false, CM);                                    \
+  } while (0)
+  if (prm.geo_mode == GEO_AFFINE) {
+    if (prm.coef_mode == COEF_ELEM) SFEM_LAUNCH_COEF_GM(GEO_AFFINE, COEF_ELEM);
+    else SFEM_LAUNCH_COEF_GM(GEO_AFFINE, COEF_POINT);
+  } else {
+    if (prm.coef_mode == COEF_ELEM)
+      SFEM_LAUNCH_COEF_GM(GEO_MULTILINEAR, COEF_ELEM);
+    else SFEM_LAUNCH_COEF_GM(GEO_MULTILINEAR, COEF_POINT);
+  }
+#undef SFEM_LAUNCH_COEF_GM
+#undef SFEM_LAUNCH_COEF
+  SFEM_LAUNCH_CHECK();
+  return SFEM_OK;
+}
+
+template <typename T, int P, int DIM, bool GS>
 int launch_helmholtz(const HelmholtzParams<T>& prm, hipStream_t stream) {
   using Tile = HelmholtzTile<T, P, DIM>;
   const int64_t groups = (prm.num_elements + Tile::EPB - 1) / Tile::EPB;
@@ -1240,6 +1338,36 @@ int launch_helmholtz(const HelmholtzParams<T>& prm, hipStream_t stream) {
 template <typename T, int DIM>
 int dispatch_helmholtz(const HelmholtzParams<T>& prm, int P, bool gs,
                        hipStream_t stream);
+
+// The coefficient kernels, one translation unit per (dtype, ndim) as well.
+template <typename T, int DIM>
+int dispatch_helmholtz_coef(const HelmholtzCoefParams<T>& prm, int P, bool gs,
+                            hipStream_t stream);
+
+#define SFEM_HELMHOLTZ_COEF_CASE(PP)                                        \
+  case PP:                                                                  \
+    return gs ? launch_helmholtz_coef<T, PP, DIM, true>(prm, stream)        \
+              : launch_helmholtz_coef<T, PP, DIM, false>(prm, stream);
+
+#define SFEM_DEFINE_HELMHOLTZ_COEF_DISPATCH(TYPE, DIMV)                     \
+  template <>                                                               \
+  int dispatch_helmholtz_coef<TYPE, DIMV>(                                  \
+      const HelmholtzCoefParams<TYPE>& prm, int P, bool gs,                 \
+      hipStream_t stream) {                                                 \
+    using T = TYPE;                                                         \
+    constexpr int DIM = DIMV;                                               \
+    switch (P) {                                                            \
+      SFEM_HELMHOLTZ_COEF_CASE(2) SFEM_HELMHOLTZ_COEF_CASE(3)               \
+      SFEM_HELMHOLTZ_COEF_CASE(4) SFEM_HELMHOLTZ_COEF_CASE(5)               \
+      SFEM_HELMHOLTZ_COEF_CASE(6) SFEM_HELMHOLTZ_COEF_CASE(7)               \
+      SFEM_HELMHOLTZ_COEF_CASE(8) SFEM_HELMHOLTZ_COEF_CASE(9)               \
+      SFEM_HELMHOLTZ_COEF_CASE(10) SFEM_HELMHOLTZ_COEF_CASE(11)             \
+      SFEM_HELMHOLTZ_COEF_CASE(12)                                          \
+      default:                                                              \
+        set_error("helmholtz: P=%d outside the compiled range 2..12", P);   \
+        return SFEM_EUNSUPPORTED;                                           \
+    }                                                                       \
+  }
 
 #define SFEM_HELMHOLTZ_CASE(PP)                                             \
   case PP:                                                                  \

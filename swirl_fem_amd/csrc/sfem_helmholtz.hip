@@ -246,6 +246,9 @@ struct HelmholtzCall {
   int64_t num_chains = 0;
   int64_t layered_extent = 0;
   int64_t dot_slots = 0;
+  const void* kappa = nullptr;
+  const void* sigma = nullptr;
+  int coef_mode = 0;
 };
 
 template <typename T>
@@ -264,6 +267,15 @@ static int run_helmholtz(const HelmholtzCall& c, hipStream_t stream) {
   prm.colored = c.colored;
   prm.shared_order = c.shared_order;
   prm.shared_stride = c.shared_stride;
+  if (c.coef_mode != COEF_NONE) {
+    HelmholtzCoefParams<T> cp{};
+    static_cast<HelmholtzParams<T>&>(cp) = prm;
+    cp.kappa = (const T*)c.kappa;
+    cp.sigma = (const T*)c.sigma;
+    cp.coef_mode = c.coef_mode;
+    if (c.ndim == 3) return dispatch_helmholtz_coef<T, 3>(cp, c.P, c.gs, stream);
+    return dispatch_helmholtz_coef<T, 2>(cp, c.P, c.gs, stream);
+  }
   if (c.cluster_elems) {
     ClusterParams<T> cl{c.cluster_elems, c.cluster_offsets, c.cluster_nodes,
                         c.num_clusters};
@@ -322,6 +334,28 @@ static int run_helmholtz(const HelmholtzCall& c, hipStream_t stream) {
   if (c.ndim == 2) return dispatch_helmholtz<T, 2>(prm, c.P, c.gs, stream);
   set_error("helmholtz: ndim=%d (fused kernel supports 2 and 3)", c.ndim);
   return SFEM_EUNSUPPORTED;
+}
+
+// The variable-coefficient launches (helmholtz_coef_kernel) take scalar
+// fields on index rows, affine or multilinear elements.
+static int check_coefficients(const char* who, const sfem_helmholtz_args* a) {
+  if (a->coef_mode == SFEM_COEF_NONE) return SFEM_OK;
+  SFEM_REQUIRE(a->coef_mode == SFEM_COEF_ELEM || a->coef_mode == SFEM_COEF_POINT,
+               "%s: unknown coef_mode %d", who, a->coef_mode);
+  SFEM_REQUIRE(a->kappa || a->sigma,
+               "%s: coef_mode %d needs kappa or sigma", who, a->coef_mode);
+  SFEM_REQUIRE(a->ncomp == 1, "%s: coefficients take scalar fields", who);
+  SFEM_REQUIRE(a->ndim == 2 || a->ndim == 3, "%s: coefficients need ndim 2 or 3",
+               who);
+  SFEM_REQUIRE(a->geo_mode == SFEM_GEO_AFFINE ||
+                   a->geo_mode == SFEM_GEO_MULTILINEAR,
+               "%s: coefficients need affine or multilinear elements (fold "
+               "them into the stored factors of curved ones)", who);
+  SFEM_REQUIRE(!a->cluster_elems && !a->facet_table && !a->shared_order &&
+                   !a->layered_extent,
+               "%s: coefficients run on index rows (no cluster, facet, "
+               "layered or sorted assembly)", who);
+  return SFEM_OK;
 }
 
 static int check_geometry(const char* who, int geo_mode, const void* geo,
@@ -457,6 +491,8 @@ int sfem_helmholtz_apply(const sfem_helmholtz_args* a, sfem_stream_t stream) {
   int rc = check_geometry("sfem_helmholtz_apply", a->geo_mode, a->geo,
                           a->geo_elem, a->weights, a->nodes);
   if (rc) return rc;
+  rc = check_coefficients("sfem_helmholtz_apply", a);
+  if (rc) return rc;
   const int64_t work = a->elem_list ? a->num_listed : a->num_elements;
   SFEM_REQUIRE(work >= 0 && work <= a->num_elements,
                "sfem_helmholtz_apply: bad element list length");
@@ -466,6 +502,9 @@ int sfem_helmholtz_apply(const sfem_helmholtz_args* a, sfem_stream_t stream) {
                   a->P, a->ncomp, a->geo_mode, a->lambda0, a->lambda1, true,
                   a->dot_out, a->colored, a->node_stride, a->comp_stride,
                   a->shared_order, a->shared_stride};
+  c.kappa = a->kappa;
+  c.sigma = a->sigma;
+  c.coef_mode = a->coef_mode;
   SFEM_REQUIRE(!a->shared_order || (a->shared_stride > 0 &&
                                     a->shared_stride <= 0xFFFF),
                "sfem_helmholtz_apply: bad shared_stride");
@@ -637,6 +676,8 @@ int sfem_helmholtz_local(const sfem_helmholtz_args* a, sfem_stream_t stream) {
   int rc = check_geometry("sfem_helmholtz_local", a->geo_mode, a->geo,
                           a->geo_elem, a->weights, a->nodes);
   if (rc) return rc;
+  rc = check_coefficients("sfem_helmholtz_local", a);
+  if (rc) return rc;
   const int64_t work = a->elem_list ? a->num_listed : a->num_elements;
   SFEM_REQUIRE(work >= 0 && work <= a->num_elements,
                "sfem_helmholtz_local: bad element list length");
@@ -645,6 +686,9 @@ int sfem_helmholtz_local(const sfem_helmholtz_args* a, sfem_stream_t stream) {
                   a->elem_list, a->dmat, a->weights, a->nodes, work, a->ndim,
                   a->P, a->ncomp, a->geo_mode, a->lambda0, a->lambda1, false,
                   nullptr, 0, a->node_stride, a->comp_stride};
+  c.kappa = a->kappa;
+  c.sigma = a->sigma;
+  c.coef_mode = a->coef_mode;
   if (a->dtype == SFEM_F64) return run_helmholtz<double>(c, as_stream(stream));
   return run_helmholtz<float>(c, as_stream(stream));
 }

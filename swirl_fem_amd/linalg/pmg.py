@@ -487,6 +487,25 @@ def _cheb_coefficients(lo, hi, degree):
   return out
 
 
+def coarse_coefficient(coef, weights):
+  """A diffusivity / reaction coefficient of the fine operator as the coarse
+  levels take it (the same elements on every level): None, a scalar or an
+  (E,) tensor unchanged; per-point values (E, Q) become the per-element mean
+  weighted by W = w detJ at those points, `weights` (E, Q):
+  sum_q k_q W_q / sum_q W_q (as the facet mean of the Robin alpha in
+  `_coarse_terms`).  `coef` in the normal form of `operators.coefficient`;
+  returns what `helmholtz_operator` accepts."""
+  from swirl_fem_amd import _lib
+  if coef is None or isinstance(coef, float):
+    return coef
+  mode, t = coef
+  if mode == _lib.COEF_ELEM:
+    return t
+  w = weights.to(torch.float64)
+  mean = (t.to(torch.float64) * w).sum(dim=1) / w.sum(dim=1)
+  return mean.to(t.dtype).contiguous()
+
+
 class _Level:
   """Operator, smoother data and work vectors of one order."""
 
@@ -500,6 +519,8 @@ class _Level:
     self.cheb = None
     self.lam_max = None
     self.boundary = []          # [(BoundaryMassOperator, scale)]
+    # (diffusivity, reaction) of the coarser levels (`coarse_coefficient`)
+    self.coefs = (None, None)
     # transfer from the next coarser level (set by the hierarchy)
     self.transfer = None
 
@@ -690,7 +711,9 @@ class PMultigridPreconditioner:
       apply_fn = lambda u, out: self._exchange_(op.apply(u, l0, l1, out=out),
                                                 mesh)
     elif isinstance(op, operators.HelmholtzOperator):
-      colored = fes.helmholtz_operator(dirichlet, assembly='colored')
+      k, c = op.coef_source
+      colored = fes.helmholtz_operator(dirichlet, assembly='colored',
+                                       diffusivity=k, reaction=c)
       self._fine_colored = colored
       apply_fn = lambda u, out: colored.apply(u, l0, l1, out=out)
     else:
@@ -713,6 +736,11 @@ class PMultigridPreconditioner:
         diag = diag + s * b.diagonal()
     lev = _Level(mesh, op, apply_fn, dirichlet, self._dinv(diag))
     lev.boundary = self.boundary_terms
+    if op.coefs is not None:
+      k, c = op.coefs
+      w = (op.point_weights() if any(
+          operators._point_coefficient(x) for x in op.coefs) else None)
+      lev.coefs = (coarse_coefficient(k, w), coarse_coefficient(c, w))
     return lev
 
   def _dinv(self, d):
@@ -741,8 +769,10 @@ class PMultigridPreconditioner:
         cmesh, Quadrature1D.create(pc + 1, NodeType.GAUSS_LOBATTO_LEGENDRE))
     l0, l1 = self.lambda0, self.lambda1
     # (the coarsest level only assembles its element matrices)
+    k, c = fine.coefs
     cop = fes.helmholtz_operator(cdir, assembly='auto' if (
-        coarsest or self.plan is not None) else 'colored')
+        coarsest or self.plan is not None) else 'colored', diffusivity=k,
+        reaction=c)
     cterms = self._coarse_terms(fine, fes, celems, cdir)
     diag = cop.diagonal(l0, l1)
     if cterms:
@@ -758,6 +788,7 @@ class PMultigridPreconditioner:
                                                 cmesh)
     lev = _Level(cmesh, cop, apply_fn, cdir, self._dinv(diag))
     lev.boundary = cterms
+    lev.coefs = fine.coefs
     lev.fespace = fes
     offsets, slots = cmesh.assembly_plan().csr()
     owner = owner_bits(fel, fmesh.num_nodes)
