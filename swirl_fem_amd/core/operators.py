@@ -1462,8 +1462,12 @@ class StokesDivGrad:
     """(Np,) -> (Np,):  D [ QQ^T ( scale * mask * D^T p ) ]  = `StokesSEM.E`
     for a diagonal Q, the direct-stiffness sum of D^T without atomics (see
     `_layered_plan`); periodic images included, one partition."""
-    enc, n_ext, node_of_pos, members, offsets, num_classes = \
-        self._layered_plan()
+    plan = self._layered_plan()
+    if plan is None:
+      raise NotImplementedError(
+          'layered E needs index-row launches on one partition (no facet '
+          'launches, positions within the index range)')
+    enc, n_ext, node_of_pos, members, offsets, num_classes = plan
     mesh = self.vspace.mesh
     if tuple(p.shape) != (self.num_pressure_nodes,):
       raise ValueError(f'expected ({self.num_pressure_nodes},) pressure, got '

@@ -94,6 +94,15 @@ class _StepTimer:
       self.t0 = now
 
 
+def _check_given_sem(sem, order, ndim):
+  """A caller's `sem` must be the stepper the other arguments describe."""
+  mesh = sem.velocity.mesh
+  if mesh.gridpoints_1d.num_points != order + 1 or mesh.ndim != ndim:
+    raise ValueError(
+        f'sem has {mesh.gridpoints_1d.num_points} velocity points per '
+        f'direction in {mesh.ndim}D; order={order} in {ndim}D was asked for')
+
+
 def _histories(sem, u0, p0, time_order):
   us = tuple(u0 for _ in range(time_order))
   ps = tuple(p0 for _ in range(time_order))
@@ -105,12 +114,17 @@ def lid_driven_cavity(n=8, order=5, reynolds=100.0, dt=1e-3, steps=10,
                       time_order=3, device=None, premesh=None, tol=1e-8,
                       profile=None, pressure_projection=None,
                       pressure_preconditioner=None,
-                      velocity_preconditioner=None):
-  """2D lid-driven cavity on [0,1]^2; returns (sem, u, p, diagnostics)."""
+                      velocity_preconditioner=None, sem=None):
+  """2D lid-driven cavity on [0,1]^2; returns (sem, u, p, diagnostics).
+  `sem`: a ready `StokesSEM` of the cavity (its own node numbering, Dirichlet
+  walls) instead of one refined here from `premesh` / `n`."""
   timer = _StepTimer(profile, device)
-  pm = premesh if premesh is not None else unit_cube_mesh(n, ndim=2)
-  sem = StokesSEM.create(pm, {'boundary': (BCType.DIRICHLET, 0.0)},
-                         order=order, device=device)
+  if sem is None:
+    pm = premesh if premesh is not None else unit_cube_mesh(n, ndim=2)
+    sem = StokesSEM.create(pm, {'boundary': (BCType.DIRICHLET, 0.0)},
+                           order=order, device=device)
+  else:
+    _check_given_sem(sem, order, 2)
   x = sem.velocity.mesh.node_coords
   # regularised lid u = (16 x^2 (1-x)^2, 0) on y = 1, zero on the other walls
   lid = (x[:, 1] > 1.0 - 1e-12).to(x.dtype)
@@ -120,7 +134,7 @@ def lid_driven_cavity(n=8, order=5, reynolds=100.0, dt=1e-3, steps=10,
   p0 = torch.zeros(sem.pressure.pspace.mesh.num_nodes, dtype=x.dtype,
                    device=x.device)
   us, ps, Cus = _histories(sem, u0, p0, time_order)
-  iters = []
+  iters, status = [], []
   timer.setup_done()
   for _ in range(steps):
     u, p, Cu, aux = navier_stokes_step(
@@ -133,7 +147,8 @@ def lid_driven_cavity(n=8, order=5, reynolds=100.0, dt=1e-3, steps=10,
     timer.step_done()
     iters.append((aux['u_star_info']['num_iterations'],
                   aux['dp_info']['num_iterations']))
-  diag = {'cg_iterations': iters,
+    status.append((aux['u_star_info']['status'], aux['dp_info']['status']))
+  diag = {'cg_iterations': iters, 'cg_status': status,
           'max_divergence': float(sem.D(us[-1]).abs().max()),
           'kinetic_energy': float(0.5 * (sem.velocity_mass_diag *
                                          us[-1] ** 2).sum())}
@@ -142,13 +157,18 @@ def lid_driven_cavity(n=8, order=5, reynolds=100.0, dt=1e-3, steps=10,
 
 def taylor_green(n=4, order=3, reynolds=100.0, dt=1e-2, steps=5, time_order=3,
                  device=None, tol=1e-8, profile=None, pressure_projection=None,
-                 pressure_preconditioner=None, velocity_preconditioner=None):
+                 pressure_preconditioner=None, velocity_preconditioner=None,
+                 sem=None):
   """3D Taylor-Green vortex on the periodic box [0, 2 pi]^3 (`n` elements
-  per direction, or one count per direction)."""
+  per direction, or one count per direction).  `sem`: a ready `StokesSEM` of
+  that box (its own node numbering) instead of one refined here."""
   timer = _StepTimer(profile, device)
-  ns = (n,) * 3 if np.isscalar(n) else tuple(n)
-  pm = box_mesh(ns, (0.0,) * 3, (2 * np.pi,) * 3, periodic_dims=(0, 1, 2))
-  sem = StokesSEM.create(pm, {}, order=order, device=device)
+  if sem is None:
+    ns = (n,) * 3 if np.isscalar(n) else tuple(n)
+    pm = box_mesh(ns, (0.0,) * 3, (2 * np.pi,) * 3, periodic_dims=(0, 1, 2))
+    sem = StokesSEM.create(pm, {}, order=order, device=device)
+  else:
+    _check_given_sem(sem, order, 3)
   x = sem.velocity.mesh.node_coords
   u0 = torch.stack([torch.sin(x[:, 0]) * torch.cos(x[:, 1]) * torch.cos(x[:, 2]),
                     -torch.cos(x[:, 0]) * torch.sin(x[:, 1]) * torch.cos(x[:, 2]),
@@ -160,7 +180,7 @@ def taylor_green(n=4, order=3, reynolds=100.0, dt=1e-2, steps=5, time_order=3,
   # share, so the plain sum is the integral
   w = sem.velocity_mass_diag
   energy = [float(0.5 * (w * u0 ** 2).sum())]
-  iters = []
+  iters, status = [], []
   timer.setup_done()
   for _ in range(steps):
     u, p, Cu, aux = navier_stokes_step(
@@ -173,7 +193,8 @@ def taylor_green(n=4, order=3, reynolds=100.0, dt=1e-2, steps=5, time_order=3,
     energy.append(float(0.5 * (w * u ** 2).sum()))
     iters.append((aux['u_star_info']['num_iterations'],
                   aux['dp_info']['num_iterations']))
-  diag = {'kinetic_energy': energy, 'cg_iterations': iters,
+    status.append((aux['u_star_info']['status'], aux['dp_info']['status']))
+  diag = {'kinetic_energy': energy, 'cg_iterations': iters, 'cg_status': status,
           'max_divergence': float(sem.D(us[-1]).abs().max())}
   return sem, us[-1], ps[-1], diag
 
@@ -210,7 +231,7 @@ def taylor_green_blocks(n=4, order=3, block_grid=(2, 2, 2), rank=None,
   # unassembled mass diagonal: the holders of a node each carry their share
   w = sem.velocity_mass_diag
   energy = [float(sem._global_sum(0.5 * (w * u0 ** 2).sum().reshape(1)))]
-  iters = []
+  iters, status = [], []
   timer.setup_done()
   for _ in range(steps):
     u, p, Cu, aux = navier_stokes_step(
@@ -222,6 +243,7 @@ def taylor_green_blocks(n=4, order=3, block_grid=(2, 2, 2), rank=None,
     energy.append(float(sem._global_sum(0.5 * (w * u ** 2).sum().reshape(1))))
     iters.append((aux['u_star_info']['num_iterations'],
                   aux['dp_info']['num_iterations']))
+    status.append((aux['u_star_info']['status'], aux['dp_info']['status']))
     timer.step_done()
-  diag = {'kinetic_energy': energy, 'cg_iterations': iters}
+  diag = {'kinetic_energy': energy, 'cg_iterations': iters, 'cg_status': status}
   return sem, us[-1], ps[-1], diag

@@ -394,6 +394,12 @@ class StokesPressure:
                                    node_type=NodeType.GAUSS_LEGENDRE)
     pmesh = refine_premesh(premesh, gridpoints_1d=gridpoints_1d).finalize(
         axis_name, rank=rank, device=device, dtype=dtype)
+    return cls.from_mesh(pmesh, quadrature)
+
+  @classmethod
+  def from_mesh(cls, pmesh: Mesh, quadrature: Quadrature1D) -> 'StokesPressure':
+    """The pressure space on a finalised Gauss-Legendre mesh, whatever its
+    node numbering (`create` refines a premesh and calls this)."""
     return cls(pspace=FiniteElementSpace.create(mesh=pmesh,
                                                 quadrature=quadrature))
 
@@ -453,6 +459,15 @@ class StokesVelocity:
             axis_name='blocks', neighbor_plan=neighbor_plan,
             exchange_gather_indices=torch.as_tensor(cat, device=vmesh.device),
             exchange_unique_indices=None)
+    return cls.from_mesh(vmesh, boundary_conditions,
+                         num_convection_overint_nodes)
+
+  @classmethod
+  def from_mesh(cls, vmesh: Mesh, boundary_conditions,
+                num_convection_overint_nodes: int = 2) -> 'StokesVelocity':
+    """The velocity space on a finalised Gauss-Lobatto-Legendre mesh, whatever
+    its node numbering (`create` refines a premesh and calls this)."""
+    gridpoints_1d = vmesh.gridpoints_1d
     vspace = FiniteElementSpace.create(
         mesh=vmesh, quadrature=Quadrature1D.create_from_nodes_1d(gridpoints_1d))
     interior_mask = dirichlet_bc(vmesh, boundary_conditions)
@@ -620,6 +635,30 @@ class StokesSEM:
                                      device=device, dtype=dtype,
                                      axis_name=axis_name, rank=rank,
                                      neighbor_plan=neighbor_plan)
+    return cls.from_spaces(velocity, pressure)
+
+  @classmethod
+  def from_meshes(cls, vmesh: Mesh, pmesh: Mesh, boundary_conditions,
+                  num_convection_overint_nodes: int = 2) -> 'StokesSEM':
+    """The operators on two finalised meshes of the same elements: `vmesh`
+    with P Gauss-Lobatto-Legendre points per direction, `pmesh` with P - 2
+    Gauss-Legendre points, each under any node numbering."""
+    P = vmesh.gridpoints_1d.num_points
+    if pmesh.gridpoints_1d.num_points != P - 2:
+      raise ValueError(f'expected {P - 2} pressure points per direction; got '
+                       f'{pmesh.gridpoints_1d.num_points}')
+    if pmesh.num_elements != vmesh.num_elements:
+      raise ValueError('velocity and pressure meshes differ in elements')
+    quadrature = Quadrature1D.create(
+        num_points=P, quadrature_type=NodeType.GAUSS_LOBATTO_LEGENDRE)
+    return cls.from_spaces(
+        StokesVelocity.from_mesh(vmesh, boundary_conditions,
+                                 num_convection_overint_nodes),
+        StokesPressure.from_mesh(pmesh, quadrature))
+
+  @classmethod
+  def from_spaces(cls, velocity: StokesVelocity,
+                  pressure: StokesPressure) -> 'StokesSEM':
     ones = torch.ones(velocity.local_shape, dtype=velocity.mesh.dtype,
                       device=velocity.mesh.device)
     velocity_mass_diag = velocity.scatter(velocity.B_local(ones))

@@ -225,11 +225,14 @@ def _ns_worker(rank, world, port, order, results):
       p0 = torch.zeros(sem.pressure.pspace.mesh.num_nodes, dtype=x.dtype,
                        device=dev)
       us, ps, Cus = _histories(sem, u0, p0, 2)
+      status = []
       for _ in range(2):
         u, p, Cu, aux = navier_stokes_step(
             sem, us, ps, Cus, reynolds=50.0, dt=1e-2, time_order=2,
             tol=1e-11, atol=0.0)
         us, ps, Cus = us[1:] + (u,), ps[1:] + (p,), Cus[1:] + (Cu,)
+        status += [aux['u_star_info']['status'], aux['dp_info']['status']]
+      aux['status'] = status
       return u, p, aux
 
     sem_p = StokesSEM.create(pm.replace(partitions=parts), bcs, order,
@@ -237,7 +240,7 @@ def _ns_worker(rank, world, port, order, results):
     assert sem_p.is_partitioned and sem_p._divgrad() is not None
     u_p, p_p, aux = run(sem_p)
     sem_g = StokesSEM.create(pm, bcs, order, device=dev)
-    u_g, p_g, _ = run(sem_g)
+    u_g, p_g, aux_g = run(sem_g)
     gl = NodeType.GAUSS_LEGENDRE
     gll = NodeType.GAUSS_LOBATTO_LEGENDRE
     pp = pm.replace(partitions=parts)
@@ -253,7 +256,8 @@ def _ns_worker(rank, world, port, order, results):
         eu=float(((u_p - u_g[vt]) * vreal).abs().max() / u_g.abs().max()),
         ep=float(((p_p - p_g[pt]) * preal).abs().max() / p_g.abs().max()),
         its=(aux['u_star_info']['num_iterations'],
-             aux['dp_info']['num_iterations']))
+             aux['dp_info']['num_iterations']),
+        status=aux['status'] + aux_g['status'])
   finally:
     dist.destroy_process_group()
 
@@ -272,6 +276,8 @@ def test_partitioned_navier_stokes_matches_single_rank():
   for r in range(world):
     assert res[r]['eu'] < 1e-8 and res[r]['ep'] < 1e-7, res[r]
     assert res[r]['its'] == res[0]['its']
+    # every solve of both steps, partitioned and one-rank, converged
+    assert res[r]['status'] == ['converged'] * 8, res[r]
 
 
 def _ns_blocks_worker(rank, world, port, order, results):

@@ -26,6 +26,13 @@ def relerr(a, b):
   return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
 
 
+def all_converged(*diags):
+  """Every solve of every step of the driver runs ended 'converged'."""
+  for d in diags:
+    assert d['cg_status'] and all(
+        s == ('converged', 'converged') for s in d['cg_status']), d['cg_status']
+
+
 @pytest.fixture(scope='module')
 def case():
   pm = SC.make_premesh()
@@ -138,6 +145,8 @@ def test_stokes_one_step(case):
   assert float((pr - ps[-1]).abs().max()) < 50 * DT ** 2
   assert float(aux['u_star_info']['residual']) < 1e-7
   assert float(aux['dp_info']['residual']) < 1e-7
+  assert aux['u_star_info']['status'] == 'converged', aux['u_star_info']
+  assert aux['dp_info']['status'] == 'converged', aux['dp_info']
   uo, po, auxo = orc.stokes_one_step(
       [x.cpu().numpy() for x in us[:-1]], [x.cpu().numpy() for x in ps[:-1]],
       0, 1, DT, K, alpha=0.05, tol=1e-12, atol=1e-12)
@@ -166,6 +175,8 @@ def test_lid_driven_cavity_steps_match_oracle():
   sem, u, p, diag = drv.lid_driven_cavity(order=order, reynolds=100.0, dt=1e-3,
                                           steps=3, device=DEV, premesh=pm,
                                           tol=1e-11)
+  assert all(s == ('converged', 'converged') for s in diag['cg_status']), \
+      diag['cg_status']
   v, pp = _staged(pm, order)
   orc = O.StokesOracle(v, pp, order, v['physical_masks']['boundary'])
   xc = v['node_coords']
@@ -196,6 +207,8 @@ def test_taylor_green_3d_periodic():
   n, order = 3, 3
   sem, u, p, diag = drv.taylor_green(n=n, order=order, reynolds=50.0, dt=2e-2,
                                      steps=3, device=DEV, tol=1e-10)
+  assert all(s == ('converged', 'converged') for s in diag['cg_status']), \
+      diag['cg_status']
   e = diag['kinetic_energy']
   assert all(b < a for a, b in zip(e, e[1:]))
   assert e[-1] > 0.8 * e[0]
@@ -249,6 +262,8 @@ def test_taylor_green_3d_p7_step_matches_oracle():
   kw = dict(reynolds=1600.0, dt=1e-3, steps=steps, time_order=3)
   sem, u, p, diag = drv.taylor_green(n=n, order=order, device=DEV, tol=1e-12,
                                      **kw)
+  assert all(s == ('converged', 'converged') for s in diag['cg_status']), \
+      diag['cg_status']
   pm = unit_cube_mesh(n, ndim=3, a=0.0, b=2 * np.pi, periodic_dims=(0, 1, 2))
   uo, po = _taylor_green_oracle(pm, order, tol=1e-12, **kw)
   assert relerr(u, uo) < 1e-8
@@ -405,6 +420,7 @@ def test_pressure_projection_cuts_iterations():
   for b in rhs:
     x0 = hist.guess(b)
     x, info = cg(E, b, x0=x0, M=M, tol=1e-9)
+    assert info['status'] == 'converged', info
     base.append(info['num_iterations'])
     hist.update(x, x0, E)
   assert hist.count == 3
@@ -413,8 +429,10 @@ def test_pressure_projection_cuts_iterations():
   b = 0.3 * rhs[0] - 1.7 * rhs[1] + 0.5 * rhs[2]   # in the span
   x, info = cg(E, b, x0=hist.guess(b), M=M, tol=1e-7)
   assert info['num_iterations'] <= 2, info
+  assert info['status'] == 'converged', info
   xz, iz = cg(E, b, M=M, tol=1e-7)
   assert iz['num_iterations'] > 10
+  assert iz['status'] == 'converged', iz
   mean0 = lambda t: t - t.mean()
   assert float((mean0(x) - mean0(xz)).abs().max()) < 1e-5 * float(
       mean0(xz).abs().max())
@@ -423,6 +441,7 @@ def test_pressure_projection_cuts_iterations():
   assert float((u1 - u0).abs().max()) < 1e-7 * float(u0.abs().max())
   assert float((mean0(p1) - mean0(p0)).abs().max()) < 1e-5 * float(
       mean0(p0).abs().max())
+  all_converged(d0, d1)
   it0 = [b for _, b in d0['cg_iterations']]
   it1 = [b for _, b in d1['cg_iterations']]
   assert it1[0] == it0[0]                  # nothing to project onto yet
@@ -456,6 +475,7 @@ def test_schwarz_pressure_preconditioner():
   assert float((u1 - u0).abs().max()) < 1e-7 * float(u0.abs().max())
   assert float((mean0(p1) - mean0(p0)).abs().max()) < 1e-5 * float(
       mean0(p0).abs().max())
+  all_converged(d0, d1)
   it0 = [b for _, b in d0['cg_iterations']]
   it1 = [b for _, b in d1['cg_iterations']]
   assert 1.15 * sum(it1) <= sum(it0), (it0, it1)
@@ -512,6 +532,7 @@ def test_schwarz_pressure_preconditioner():
   _, ub, pb, db = drv.lid_driven_cavity(pressure_preconditioner='schwarz',
                                         **kw2)
   assert float((ub - ua).abs().max()) < 1e-7 * float(ua.abs().max())
+  all_converged(da, db)
   ia = sum(b for _, b in da['cg_iterations'])
   ib = sum(b for _, b in db['cg_iterations'])
   assert ib <= ia, (da['cg_iterations'], db['cg_iterations'])
@@ -535,6 +556,7 @@ def test_mass_preconditioned_velocity_solve():
     del os.environ['SFEM_VELOCITY_PC']
   assert float((u1 - u0).abs().max()) <= 1e-8 * float(u0.abs().max())
   assert float((p1 - p0).abs().max()) <= 1e-6 * max(1.0, float(p0.abs().max()))
+  all_converged(d0, d1)
   it0 = [v for v, _ in d0['cg_iterations']]
   it1 = [v for v, _ in d1['cg_iterations']]
   assert all(b * 3 <= a for a, b in zip(it0, it1)), (it0, it1)
