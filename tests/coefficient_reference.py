@@ -5,8 +5,10 @@
 
 the coefficient form of `pmg_reference.element_matrices` (the oracle's
 geometry), applied element by element without forming the (n, n) matrices so
-that 3D orders up to p = 6 stay small.  Also the coarse-level coefficient rule
-of `linalg/pmg.py` restated."""
+that 3D orders up to p = 6 stay small (above that: the sum-factorised
+`tests/sumfact_reference.py`, which holds no (E, Q, n, d) gradients and
+reaches P = 12 in 3D).  Also the coarse-level coefficient rule of
+`linalg/pmg.py` restated."""
 
 import numpy as np
 

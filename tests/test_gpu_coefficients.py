@@ -17,6 +17,7 @@ from swirl_fem_amd.examples.helmholtz import BCType, solve_helmholtz
 from tests import bvp_reference as BR
 from tests import coefficient_reference as R
 from tests import geometry_cases as G
+from tests.fp32util import tolerance
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -126,7 +127,7 @@ def test_fp32_within_policy(ndim, P):
                               reaction=_dev(c, torch.float32))
   u = rng.standard_normal(mesh.num_nodes)
   got = _np(op.apply(_dev(u, torch.float32), 0.7, 1.3))
-  tol = 2e-5 if P >= 11 else 1e-5
+  tol = tolerance(torch.float32, P)
   assert _rel(got, R.apply(ref, u, 0.7, 1.3, kq, cq)) <= tol
 
 
