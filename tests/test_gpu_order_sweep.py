@@ -24,6 +24,7 @@ from swirl_fem_amd.core.interpolation import NodeType, Quadrature1D
 from tests import geometry_cases as G
 from tests import sumfact_reference as S
 from tests.fp32util import F32Rng, f32_mesh, f32r, tolerance
+from tests.packing import epb
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -47,25 +48,6 @@ FP32_EXCEPTIONS = {
     (3, 12, 'd', 'constant'): 2 * 1.199e-5,
     (3, 12, 'd', 'point'): 2 * 1.208e-5,
 }
-
-
-def epb(ndim, P, itemsize):
-  """Elements per workgroup: the rule of `HelmholtzTile::pick_epb`."""
-  tpe = P * P if ndim == 3 else P
-  if 64 % tpe == 0:
-    return 64 // tpe
-  if tpe > 32:                  # more than half a wave, or several waves
-    return 1
-  sb = P | 1
-  lds = 2 * P * (P * sb if ndim == 3 else sb) * itemsize
-  best, best_util = 1, 0.0
-  for n in range(1, 17):
-    thr = -(-n * tpe // 64) * 64
-    if thr > 512 or n * lds > 40 * 1024:
-      break
-    if n * tpe / thr > best_util + 1e-9:
-      best, best_util = n, n * tpe / thr
-  return best
 
 
 def padding(ndim, P, itemsize=8):
