@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SFEM_ABI_VERSION 8
+#define SFEM_ABI_VERSION 9
 
 enum { SFEM_F32 = 0, SFEM_F64 = 1 };
 enum {
@@ -324,6 +324,23 @@ typedef struct sfem_helmholtz_args {
   /* the sum over the slots in index order (sfem_cg_scalars_n) is bitwise       */
   /* reproducible                                                               */
   int64_t dot_slots;
+  /* Advective term (NULL = off): the operator becomes                        */
+  /*   lambda0 B_c + lambda1 A_k + C_b,                                       */
+  /*   C_b[i,j] = sum_q W_q phi_i(q) b_q . grad phi_j(q),                     */
+  /* not scaled by either lambda.  `beta` holds the velocity with the         */
+  /* geometry folded in, beta[e,q,d] = W[e,q] sum_j b[e,q,j] invjac[e,q,j,d]  */
+  /* (d = reference direction), at the element's points in slot order         */
+  /* (lexicographic, axis 0 slowest), indexed by element id, in the dtype of  */
+  /* the field.  Honoured by sfem_helmholtz_apply on index rows and by        */
+  /* sfem_helmholtz_local; every geo_mode but SFEM_GEO_BOX.  kappa / sigma    */
+  /* (below) then come per point only (SFEM_COEF_POINT, or off), folded into  */
+  /* the stored factors for SFEM_GEO_POINT.  Vector fields, cluster,          */
+  /* facet, chain, layered and sorted assembly, dot_out and SFEM_COEF_ELEM    */
+  /* return SFEM_EUNSUPPORTED.                                                */
+  /* The field sits in front of the coefficient block, which stays the tail   */
+  /* of the struct; callers that zero the struct keep the operator without    */
+  /* the term.                                                                */
+  const void* beta;       /* (E, n, ndim) or NULL = off                       */
   /* Variable coefficients (NULL / 0 = off): the operator becomes             */
   /*   lambda0 B_c + lambda1 A_k,  B_c[i,j] = sum_q c_q W_q phi_i phi_j,      */
   /*   A_k[i,j] = sum_q k_q grad phi_i . G_q grad phi_j.                      */
@@ -976,6 +993,58 @@ int sfem_boundary_add_rows(const void* local, const int32_t* rows,
                            const int64_t* offsets, const int32_t* slots,
                            int64_t num_rows, void* out, int dtype,
                            sfem_stream_t stream);
+/* ---------------------------------------------------------------- BiCGStab ---
+ * Right-preconditioned BiCGStab (linalg/bicgstab.py) for the non-symmetric
+ * systems of an advective term: r is the true residual and the solve stops on
+ * r.r <= max(tol^2 b.b, atol^2).  As in the CG core the scalars live in a
+ * device array, `scalars` of SFEM_BICGSTAB_NSCALARS doubles, every kernel
+ * returns at once when `done` is set and the host only polls:
+ *   [0] rho = r0.r of the open iteration   [1] r0.r being summed   [2] alpha
+ *   [3] omega   [4] beta   [5] r0.v   [6] s.s   [7] t.s   [8] t.t
+ *   [9] r.r being summed   [10] b.b   [11] max(tol^2 b.b, atol^2)   [12] done
+ *   [13] iterations   [14] status, SFEM_BICGSTAB_STATUS_*
+ *   [15] the iteration stopped after its first half (s.s under the threshold:
+ *        x += alpha phat, r = s, no second apply is read)
+ *   [16] r.r of the last closed iteration
+ * One iteration, with phat = M p and shat = M s (M = diag(dinv) is folded into
+ * the kernels; dinv NULL: phat / shat are p / s themselves):
+ *   sfem_bicgstab_update_p    p = r + beta (p - omega v); phat = dinv p
+ *   v = A phat;  sfem_bicgstab_dot(r0, v, slot 5);  scalars phase 1: alpha
+ *   sfem_bicgstab_update_s    s = r - alpha v; shat = dinv s; [6] += s.s
+ *   scalars phase 2 (half-step test);  t = A shat
+ *   sfem_bicgstab_dot(t, s, slot 7, two = 1)   [7] += t.s, [8] += t.t
+ *   sfem_bicgstab_update_xr   omega = [7] / [8]; x += alpha phat + omega shat;
+ *                             r = s - omega t; [9] += r.r, [1] += r0.r
+ *   scalars phase 3           closes: beta, rho, counter, stop test
+ * Phase 0 starts a solve from [10] = b.b, [9] = r.r, [1] = r0.r; p and v must
+ * start as zeros.  rho = 0, r0.v = 0 and omega = 0 (t.s = 0 or t = 0) end the
+ * solve with BAD_RHO / BAD_ALPHA / BAD_OMEGA before anything is divided by
+ * them: x stays finite.                                                       */
+#define SFEM_BICGSTAB_NSCALARS 32
+#define SFEM_BICGSTAB_STATUS_RUNNING 0.0
+#define SFEM_BICGSTAB_STATUS_CONVERGED 1.0
+#define SFEM_BICGSTAB_STATUS_MAXITER 2.0
+#define SFEM_BICGSTAB_STATUS_BAD_RHO 3.0
+#define SFEM_BICGSTAB_STATUS_BAD_OMEGA 4.0
+#define SFEM_BICGSTAB_STATUS_BAD_ALPHA 5.0
+int sfem_bicgstab_scalars(double* scalars, int phase, double maxiter,
+                          double tol, double atol, sfem_stream_t stream);
+/* scalars[slot] += a.b (two != 0: also scalars[slot + 1] += a.a, and the pass
+ * is skipped after a half-step stop)                                          */
+int sfem_bicgstab_dot(const void* a, const void* b, int64_t count,
+                      double* scalars, int slot, int two, int dtype,
+                      sfem_stream_t stream);
+int sfem_bicgstab_update_p(void* p, void* phat, const void* r, const void* v,
+                           const void* dinv, int64_t count, double* scalars,
+                           int dtype, sfem_stream_t stream);
+int sfem_bicgstab_update_s(void* s, void* shat, const void* r, const void* v,
+                           const void* dinv, int64_t count, double* scalars,
+                           int dtype, sfem_stream_t stream);
+int sfem_bicgstab_update_xr(void* x, void* r, const void* phat,
+                            const void* shat, const void* s, const void* t,
+                            const void* r0, int64_t count, double* scalars,
+                            int dtype, sfem_stream_t stream);
+
 /* y = a*x + b*y (plain fused vector update used outside the CG core)         */
 int sfem_axpby(double a, const void* x, double b, void* y, int64_t count,
                int dtype, sfem_stream_t stream);

@@ -15,11 +15,15 @@ from swirl_fem_amd import switches
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SFEM_LIB: another build of the same library (kernel A/B experiments)
 LIB_PATH = switches.get('SFEM_LIB') or os.path.join(_HERE, 'libsfem_hip.so')
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 SFEM_F32, SFEM_F64 = 0, 1
 SFEM_CG_NSCALARS_NAMED = 16
 SFEM_CG_NSCALARS = 80      # 16 named scalars + 64 partial sums of gamma_new
+SFEM_BICGSTAB_NSCALARS = 32
+BICGSTAB_STATUS = {0: 'running', 1: 'converged', 2: 'maxiter',
+                   3: 'breakdown_rho', 4: 'breakdown_omega',
+                   5: 'breakdown_alpha'}
 CG_STATUS = {0: 'running', 1: 'converged', 2: 'maxiter', 3: 'breakdown_pAp',
              4: 'breakdown_gamma'}
 SFEM_DOT_SLOTS = 1024
@@ -54,6 +58,10 @@ class HelmholtzArgs(ctypes.Structure):
       ('facet_table', c_ptr), ('geo_const', c_ptr),
       ('chain_offsets', c_ptr), ('chain_elems', c_ptr), ('num_chains', c_i64),
       ('layered_extent', c_i64), ('dot_slots', c_i64),
+      # advective term (None = off): the folded velocity (E, n, ndim) in slot
+      # order, W b . invjac; index rows / element-local, scalar fields,
+      # coefficients per point only
+      ('beta', c_ptr),
       # variable coefficients (None / 0 = off): kappa (diffusivity k) and
       # sigma (reaction c), device arrays indexed by element id -- (E,) for
       # coef_mode COEF_ELEM, (E, n) in slot order for COEF_POINT; None
@@ -224,6 +232,15 @@ SIGNATURES = {
                                c_ptr],
     'sfem_ell_spmv': [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_i64, c_i64,
                       c_ptr, c_i64, c_i32, c_ptr],
+    'sfem_bicgstab_scalars': [c_ptr, c_i32, c_dbl, c_dbl, c_dbl, c_ptr],
+    'sfem_bicgstab_dot': [c_ptr, c_ptr, c_i64, c_ptr, c_i32, c_i32, c_i32,
+                          c_ptr],
+    'sfem_bicgstab_update_p': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr,
+                               c_i32, c_ptr],
+    'sfem_bicgstab_update_s': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr,
+                               c_i32, c_ptr],
+    'sfem_bicgstab_update_xr': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                c_ptr, c_i64, c_ptr, c_i32, c_ptr],
     'sfem_abi_version': [],
 }
 

@@ -525,7 +525,8 @@ def _helmholtz_args(u, out, enc, part, host, ndim, P, num_elements, num_nodes,
       num_chains=0 if ch is None else ch[0].numel() - 1,
       layered_extent=int(layered_extent), dot_slots=int(dot_slots),
       kappa=_dptr(part.get('kappa')), sigma=_dptr(part.get('sigma')),
-      coef_mode=int(part.get('coef_mode', _lib.COEF_NONE)))
+      coef_mode=int(part.get('coef_mode', _lib.COEF_NONE)),
+      beta=_dptr(part.get('beta')))
 
 
 _CLUSTER_LIMITS = {}
@@ -573,6 +574,9 @@ def helmholtz_kernel_name(real, P, ndim, scalar, geo_mode, part, mass,
   if part.get('cluster') is not None:
     return 'sfem::helmholtz_cluster_kernel<%s, %d, %s, %d, %s>' % (
         real, P, b(scalar), geo_mode, b(mass))
+  if part.get('beta') is not None:
+    return 'sfem::helmholtz_adv_kernel<%s, %d, %d, true, %d>' % (
+        real, P, ndim, geo_mode)
   if part.get('coef_mode'):
     return ('sfem::helmholtz_kernel<%s, %d, %d, true, true, %d, false, %s, '
             '%d>' % (real, P, ndim, geo_mode, b(mass), part['coef_mode']))
@@ -1249,6 +1253,67 @@ def axpby(a, x, b, y):
         float(a), _ptr(x), float(b), _ptr(y), x.numel(), _dtype_code(x),
         _stream(dev)), 'sfem_axpby')
   return y
+
+
+# ----------------------------------------------------------------- BiCGStab
+def bicgstab_scalars(scalars, phase, maxiter, tol, atol):
+  dev = _dev(scalars)
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_bicgstab_scalars(
+        _ptr(scalars), int(phase), float(maxiter), float(tol), float(atol),
+        _stream(dev)), 'sfem_bicgstab_scalars')
+
+
+def bicgstab_dot(a, b, scalars, slot, two=False):
+  """scalars[slot] += a . b (`two`: and scalars[slot + 1] += a . a)."""
+  dev = _dev(a, b, scalars)
+  if a.dtype != b.dtype or a.numel() != b.numel():
+    raise ValueError('bicgstab_dot: operands must share size and dtype')
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_bicgstab_dot(
+        _ptr(a), _ptr(b), a.numel(), _ptr(scalars), int(slot), int(two),
+        _dtype_code(a), _stream(dev)), 'sfem_bicgstab_dot')
+
+
+def _same(name, *ts):
+  first = ts[0]
+  for t in ts:
+    if t is not None and (t.dtype != first.dtype or
+                          t.numel() != first.numel()):
+      raise ValueError(f'{name}: vectors must share size and dtype')
+
+
+def bicgstab_update_p(p, phat, r, v, dinv, scalars):
+  """p = r + beta (p - omega v); phat = dinv p (dinv None: phat unused)."""
+  dev = _dev(p, phat, r, v, dinv, scalars)
+  _same('bicgstab_update_p', p, phat, r, v, dinv)
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_bicgstab_update_p(
+        _ptr(p), _ptr(phat), _ptr(r), _ptr(v), _ptr(dinv), p.numel(),
+        _ptr(scalars), _dtype_code(p), _stream(dev)),
+        'sfem_bicgstab_update_p')
+
+
+def bicgstab_update_s(s, shat, r, v, dinv, scalars):
+  """s = r - alpha v; shat = dinv s; s . s into the scalars."""
+  dev = _dev(s, shat, r, v, dinv, scalars)
+  _same('bicgstab_update_s', s, shat, r, v, dinv)
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_bicgstab_update_s(
+        _ptr(s), _ptr(shat), _ptr(r), _ptr(v), _ptr(dinv), s.numel(),
+        _ptr(scalars), _dtype_code(s), _stream(dev)),
+        'sfem_bicgstab_update_s')
+
+
+def bicgstab_update_xr(x, r, phat, shat, s, t, r0, scalars):
+  """x += alpha phat + omega shat; r = s - omega t; r . r and r0 . r."""
+  dev = _dev(x, r, phat, shat, s, t, r0, scalars)
+  _same('bicgstab_update_xr', x, r, phat, shat, s, t, r0)
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_bicgstab_update_xr(
+        _ptr(x), _ptr(r), _ptr(phat), _ptr(shat), _ptr(s), _ptr(t), _ptr(r0),
+        x.numel(), _ptr(scalars), _dtype_code(x), _stream(dev)),
+        'sfem_bicgstab_update_xr')
 
 
 # ------------------------------------------------------------------- Jacobi

@@ -494,8 +494,26 @@ class FiniteElementSpace:
                                 dirichlet_mask)
 
   # -------------------------------------------------------- fused operators
+  def to_quadrature(self, nodal) -> torch.Tensor:
+    """Nodal values (N,) or (N, d) at the quadrature points: (E, Q^d) or
+    (E, Q^d, d), in the point order of `quad_coords` (gather + the
+    values-only basis kernel).  E.g. a nodal velocity of `StokesSEM` as the
+    `velocity` of `helmholtz_operator`."""
+    u = torch.as_tensor(nodal, dtype=self.dtype, device=self.device)
+    if u.dim() not in (1, 2) or u.shape[0] != self.mesh.num_nodes:
+      raise ValueError(f'expected ({self.mesh.num_nodes},) or '
+                       f'({self.mesh.num_nodes}, d) nodal values, got '
+                       f'{tuple(u.shape)}')
+    scalar = u.dim() == 1
+    loc = (self.mesh.gather(u)[..., None] if scalar
+           else _ops.gather_rows(u.contiguous(), self.mesh.elements))
+    vals = loc if self.is_collocated else self._basis(loc.contiguous(), True,
+                                                      False)[0]
+    return (vals[..., 0] if scalar else vals).contiguous()
+
   def helmholtz_operator(self, dirichlet_mask=None, geometry='auto',
-                         assembly='auto', *, diffusivity=None, reaction=None):
+                         assembly='auto', *, diffusivity=None, reaction=None,
+                         velocity=None):
     """Fused `out = mask * scatter((l0 B + l1 A)_local(gather(u)))`.
 
     `geometry`: 'auto' evaluates the geometric factors of affine / multilinear
@@ -510,8 +528,25 @@ class FiniteElementSpace:
     the quadrature points (`quad_coords` order) or a callable (M, d) ->
     (M,) evaluated there once (`operators.coefficient`); None means 1.  Such
     operators are not cached.
+
+    `velocity` b adds the advective term C_b[i,j] = sum_q W_q phi_i(q) b_q .
+    grad phi_j(q) (plain Galerkin convective form, scaled by neither
+    lambda): a (d,) constant, an (E, d) tensor, an (E, Q^d, d) tensor at the
+    quadrature points (`to_quadrature` makes one from nodal values) or a
+    callable (M, d) -> (M, d) on coordinates (`operators.velocity_field`).
+    The operator is then not symmetric: solve with `linalg.bicgstab`.  There
+    is no stabilisation, so boundary layers have to be resolved.  Not cached.
     """
     from swirl_fem_amd.core import operators
+    if velocity is not None:
+      if (not self.is_collocated and assembly in ('auto', 'atomic') and
+          operators.supports_two_grid(self) is None):
+        return operators.TwoGridHelmholtzOperator.create(
+            self, dirichlet_mask, 'stored' if geometry == 'stored' else 'auto',
+            diffusivity=diffusivity, reaction=reaction, velocity=velocity)
+      return operators.HelmholtzOperator.create(
+          self, dirichlet_mask, geometry, assembly, diffusivity=diffusivity,
+          reaction=reaction, velocity=velocity)
     if diffusivity is not None or reaction is not None:
       if (not self.is_collocated and assembly in ('auto', 'atomic') and
           operators.supports_two_grid(self) is None):

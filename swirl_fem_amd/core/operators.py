@@ -598,15 +598,138 @@ def _check_coefficient_mesh(mesh, assembly):
     raise NotImplementedError('coefficients on a partitioned mesh')
 
 
-def _check_scalar_field(u):
+def _check_scalar_field(u, who='coefficients take'):
   if u.dim() > 1 and u.shape[-1] != 1:
-    raise NotImplementedError('coefficients take scalar fields')
+    raise NotImplementedError(f'{who} scalar fields')
 
 
 def _point_coefficient(c):
   """True if a normal-form coefficient holds per-point values."""
   from swirl_fem_amd import _lib
   return isinstance(c, tuple) and c[0] == _lib.COEF_POINT
+
+
+def velocity_field(value, num_elements, npts, ndim, points, dtype, device):
+  """An advecting velocity b in normal form, an (E, npts, d) tensor at the
+  operator's points (lexicographic, axis 0 slowest), or None.  `value`: a
+  (d,) constant, an (E, d) tensor of per-element values, an (E, npts, d)
+  tensor, or a callable that maps (M, d) coordinates to (M, d) values,
+  evaluated once at `points()` (E, npts, d).  Anything else raises
+  ValueError."""
+  if value is None:
+    return None
+  E, d = num_elements, ndim
+  if callable(value) and not isinstance(value, torch.Tensor):
+    x = points()
+    t = torch.as_tensor(value(x.reshape(-1, x.shape[-1])), dtype=dtype,
+                        device=device)
+    if tuple(t.shape) != (E * npts, d):
+      raise ValueError(f'velocity: the callable returned shape '
+                       f'{tuple(t.shape)}, expected ({E * npts}, {d})')
+    t = t.reshape(E, npts, d)
+  else:
+    try:
+      t = torch.as_tensor(value)
+    except (TypeError, ValueError, RuntimeError):
+      t = torch.zeros((), dtype=torch.bool)
+    if not (t.is_floating_point() or t.dtype in (torch.int32, torch.int64)):
+      raise ValueError('velocity: expected a (d,), (E, d) or (E, Q^d, d) '
+                       'tensor or a callable')
+    t = t.to(dtype=dtype, device=device)
+    if tuple(t.shape) == (d,):
+      t = t[None, None, :].expand(E, npts, d)
+    elif tuple(t.shape) == (E, d):
+      t = t[:, None, :].expand(E, npts, d)
+    elif tuple(t.shape) != (E, npts, d):
+      raise ValueError(f'velocity: shape {tuple(t.shape)}; expected ({d},), '
+                       f'({E}, {d}) or ({E}, {npts}, {d})')
+  if not bool(torch.isfinite(t).all()):
+    raise ValueError('velocity: values must be finite')
+  return t.contiguous()
+
+
+def fold_velocity(fespace, b):
+  """beta[e,q,d] = W[e,q] sum_j b[e,q,j] invjacs[e,q,j,d]: the velocity (E,
+  Q^d, d) at the quadrature points with the geometry folded in, so that the
+  advective term at a point is beta . (reference-space derivatives of u)."""
+  beta = torch.einsum('eqj,eqjd->eqd', b, fespace.invjacs)
+  return (beta * fespace.wdet()[..., None]).contiguous()
+
+
+def _check_velocity_mesh(mesh, assembly):
+  """The refusals of operators with an advective term."""
+  if assembly not in ('auto', 'atomic', 'colored'):
+    raise NotImplementedError(
+        f'a velocity runs on index rows: no {assembly!r} assembly')
+  if mesh.axis_name is not None or mesh.neighbor_plan is not None:
+    raise NotImplementedError('velocity on a partitioned mesh')
+  if mesh._cache.get('replicas', 1) > 1:
+    raise NotImplementedError('velocity on an ensemble (Mesh.replicate)')
+
+
+def _advection_parts(parts, beta, num_elements, npts):
+  """`parts` with the folded velocity attached.  The advective kernels take
+  kappa / sigma per point only: per-element arrays are expanded."""
+  from swirl_fem_amd import _lib
+  out = []
+  for part in parts:
+    part = dict(part, beta=beta)
+    if part.get('coef_mode') == _lib.COEF_ELEM:
+      full = lambda c: None if c is None else (
+          c[:, None].expand(num_elements, npts).contiguous())
+      part.update(kappa=full(part.get('kappa')), sigma=full(part.get('sigma')),
+                  coef_mode=_lib.COEF_POINT)
+    out.append(part)
+  return out
+
+
+def _advection_diagonal(fespace, parts, beta, dq, keep, bmat):
+  """Assembled diagonal (N,) of C_b over the elements of `parts`:
+  C_e[i,i] = sum_q I[q,i] beta[e,q,:] . (D I)[q,i] with I the (Q, P)
+  interpolation (`bmat`; None: collocated) and D the q-grid differentiation
+  matrix `dq`.  Tensor structure: the factor of direction d is I (D I)
+  elementwise along axis d and I^2 along the others.  Computed once per
+  operator with dense contractions, summed per node like the other parts."""
+  mesh = fespace.mesh
+  E, d = mesh.num_elements, mesh.ndim
+  dev, dtype = fespace.device, fespace.dtype
+  dq = np.asarray(dq, dtype=np.float64)
+  i1 = np.eye(dq.shape[0]) if bmat is None else np.asarray(bmat, np.float64)
+  Q = i1.shape[0]
+  S = torch.as_tensor(i1 * i1, dtype=dtype, device=dev)
+  T = torch.as_tensor(i1 * (dq @ i1), dtype=dtype, device=dev)
+  b = beta.reshape((E,) + (Q,) * d + (d,))
+  if d == 2:
+    loc = (torch.einsum('eab,ai,bj->eij', b[..., 0], T, S) +
+           torch.einsum('eab,ai,bj->eij', b[..., 1], S, T))
+  else:
+    loc = (torch.einsum('eabc,ai,bj,ck->eijk', b[..., 0], T, S, S) +
+           torch.einsum('eabc,ai,bj,ck->eijk', b[..., 1], S, T, S) +
+           torch.einsum('eabc,ai,bj,ck->eijk', b[..., 2], S, S, T))
+  loc = loc.reshape(E, -1)
+  if any('elem_list' in part for part in parts):
+    sel = torch.zeros(E, dtype=dtype, device=dev)
+    for part in parts:
+      if 'elem_list' in part:
+        sel[part['elem_list'].to(torch.int64)] = 1
+      else:
+        sel[:] = 1
+    loc = loc * sel[:, None]
+  offsets, slots = mesh.assembly_plan().csr()
+  out = _ops.scatter_csr(loc.contiguous().reshape(-1), offsets, slots,
+                         mesh.num_nodes)
+  return out if keep is None else out * keep
+
+
+class _PlainLinearOperator:
+  """`u -> op.apply(u, lambda0, lambda1)` without a fused `u . A(u)`: what
+  `linalg.bicgstab` takes (it needs no p . Ap)."""
+
+  def __init__(self, op, lambda0, lambda1):
+    self.op, self.lambda0, self.lambda1 = op, lambda0, lambda1
+
+  def __call__(self, u):
+    return self.op.apply(u, self.lambda0, self.lambda1)
 
 
 @dataclasses.dataclass(eq=False)
@@ -631,11 +754,16 @@ class HelmholtzOperator:
   coefs: tuple | None = None
   coef_source: tuple = (None, None)
   _geo_parts: list | None = None      # the launches without coefficients
+  # advective term C_b: the velocity in normal form (`velocity_field`) and
+  # with the geometry folded in (`fold_velocity`), or None
+  velocity: torch.Tensor | None = None
+  beta: torch.Tensor | None = None
+  _diag_adv: torch.Tensor | None = None   # assembled diag C_b, `diagonal`
 
   @classmethod
   def create(cls, fespace, dirichlet_mask=None, geometry='auto',
-             assembly='auto', *, diffusivity=None,
-             reaction=None) -> 'HelmholtzOperator':
+             assembly='auto', *, diffusivity=None, reaction=None,
+             velocity=None) -> 'HelmholtzOperator':
     """geometry: 'auto' (per element: affine / multilinear / stored factors),
     'multilinear' (no affine shortcut) or 'stored' (6 factors per point for
     every element, the general-geometry path).
@@ -652,12 +780,22 @@ class HelmholtzOperator:
     diffusivity k, reaction c (`coefficient`): the operator becomes
     lambda0 B_c + lambda1 A_k.  With either one it runs on index rows
     ('atomic' or 'colored' assembly, no facet tables or layers); scalar
-    fields on one unpartitioned mesh only."""
+    fields on one unpartitioned mesh only.
+
+    velocity b (`velocity_field`): adds the plain Galerkin convective form
+    C_b[i,j] = sum_q W_q phi_i(q) b_q . grad phi_j(q), not scaled by either
+    lambda: `apply` computes (lambda0 B_c + lambda1 A_k + C_b) u.  The
+    operator is then not symmetric (`linalg.bicgstab`); it runs on index rows
+    like one with coefficients.  No stabilisation: the Galerkin form needs
+    the boundary layers of an advection-dominated problem to be resolved by
+    the mesh."""
     why = supports_fused(fespace)
     if why is not None:
       raise NotImplementedError(f'fused Helmholtz kernel unavailable: {why}')
     if geometry not in ('auto', 'multilinear', 'stored'):
       raise ValueError(f'unknown geometry mode {geometry!r}')
+    if velocity is not None:
+      _check_velocity_mesh(fespace.mesh, assembly)
     if assembly not in ('auto', 'cluster', 'atomic', 'colored'):
       raise ValueError(f'unknown assembly mode {assembly!r}')
     coefs = None
@@ -670,6 +808,15 @@ class HelmholtzOperator:
                            points, fespace.dtype, fespace.device),
                coefficient(reaction, 'reaction', mesh.num_elements, npts,
                            points, fespace.dtype, fespace.device))
+      if assembly == 'auto':
+        assembly = 'atomic'
+    beta = None
+    if velocity is not None:
+      mesh = fespace.mesh
+      velocity = velocity_field(
+          velocity, mesh.num_elements, mesh.num_nodes_per_element, mesh.ndim,
+          mesh.element_coords, fespace.dtype, fespace.device)
+      beta = fold_velocity(fespace, velocity)
       if assembly == 'auto':
         assembly = 'atomic'
     requested = assembly
@@ -718,6 +865,8 @@ class HelmholtzOperator:
     if coefs is not None:
       parts = _coefficient_parts(parts, *coefs, E, mesh.num_nodes_per_element,
                                  mesh.ndim)
+    if beta is not None:
+      parts = _advection_parts(parts, beta, E, mesh.num_nodes_per_element)
     plan = mesh.assembly_plan()
     mask = None
     if dirichlet_mask is not None:
@@ -759,6 +908,7 @@ class HelmholtzOperator:
         assembly = 'atomic'
 
     if (assembly == 'atomic' and mesh.ndim == 3 and coefs is None and
+        beta is None and
         mesh.gridpoints_1d.num_points <= 8 and      # one wave per element
         switches.get('SFEM_SORTED_SCATTER') != '0'):
       # 3D: most slots of an element are shared; issue their atomics in node
@@ -768,6 +918,7 @@ class HelmholtzOperator:
         parts = [dict(part, shared_order=so) for part in parts]
     facet_parts = None
     if (assembly == 'atomic' and mesh.ndim == 3 and coefs is None and
+        beta is None and
         mesh.gridpoints_1d.num_points in FACET_P and
         switches.get('SFEM_FACET') != '0'):
       facet_parts = _facet_parts(fespace, parts, mask, plan.multiplicity, coef)
@@ -780,8 +931,9 @@ class HelmholtzOperator:
                num_curved=counts[_GEO_POINT], facet_parts=facet_parts,
                keep=None if mask is None else (mask == 0).to(fespace.dtype),
                coefs=coefs, coef_source=(diffusivity, reaction),
-               _geo_parts=geo_parts,
-               _layer_plan=False if coefs is not None else None)
+               _geo_parts=geo_parts, velocity=velocity, beta=beta,
+               _layer_plan=(False if coefs is not None or beta is not None
+                            else None))
 
   def split(self, element_mask):
     """Two operators over the elements inside / outside `element_mask` (E,)
@@ -828,7 +980,7 @@ class HelmholtzOperator:
       # (each half covers part of the mesh only: no layer plan)
       halves.append(dataclasses.replace(self, parts=parts, facet_parts=facet,
                                         _vector_parts=None, _layer_plan=False,
-                                        _diag=None))
+                                        _diag=None, _diag_adv=None))
     return tuple(halves)
 
   def apply(self, u, lambda0=0.0, lambda1=1.0, out=None, *, zero=True,
@@ -847,6 +999,10 @@ class HelmholtzOperator:
     if self.coefs is not None:
       _check_scalar_field(u)
       lambda0, lambda1 = _scaled(self.coefs, lambda0, lambda1)
+    if self.beta is not None:
+      _check_scalar_field(u, 'a velocity takes')
+      if dot_out is not None:
+        raise NotImplementedError('dot_out of an operator with a velocity')
     u = u.to(self.fespace.dtype)
     if not (u.is_contiguous() or _ops.is_component_major(u)):
       u = u.contiguous()
@@ -952,8 +1108,15 @@ class HelmholtzOperator:
       self._diag = _assembled_diagonal(self.fespace, self.parts, self.host,
                                        self.keep, None)
     lambda0, lambda1 = _scaled(self.coefs, lambda0, lambda1)
-    return _combine_diagonal(self._diag, lambda0, lambda1, assembled,
-                             self.fespace.mesh)
+    d = _combine_diagonal(self._diag, lambda0, lambda1, assembled,
+                          self.fespace.mesh)
+    if self.beta is not None:      # + diag C_b, which no lambda scales
+      if self._diag_adv is None:
+        self._diag_adv = _advection_diagonal(
+            self.fespace, self.parts, self.beta, self.host['dmat'], self.keep,
+            None)
+      d = d + self._diag_adv
+    return d
 
   def point_weights(self):
     """W = w detJ (E, n) at the operator's points, without coefficients (the
@@ -973,13 +1136,19 @@ class HelmholtzOperator:
       if u_local.dim() == 3 and u_local.shape[-1] != 1:
         raise NotImplementedError('coefficients take scalar fields')
       lambda0, lambda1 = _scaled(self.coefs, lambda0, lambda1)
+    if self.beta is not None and u_local.dim() == 3 and u_local.shape[-1] != 1:
+      raise NotImplementedError('a velocity takes scalar fields')
     return _ops.helmholtz_local(
         u_local.to(self.fespace.dtype), self.parts, self.host, mesh.ndim,
         mesh.gridpoints_1d.num_points, lambda0, lambda1)
 
   def linear_operator(self, lambda0=0.0, lambda1=1.0):
     """`u -> apply(u, lambda0, lambda1)` as an object that `cg` recognises:
-    it also offers `apply_with_dot(u, partials)` (fused p.Ap)."""
+    it also offers `apply_with_dot(u, partials)` (fused p.Ap).  With a
+    velocity the operator is not symmetric and goes to `linalg.bicgstab`,
+    which needs no p.Ap: a plain callable."""
+    if self.beta is not None:
+      return _PlainLinearOperator(self, lambda0, lambda1)
     return FusedLinearOperator(self, lambda0, lambda1)
 
   def bytes_per_apply(self, lambda0=0.0, ncomp=1, layered=False):
@@ -1021,6 +1190,8 @@ class HelmholtzOperator:
       else:
         geo = 24 * s
       geo += _coefficient_bytes(part, s, n, lambda0)
+      if part.get('beta') is not None:     # the folded velocity
+        geo += s * n * mesh.ndim
       total += count * (conn + geo)
     return total
 
@@ -1672,12 +1843,19 @@ class TwoGridHelmholtzOperator:
   coefs: tuple | None = None
   coef_source: tuple = (None, None)
   _geo_parts: list | None = None
+  # advective term, as in `HelmholtzOperator` (at the Q^d quadrature points)
+  velocity: torch.Tensor | None = None
+  beta: torch.Tensor | None = None
+  _diag_adv: torch.Tensor | None = None
 
   @classmethod
   def create(cls, fespace, dirichlet_mask=None, geometry='auto', *,
-             diffusivity=None, reaction=None) -> 'TwoGridHelmholtzOperator':
-    """`diffusivity`, `reaction`: see `HelmholtzOperator.create`; per-point
-    values and callables live on the Q^d quadrature points."""
+             diffusivity=None, reaction=None,
+             velocity=None) -> 'TwoGridHelmholtzOperator':
+    """`diffusivity`, `reaction`, `velocity`: see `HelmholtzOperator.create`;
+    per-point values and callables live on the Q^d quadrature points.  The
+    advective term is I^T C_q I with C_q the collocated term of the q-grid:
+    the q-grid kernel adds beta . (derivatives of the interpolant)."""
     why = supports_two_grid(fespace)
     if why is not None:
       raise NotImplementedError(f'two-grid Helmholtz unavailable: {why}')
@@ -1698,6 +1876,16 @@ class TwoGridHelmholtzOperator:
                            fespace.dtype, dev),
                coefficient(reaction, 'reaction', E, nq, points,
                            fespace.dtype, dev))
+    beta = None
+    if velocity is not None:
+      _check_velocity_mesh(mesh, 'atomic')
+      nq = fespace.quadrature.num_points ** mesh.ndim
+      points = lambda: (mesh.element_coords() if fespace.is_collocated else
+                        fespace._basis(mesh.element_coords(), True,
+                                       False)[0])
+      velocity = velocity_field(velocity, E, nq, mesh.ndim, points,
+                                fespace.dtype, dev)
+      beta = fold_velocity(fespace, velocity)
     w = torch.as_tensor(fespace.quadrature.weights_nd(mesh.ndim),
                         dtype=fespace.dtype, device=dev)
     from swirl_fem_amd.core.interpolation import NodeType
@@ -1743,9 +1931,12 @@ class TwoGridHelmholtzOperator:
       parts = _coefficient_parts(parts, *coefs, E,
                                  fespace.quadrature.num_points ** mesh.ndim,
                                  mesh.ndim)
+    if beta is not None:
+      parts = _advection_parts(parts, beta, E,
+                               fespace.quadrature.num_points ** mesh.ndim)
     return cls(fespace=fespace, parts=parts, host=host, mask=mask,
                coefs=coefs, coef_source=(diffusivity, reaction),
-               _geo_parts=geo_parts)
+               _geo_parts=geo_parts, velocity=velocity, beta=beta)
 
   def point_weights(self):
     """W = w detJ (E, Q^d) at the quadrature points, without coefficients."""
@@ -1769,6 +1960,8 @@ class TwoGridHelmholtzOperator:
       if nc != 1:
         raise NotImplementedError('coefficients take scalar fields')
       lambda0, lambda1 = _scaled(self.coefs, lambda0, lambda1)
+    if self.beta is not None and nc != 1:
+      raise NotImplementedError('a velocity takes scalar fields')
     q = fes.quadrature.num_points
     uq = u3 if fes.is_collocated else fes._basis(u3, True, False)[0]
     rq = _ops.helmholtz_local(uq.contiguous(), self.parts, self.host,
@@ -1807,14 +2000,22 @@ class TwoGridHelmholtzOperator:
     """The assembled diagonal of `apply(u, lambda0, lambda1)` (N,), see
     `HelmholtzOperator.diagonal`: the element diagonals of I^T H_q I with
     I the (Q, P) interpolation and D_q I its derivative."""
+    interp = self.fespace.interpolator
     if self._diag is None:
-      interp = self.fespace.interpolator
       bmat = np.asarray(interp._interpolation_matrix_1d(), dtype=np.float64)
       self._diag = _assembled_diagonal(self.fespace, self.parts, self.host,
                                        self.mask, bmat)
     lambda0, lambda1 = _scaled(self.coefs, lambda0, lambda1)
-    return _combine_diagonal(self._diag, lambda0, lambda1, assembled,
-                             self.fespace.mesh)
+    d = _combine_diagonal(self._diag, lambda0, lambda1, assembled,
+                          self.fespace.mesh)
+    if self.beta is not None:
+      if self._diag_adv is None:
+        bmat = np.asarray(interp._interpolation_matrix_1d(), dtype=np.float64)
+        self._diag_adv = _advection_diagonal(
+            self.fespace, self.parts, self.beta, self.host['dmat'], self.mask,
+            bmat)
+      d = d + self._diag_adv
+    return d
 
 
 # ---------------------------------------------------------------------------

@@ -5,6 +5,7 @@
 #include "sfem_helmholtz_cluster.h"
 #include "sfem_helmholtz_mfma.h"
 #include "sfem_helmholtz_facet.h"
+#include "sfem_helmholtz_adv.h"
 
 namespace sfem {
 
@@ -249,6 +250,7 @@ struct HelmholtzCall {
   const void* kappa = nullptr;
   const void* sigma = nullptr;
   int coef_mode = 0;
+  const void* beta = nullptr;
 };
 
 template <typename T>
@@ -267,6 +269,18 @@ static int run_helmholtz(const HelmholtzCall& c, hipStream_t stream) {
   prm.colored = c.colored;
   prm.shared_order = c.shared_order;
   prm.shared_stride = c.shared_stride;
+  if (c.beta) {
+    // advective term (checked by check_advection): its own kernels
+    HelmholtzAdvParams<T> ap{};
+    static_cast<HelmholtzParams<T>&>(ap) = prm;
+    ap.dot_out = nullptr;
+    ap.shared_order = nullptr;
+    ap.kappa = (const T*)c.kappa;
+    ap.sigma = (const T*)c.sigma;
+    ap.beta = (const T*)c.beta;
+    if (c.ndim == 3) return dispatch_helmholtz_adv<T, 3>(ap, c.P, c.gs, stream);
+    return dispatch_helmholtz_adv<T, 2>(ap, c.P, c.gs, stream);
+  }
   if (c.coef_mode != COEF_NONE) {
     HelmholtzCoefParams<T> cp{};
     static_cast<HelmholtzParams<T>&>(cp) = prm;
@@ -355,6 +369,31 @@ static int check_coefficients(const char* who, const sfem_helmholtz_args* a) {
                    !a->layered_extent,
                "%s: coefficients run on index rows (no cluster, facet, "
                "layered or sorted assembly)", who);
+  return SFEM_OK;
+}
+
+// The advective launches (helmholtz_adv_kernel): scalar fields on index rows
+// or element-local, any stored / affine / multilinear geometry, coefficients
+// per point only.  Everything else is out of scope: SFEM_EUNSUPPORTED.
+static int check_advection(const char* who, const sfem_helmholtz_args* a) {
+  if (!a->beta) return SFEM_OK;
+  const char* why = nullptr;
+  if (a->ncomp != 1) why = "a vector field";
+  else if (a->ndim != 2 && a->ndim != 3) why = "ndim other than 2 or 3";
+  else if (a->geo_mode == SFEM_GEO_BOX) why = "SFEM_GEO_BOX";
+  else if (a->cluster_elems || a->facet_table || a->shared_order ||
+           a->layered_extent || a->chain_offsets)
+    why = "cluster, facet, chain, layered or sorted assembly";
+  else if (a->dot_out) why = "dot_out";
+  else if (a->coef_mode == SFEM_COEF_ELEM)
+    why = "per-element coefficients (expand them per point)";
+  else if (a->coef_mode != SFEM_COEF_NONE && a->geo_mode == SFEM_GEO_POINT)
+    why = "coefficient arrays on stored factors (fold them in)";
+  else if (a->node_stride > 1) why = "a strided field";
+  if (why) {
+    set_error("%s: the advective term (beta) does not take %s", who, why);
+    return SFEM_EUNSUPPORTED;
+  }
   return SFEM_OK;
 }
 
@@ -491,6 +530,8 @@ int sfem_helmholtz_apply(const sfem_helmholtz_args* a, sfem_stream_t stream) {
   int rc = check_geometry("sfem_helmholtz_apply", a->geo_mode, a->geo,
                           a->geo_elem, a->weights, a->nodes);
   if (rc) return rc;
+  rc = check_advection("sfem_helmholtz_apply", a);
+  if (rc) return rc;
   rc = check_coefficients("sfem_helmholtz_apply", a);
   if (rc) return rc;
   const int64_t work = a->elem_list ? a->num_listed : a->num_elements;
@@ -505,6 +546,7 @@ int sfem_helmholtz_apply(const sfem_helmholtz_args* a, sfem_stream_t stream) {
   c.kappa = a->kappa;
   c.sigma = a->sigma;
   c.coef_mode = a->coef_mode;
+  c.beta = a->beta;
   SFEM_REQUIRE(!a->shared_order || (a->shared_stride > 0 &&
                                     a->shared_stride <= 0xFFFF),
                "sfem_helmholtz_apply: bad shared_stride");
@@ -676,6 +718,8 @@ int sfem_helmholtz_local(const sfem_helmholtz_args* a, sfem_stream_t stream) {
   int rc = check_geometry("sfem_helmholtz_local", a->geo_mode, a->geo,
                           a->geo_elem, a->weights, a->nodes);
   if (rc) return rc;
+  rc = check_advection("sfem_helmholtz_local", a);
+  if (rc) return rc;
   rc = check_coefficients("sfem_helmholtz_local", a);
   if (rc) return rc;
   const int64_t work = a->elem_list ? a->num_listed : a->num_elements;
@@ -689,6 +733,7 @@ int sfem_helmholtz_local(const sfem_helmholtz_args* a, sfem_stream_t stream) {
   c.kappa = a->kappa;
   c.sigma = a->sigma;
   c.coef_mode = a->coef_mode;
+  c.beta = a->beta;
   if (a->dtype == SFEM_F64) return run_helmholtz<double>(c, as_stream(stream));
   return run_helmholtz<float>(c, as_stream(stream));
 }

@@ -1,0 +1,300 @@
+// Helmholtz operator with an advective term, index rows / element-local:
+//
+//   out = mask * scatter( (lambda0 B_c + lambda1 A_k + C_b)_local(g) ),
+//   C_b[i,j] = sum_q W_q phi_i(q) b_q . grad phi_j(q)
+//
+// At a collocated point q the advective term is a dot product of the
+// reference-space derivatives of u (the lines helmholtz_kernel computes for the
+// stiffness term anyway) with the folded velocity
+//   beta[e,q,d] = W[e,q] sum_j b[e,q,j] invjac[e,q,j,d],
+// added to the pointwise (mass-like) contribution of q.  So the term does not
+// depend on the geometry kind and costs DIM extra loads per point and no extra
+// derivative line.
+//
+// helmholtz_adv_kernel is a sibling of helmholtz_kernel (sfem_helmholtz.h): the
+// same lane mapping (one line of P nodes per lane, one element per wave or
+// workgroup), the same LDS tensor pair, the same device functions (ElemGeom,
+// line_apply*, HelmholtzTile).  It is kept apart so that the constant- and
+// variable-coefficient instantiations compile from code this file never
+// touches.  Scalar fields, slot-order scatter; kappa / sigma per point or null
+// (one form bounds the number of instantiations: Python expands scalars and
+// per-element values).  The derivative lines are always computed (C_b needs
+// them when lambda1 = 0 as well); lambda0 is tested at run time.
+#pragma once
+#include "sfem_helmholtz.h"
+
+namespace sfem {
+
+template <typename T>
+struct HelmholtzAdvParams : HelmholtzParams<T> {
+  const T* kappa;        // diffusivity (E, N) slot order; null = 1
+  const T* sigma;        // reaction (E, N); null = 1
+  const T* beta;         // folded velocity (E, N, DIM), slot order
+};
+
+template <typename T, int P, int DIM, bool GS, int GM>
+__global__ void __launch_bounds__((HelmholtzTile<T, P, DIM>::BLOCK),
+                                  (HelmholtzTile<T, P, DIM>::MINW))
+helmholtz_adv_kernel(HelmholtzAdvParams<T> prm, DMat<T, P> dm) {
+  using PRM = HelmholtzAdvParams<T>;
+  using Tile = HelmholtzTile<T, P, DIM, true>;
+  constexpr int TPE = Tile::TPE, SA = Tile::SA, SB = Tile::SB;
+  constexpr int EPB = Tile::EPB, W = Tile::ELEM_WORDS;
+  constexpr int N = DIM == 3 ? P * P * P : P * P;        // nodes per element
+  __shared__ T lds[2 * EPB * W];
+
+  const int tid = threadIdx.x;
+  const int el = tid / TPE;                 // element within the workgroup
+  const int t = tid - el * TPE;             // lane within the element
+  const int i = DIM == 3 ? t / P : 0;
+  const int j = DIM == 3 ? t - i * P : t;
+  const bool lane_ok = el < EPB;            // tail lanes of a padded block
+  const int64_t work = (int64_t)blockIdx.x * EPB + (lane_ok ? el : 0);
+  const bool active = lane_ok && work < prm.num_elements;
+  const int64_t e =
+      prm.elem_list ? (active ? (int64_t)prm.elem_list[work] : 0) : work;
+
+  T* s0 = lds + (lane_ok ? el : 0) * 2 * W;    // becomes the axis-1 result
+  T* s1 = s0 + W;                              // becomes the axis-2 result
+  const DMat<T, P>& dmat = dm;
+  // fp32, P >= 9: matrix entries from the kernarg segment, as the parent does
+#if SFEM_DMAT_MEM
+#define SFEM_ADV_LINE_APPLY(TR, X, Y)                                         \
+  do {                                                                        \
+    if constexpr (P >= 9 && sizeof(T) == 4)                                   \
+      line_apply_mem<T, P, TR>(                                               \
+          (const SFEM_CONSTANT_AS DMat<T, P>*)((                              \
+              const SFEM_CONSTANT_AS char*)                                   \
+                  __builtin_amdgcn_kernarg_segment_ptr() +                    \
+              sizeof(PRM)),                                                   \
+          X, Y);                                                              \
+    else                                                                      \
+      line_apply<T, P, TR>(dmat, X, Y);                                       \
+  } while (0)
+#else
+#define SFEM_ADV_LINE_APPLY(TR, X, Y) line_apply<T, P, TR>(dmat, X, Y)
+#endif
+  const int64_t ns = prm.node_stride;
+  const bool has_mass = prm.lambda0 != T(0);
+
+  ElemGeom<T, P, DIM, GM> geom;
+#if SFEM_KERNARG_PICK
+  static_assert(sizeof(PRM) % alignof(DMat<T, P>) == 0, "");
+  geom.template init<true>(prm, dm, e, active, i, j, t,
+                           kernarg_dmat<T, P>(sizeof(PRM)));
+#else
+  geom.init(prm, dm, e, active, i, j, t);
+#endif
+  const uint32_t slot_off = (uint32_t)t;
+
+  // per-point arrays of this element, read in the plane layout of the stored
+  // factors: lane t of slice a reads point a * TPE + t (coalesced); beta holds
+  // DIM consecutive reals per point, so a wave reads one contiguous strip
+  const T* kpt = prm.kappa ? prm.kappa + e * N : nullptr;
+  const T* cpt = prm.sigma ? prm.sigma + e * N : nullptr;
+  const T* bpt = prm.beta + e * N * DIM;
+
+  uint32_t enc[P];
+  if (GS) {
+    const int32_t* enc0 = prm.enc + e * N;
+#pragma unroll
+    for (int a = 0; a < P; ++a)
+      enc[a] = active ? (uint32_t)__builtin_nontemporal_load(
+                            &enc0[slot_off + a * TPE])
+                      : (uint32_t)SFEM_IDX_PAD;
+  }
+  const T* ul0 = GS ? nullptr : prm.u + e * N * ns;
+  T* ol0 = GS ? nullptr : prm.out + e * N * ns;
+  const T* ug = prm.u;
+  T* og = prm.out;
+
+  T ua[P], acc[P];
+#pragma unroll
+  for (int a = 0; a < P; ++a) {
+    if (GS) {
+      const uint32_t id = enc[a] & SFEM_IDX_MASK;
+      ua[a] = id == SFEM_IDX_PAD ? T(0) : ug[(int64_t)id * ns];
+    } else {
+      ua[a] = active ? ul0[(int64_t)(slot_off + a * TPE) * ns] : T(0);
+    }
+  }
+  T d0[P];   // derivative along axis 0 at (a, i, j)
+  SFEM_ADV_LINE_APPLY(false, ua, d0);
+  if (lane_ok) {
+#pragma unroll
+    for (int a = 0; a < P; ++a) {
+      s0[a * SA + i * SB + j] = ua[a];
+      if (DIM == 3) s1[a * SA + i * SB + j] = ua[a];
+    }
+  }
+  __syncthreads();
+  if (lane_ok) {  // last axis: lane owns the line [i, j, *] (3D) / [j, *]
+    T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
+    T x[P], y[P];
+#pragma unroll
+    for (int m = 0; m < P; ++m) x[m] = line[m];
+    SFEM_ADV_LINE_APPLY(false, x, y);
+#pragma unroll
+    for (int m = 0; m < P; ++m) line[m] = y[m];
+  }
+  if (DIM == 3 && lane_ok) {  // middle axis: lane owns the line [i, *, j]
+    T* line = s0 + i * SA + j;
+    T x[P], y[P];
+#pragma unroll
+    for (int m = 0; m < P; ++m) x[m] = line[m * SB];
+    SFEM_ADV_LINE_APPLY(false, x, y);
+#pragma unroll
+    for (int m = 0; m < P; ++m) line[m * SB] = y[m];
+  }
+  __syncthreads();
+  // pointwise: the advective and mass terms go to acc, w = k G * (reference
+  // gradient) replaces the gradient
+  T w0[P];
+#pragma unroll
+  for (int a = 0; a < P; ++a) { w0[a] = T(0); acc[a] = T(0); }
+  if (active) {
+#pragma unroll
+    for (int a = 0; a < P; ++a) {
+      const int o = a * SA + i * SB + j;
+      const uint32_t q = slot_off + a * TPE;
+      const T g0 = d0[a], g1 = s0[o];
+      [[maybe_unused]] T g2 = T(0);
+      if constexpr (DIM == 3) g2 = s1[o];
+      T adv = bpt[q * DIM] * g0 + bpt[q * DIM + 1] * g1;
+      if constexpr (DIM == 3) adv += bpt[q * DIM + 2] * g2;
+      const T kq = kpt ? kpt[q] : T(1);
+      T Wm;
+      if constexpr (GM == GEO_MULTILINEAR && DIM == 3) {
+        T o0, o1, o2;
+        geom.apply_multilinear3(dm, a, has_mass, g0, g1, g2, o0, o1, o2, Wm);
+        w0[a] = kq * o0; s0[o] = kq * o1; s1[o] = kq * o2;
+      } else {
+        T G[6];
+        geom.factors(dm, a, true, has_mass, G, Wm);
+        if constexpr (DIM == 3) {
+          w0[a] = kq * (G[0] * g0 + G[1] * g1 + G[2] * g2);
+          s0[o] = kq * (G[1] * g0 + G[3] * g1 + G[4] * g2);
+          s1[o] = kq * (G[2] * g0 + G[4] * g1 + G[5] * g2);
+        } else {
+          w0[a] = kq * (G[0] * g0 + G[1] * g1);
+          s0[o] = kq * (G[1] * g0 + G[3] * g1);
+        }
+      }
+      if (has_mass) {
+        if (cpt) Wm *= cpt[q];
+        adv += prm.lambda0 * Wm * ua[a];
+      }
+      acc[a] = adv;
+    }
+  }
+  __syncthreads();
+  if (lane_ok) {  // transposed derivative along the last axis, in place
+    T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
+    T x[P], y[P];
+#pragma unroll
+    for (int m = 0; m < P; ++m) x[m] = line[m];
+    SFEM_ADV_LINE_APPLY(true, x, y);
+#pragma unroll
+    for (int m = 0; m < P; ++m) line[m] = y[m];
+  }
+  if (DIM == 3 && lane_ok) {
+    T* line = s0 + i * SA + j;
+    T x[P], y[P];
+#pragma unroll
+    for (int m = 0; m < P; ++m) x[m] = line[m * SB];
+    SFEM_ADV_LINE_APPLY(true, x, y);
+#pragma unroll
+    for (int m = 0; m < P; ++m) line[m * SB] = y[m];
+  }
+  T dt0[P];
+  SFEM_ADV_LINE_APPLY(true, w0, dt0);
+  __syncthreads();
+  if (lane_ok) {
+#pragma unroll
+    for (int a = 0; a < P; ++a) {
+      const int o = a * SA + i * SB + j;
+      T v = dt0[a] + s0[o];
+      if (DIM == 3) v += s1[o];
+      acc[a] += prm.lambda1 * v;
+    }
+  }
+  // direct-stiffness summation in slot order
+#pragma unroll
+  for (int a = 0; a < P; ++a) {
+    if (GS) {
+      const uint32_t ea = enc[a];
+      const uint32_t id = ea & SFEM_IDX_MASK;
+      if (id != SFEM_IDX_PAD) {
+        T* dst = og + (int64_t)id * ns;
+        const bool dirichlet = ea & SFEM_IDX_DIRICHLET;
+        if (ea & SFEM_IDX_SHARED) {
+          if (!dirichlet) {
+            if (prm.colored) *dst = *dst + acc[a];
+            else unsafeAtomicAdd(dst, acc[a]);
+          }
+        } else {
+          *dst = dirichlet ? T(0) : acc[a];
+        }
+      }
+    } else if (active) {
+      ol0[(int64_t)(slot_off + a * TPE) * ns] = acc[a];
+    }
+  }
+#undef SFEM_ADV_LINE_APPLY
+}
+
+template <typename T, int P, int DIM, bool GS>
+int launch_helmholtz_adv(const HelmholtzAdvParams<T>& prm, hipStream_t stream) {
+  using Tile = HelmholtzTile<T, P, DIM>;
+  const int64_t groups = (prm.num_elements + Tile::EPB - 1) / Tile::EPB;
+  if (groups > 0x7fffffff) {
+    set_error("helmholtz: too many workgroups (%lld)", (long long)groups);
+    return SFEM_EINVAL;
+  }
+  const DMat<T, P> dm =
+      make_dmat<T, P>(prm.dmat_host, prm.weights_host, prm.nodes_host);
+  const dim3 grid((unsigned)groups), block(Tile::BLOCK);
+#define SFEM_LAUNCH_ADV(GMV)                                                  \
+  hipLaunchKernelGGL((helmholtz_adv_kernel<T, P, DIM, GS, GMV>), grid, block, \
+                     0, stream, prm, dm)
+  switch (prm.geo_mode) {
+    case GEO_POINT: SFEM_LAUNCH_ADV(GEO_POINT); break;
+    case GEO_AFFINE: SFEM_LAUNCH_ADV(GEO_AFFINE); break;
+    default: SFEM_LAUNCH_ADV(GEO_MULTILINEAR); break;
+  }
+#undef SFEM_LAUNCH_ADV
+  SFEM_LAUNCH_CHECK();
+  return SFEM_OK;
+}
+
+// Defined once per (dtype, ndim) translation unit, P = 2..12.
+template <typename T, int DIM>
+int dispatch_helmholtz_adv(const HelmholtzAdvParams<T>& prm, int P, bool gs,
+                           hipStream_t stream);
+
+#define SFEM_HELMHOLTZ_ADV_CASE(PP)                                         \
+  case PP:                                                                  \
+    return gs ? launch_helmholtz_adv<T, PP, DIM, true>(prm, stream)         \
+              : launch_helmholtz_adv<T, PP, DIM, false>(prm, stream);
+
+#define SFEM_DEFINE_HELMHOLTZ_ADV_DISPATCH(TYPE, DIMV)                      \
+  template <>                                                               \
+  int dispatch_helmholtz_adv<TYPE, DIMV>(                                   \
+      const HelmholtzAdvParams<TYPE>& prm, int P, bool gs,                  \
+      hipStream_t stream) {                                                 \
+    using T = TYPE;                                                         \
+    constexpr int DIM = DIMV;                                               \
+    switch (P) {                                                            \
+      SFEM_HELMHOLTZ_ADV_CASE(2) SFEM_HELMHOLTZ_ADV_CASE(3)                 \
+      SFEM_HELMHOLTZ_ADV_CASE(4) SFEM_HELMHOLTZ_ADV_CASE(5)                 \
+      SFEM_HELMHOLTZ_ADV_CASE(6) SFEM_HELMHOLTZ_ADV_CASE(7)                 \
+      SFEM_HELMHOLTZ_ADV_CASE(8) SFEM_HELMHOLTZ_ADV_CASE(9)                 \
+      SFEM_HELMHOLTZ_ADV_CASE(10) SFEM_HELMHOLTZ_ADV_CASE(11)               \
+      SFEM_HELMHOLTZ_ADV_CASE(12)                                           \
+      default:                                                              \
+        set_error("helmholtz: P=%d outside the compiled range 2..12", P);   \
+        return SFEM_EUNSUPPORTED;                                           \
+    }                                                                       \
+  }
+
+}  // namespace sfem

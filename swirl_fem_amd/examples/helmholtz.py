@@ -1,13 +1,20 @@
 """Helmholtz / Poisson solves with inhomogeneous Dirichlet, Neumann and Robin
-data and variable coefficients.
+data, variable coefficients and an optional advective term.
 
-    lambda0 c u - lambda1 div(k grad u) = f   in the mesh,
+    lambda0 c u + b . grad u - lambda1 div(k grad u) = f   in the mesh,
     u = g_D on Dirichlet groups,   k du/dn = g_N on Neumann groups,
     k du/dn + alpha u = g_R on Robin groups (alpha >= 0),
     k du/dn = 0 on the rest of the boundary,
 
 with the diffusivity k > 0 and the reaction coefficient c >= 0 (both 1 by
-default: then the equation is lambda0 u - lambda1 lap u = f).
+default: then the equation is lambda0 u - lambda1 lap u = f) and the
+advecting velocity b (default: none).  Only the diffusive term is integrated
+by parts, so Neumann and Robin data stay the flux k du/dn with or without b.
+The advective term is the plain Galerkin convective form
+C_b[i,j] = sum_q W_q phi_i(q) b_q . grad phi_j(q) without stabilisation: the
+mesh has to resolve the boundary layers of an advection-dominated problem.
+With a velocity the system is not symmetric and is solved by right-
+preconditioned BiCGStab (`linalg/bicgstab.py`) instead of CG.
 
 The boundary data the reference's `solve_poisson` docstring promises and
 leaves as a TODO (swirl_fem/examples/poisson.py:79-90); `solve_poisson`
@@ -50,6 +57,7 @@ from swirl_fem_amd.core.interpolation import Quadrature1D
 from swirl_fem_amd.core.mesh import Mesh
 from swirl_fem_amd.examples.poisson import BCType
 from swirl_fem_amd.examples.poisson import BCValue
+from swirl_fem_amd.linalg.bicgstab import bicgstab
 from swirl_fem_amd.linalg.cg import cg
 
 # pylint: disable=invalid-name
@@ -74,9 +82,17 @@ def solve_helmholtz(mesh: Mesh, forcing,
                     *, lambda0: float = 0.0, lambda1: float = 1.0,
                     rtol: float = 1e-5, atol: float = 0.,
                     return_info: bool = False, preconditioner=None,
-                    diffusivity=None, reaction=None):
-  """Solves `lambda0 c u - lambda1 div(k grad u) = forcing` with boundary
-  data.
+                    diffusivity=None, reaction=None, velocity=None):
+  """Solves `lambda0 c u + b . grad u - lambda1 div(k grad u) = forcing` with
+  boundary data.
+
+  `velocity` b: None (no advective term: the symmetric solve by CG), a `(d,)`
+  constant, an `(E, d)` tensor, an `(E, Q^d, d)` tensor at the quadrature
+  points of the solve's rule (`FiniteElementSpace.to_quadrature` makes one
+  from nodal values) or a callable from `(M, d)` coordinates to `(M, d)`
+  values.  The solve then runs BiCGStab (`info` is its), `preconditioner` is
+  None or 'jacobi', and it needs the fused operator and a mesh without
+  partitions.  A velocity does not remove the constant nullspace.
 
   `diffusivity` k (> 0) and `reaction` c (>= 0): None (= 1), a scalar, an
   `(E,)` tensor of per-element values, an `(E, Q^d)` tensor at the quadrature
@@ -98,7 +114,7 @@ def solve_helmholtz(mesh: Mesh, forcing,
 
   `preconditioner`: None, 'jacobi' or 'pmg', as in `solve_poisson` (on a
   mesh without periodic images).  `rtol` is relative to the norm of the
-  lifted right-hand side; `info` is CG's.
+  lifted right-hand side; `info` is CG's (BiCGStab's with a velocity).
   """
   if preconditioner not in (None, 'jacobi', 'pmg'):
     raise ValueError(f'unknown preconditioner {preconditioner!r}')
@@ -107,6 +123,10 @@ def solve_helmholtz(mesh: Mesh, forcing,
   if mesh._cache.get('replicas', 1) > 1:
     raise NotImplementedError('solve_helmholtz on an ensemble '
                               '(Mesh.replicate)')
+  advection = velocity is not None
+  if advection and preconditioner == 'pmg':
+    raise NotImplementedError("preconditioner='pmg' with a velocity: the "
+                              'V-cycle is built for the symmetric operator')
   lambda0, lambda1 = float(lambda0), float(lambda1)
   quadrature = Quadrature1D.create(
       num_points=mesh.order + (mesh.ndim + 1) // 2,
@@ -187,13 +207,23 @@ def solve_helmholtz(mesh: Mesh, forcing,
   if (fespace.is_collocated and operators.supports_fused(fespace) is None) or (
       not fespace.is_collocated and
       operators.supports_two_grid(fespace) is None):
-    op = fespace.helmholtz_operator(mask, diffusivity=diffusivity,
-                                    reaction=reaction)
-    full = (fespace.helmholtz_operator(None, diffusivity=diffusivity,
-                                       reaction=reaction)
-            if has_dirichlet or not coefficients else op)
-    # the right-hand side B f takes the plain mass matrix
-    plain = fespace.helmholtz_operator(None) if coefficients else full
+    if advection:
+      # the masked operator with the advective term goes to BiCGStab, the
+      # unmasked one lifts the Dirichlet data; B f takes the plain mass matrix
+      op = fespace.helmholtz_operator(mask, diffusivity=diffusivity,
+                                      reaction=reaction, velocity=velocity)
+      full = (fespace.helmholtz_operator(None, diffusivity=diffusivity,
+                                         reaction=reaction, velocity=velocity)
+              if has_dirichlet else op)
+      plain = fespace.helmholtz_operator(None)
+    else:
+      op = fespace.helmholtz_operator(mask, diffusivity=diffusivity,
+                                      reaction=reaction)
+      full = (fespace.helmholtz_operator(None, diffusivity=diffusivity,
+                                         reaction=reaction)
+              if has_dirichlet or not coefficients else op)
+      # the right-hand side B f takes the plain mass matrix
+      plain = fespace.helmholtz_operator(None) if coefficients else full
     if callable(reaction) and not no_mass:
       c = op.coefs[1][1]
       if bool((c == 0).all()) and not has_dirichlet and not robin_weight > 0:
@@ -222,6 +252,10 @@ def solve_helmholtz(mesh: Mesh, forcing,
     raise NotImplementedError(
         f"preconditioner={preconditioner!r} needs the fused operator: "
         f"{operators.supports_two_grid(fespace)}")
+  elif advection:
+    raise NotImplementedError(
+        'a velocity needs the fused operator: '
+        f'{operators.supports_two_grid(fespace)}')
   elif coefficients:
     raise NotImplementedError(
         'diffusivity / reaction need the fused operator: '
@@ -262,7 +296,10 @@ def solve_helmholtz(mesh: Mesh, forcing,
   A = K
   if periodic:
     A = lambda x: mesh.exchange(K(mesh.exchange(x))) * keep
-  w, info = cg(A, b, tol=rtol, atol=atol, M=M)
+  if advection:
+    w, info = bicgstab(A, b, tol=rtol, atol=atol, M=M)
+  else:
+    w, info = cg(A, b, tol=rtol, atol=atol, M=M)
   if periodic:
     w = mesh.exchange(w)
   u = w + u_D
