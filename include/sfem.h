@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SFEM_ABI_VERSION 9
+#define SFEM_ABI_VERSION 10
 
 enum { SFEM_F32 = 0, SFEM_F64 = 1 };
 enum {
@@ -341,6 +341,12 @@ typedef struct sfem_helmholtz_args {
   /* of the struct; callers that zero the struct keep the operator without    */
   /* the term.                                                                */
   const void* beta;       /* (E, n, ndim) or NULL = off                       */
+  /* 0: C_b as above.  != 0: its transpose,                                   */
+  /*   (C_b^T v)_i = sum_q (sum_d beta[q,d] D_d phi_i(q)) v(q),               */
+  /* so that the call applies (lambda0 B_c + lambda1 A_k + C_b)^T (B_c and    */
+  /* A_k are symmetric).  Honoured wherever `beta` is; ignored without        */
+  /* `beta`, when the operator is symmetric.  ABI version 10.                 */
+  int32_t adv_transpose;
   /* Variable coefficients (NULL / 0 = off): the operator becomes             */
   /*   lambda0 B_c + lambda1 A_k,  B_c[i,j] = sum_q c_q W_q phi_i phi_j,      */
   /*   A_k[i,j] = sum_q k_q grad phi_i . G_q grad phi_j.                      */
@@ -398,6 +404,44 @@ int sfem_helmholtz_apply(const sfem_helmholtz_args* args, sfem_stream_t stream);
 /* Element-local variant (no gather/scatter, no mask): u, out are (E, n, ncomp).
  * StokesVelocity.A_local / B_local (navier_stokes.py:220-236).               */
 int sfem_helmholtz_local(const sfem_helmholtz_args* args, sfem_stream_t stream);
+
+/* Coefficient sensitivities of  A(k, c, beta) = lambda0 B_c + lambda1 A_k +
+ * C_beta  (sfem_helmholtz_args: kappa, sigma, beta), element-local: for two
+ * scalar fields u, lam given at the operator's points, (E, n) each, per point
+ *   dkappa[e,q]  = d(lam . A u) / d k[e,q]      = lambda1 g_lam . G g_u
+ *   dsigma[e,q]  = d(lam . A u) / d c[e,q]      = lambda0 W lam u
+ *   dbeta[e,q,d] = d(lam . A u) / d beta[e,q,d] = lam (D_d u)
+ * with g the reference-space gradients, D_d the derivative along reference
+ * direction d, and G, W the geometric factors WITHOUT coefficients: pass the
+ * bare stored factors in `geo`, not a copy with k and c folded in.  No gather,
+ * no scatter; arrays are indexed by element id, points in slot order
+ * (lexicographic, axis 0 slowest), dbeta with ndim consecutive reals per
+ * point.  Each output is optional: NULL skips the product and its stores;
+ * with all three NULL the call does nothing.  geo / geo_elem / geo_index /
+ * elem_list / dmat / weights / nodes / geo_mode as in sfem_helmholtz_args
+ * (every geo_mode but SFEM_GEO_BOX).  ncomp != 1, ndim outside 2..3 and P
+ * outside 2..12 return SFEM_EUNSUPPORTED; u or lam NULL is SFEM_EINVAL.
+ * ABI version 10.                                                           */
+typedef struct sfem_helmholtz_sens_args {
+  const void* u;          /* (E, n)                                           */
+  const void* lam;        /* (E, n)                                           */
+  void* dkappa;           /* (E, n) or NULL                                   */
+  void* dsigma;           /* (E, n) or NULL                                   */
+  void* dbeta;            /* (E, n, ndim) or NULL                             */
+  const void* geo;
+  const void* geo_elem;
+  const int32_t* geo_index;
+  const int32_t* elem_list;
+  const void* dmat;       /* HOST (P, P)                                      */
+  const void* weights;    /* HOST (P,)                                        */
+  const void* nodes;      /* HOST (P,)                                        */
+  int64_t num_elements;
+  int64_t num_listed;
+  int32_t ndim, P, ncomp, dtype, geo_mode;
+  double lambda0, lambda1;
+} sfem_helmholtz_sens_args;
+int sfem_helmholtz_sens(const sfem_helmholtz_sens_args* args,
+                        sfem_stream_t stream);
 
 /* ------------------------------------------------- fused Stokes operators ---
  * The P_N - P_{N-2} divergence D and pressure gradient D^T of

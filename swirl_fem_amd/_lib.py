@@ -15,7 +15,7 @@ from swirl_fem_amd import switches
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SFEM_LIB: another build of the same library (kernel A/B experiments)
 LIB_PATH = switches.get('SFEM_LIB') or os.path.join(_HERE, 'libsfem_hip.so')
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 SFEM_F32, SFEM_F64 = 0, 1
 SFEM_CG_NSCALARS_NAMED = 16
@@ -62,12 +62,29 @@ class HelmholtzArgs(ctypes.Structure):
       # order, W b . invjac; index rows / element-local, scalar fields,
       # coefficients per point only
       ('beta', c_ptr),
+      # != 0: the advective term transposed (C_b^T; B_c and A_k are
+      # symmetric, so the call applies the transposed operator); ignored
+      # without beta
+      ('adv_transpose', c_i32),
       # variable coefficients (None / 0 = off): kappa (diffusivity k) and
       # sigma (reaction c), device arrays indexed by element id -- (E,) for
       # coef_mode COEF_ELEM, (E, n) in slot order for COEF_POINT; None
       # stands for 1.  Scalar fields, index rows, affine / multilinear
       # launches only.
       ('kappa', c_ptr), ('sigma', c_ptr), ('coef_mode', c_i32),
+  ]
+
+
+class HelmholtzSensArgs(ctypes.Structure):
+  """Mirror of `struct sfem_helmholtz_sens_args`."""
+  _fields_ = [
+      ('u', c_ptr), ('lam', c_ptr), ('dkappa', c_ptr), ('dsigma', c_ptr),
+      ('dbeta', c_ptr), ('geo', c_ptr), ('geo_elem', c_ptr),
+      ('geo_index', c_ptr), ('elem_list', c_ptr), ('dmat', c_ptr),
+      ('weights', c_ptr), ('nodes', c_ptr), ('num_elements', c_i64),
+      ('num_listed', c_i64), ('ndim', c_i32), ('P', c_i32), ('ncomp', c_i32),
+      ('dtype', c_i32), ('geo_mode', c_i32), ('lambda0', c_dbl),
+      ('lambda1', c_dbl),
   ]
 
 
@@ -141,6 +158,7 @@ SIGNATURES = {
     'sfem_helmholtz_setup_multilinear': [c_ptr, c_ptr, c_i64, c_i32, c_i32,
                                          c_i32, c_ptr],
     'sfem_helmholtz_local': [ctypes.POINTER(HelmholtzArgs), c_ptr],
+    'sfem_helmholtz_sens': [ctypes.POINTER(HelmholtzSensArgs), c_ptr],
     'sfem_facet_table_build': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64,
                                c_i32, c_ptr],
     'sfem_helmholtz_setup_affine': [c_ptr, c_ptr, c_i64, c_dbl, c_i32, c_ptr],

@@ -468,7 +468,7 @@ def _dptr(t):
 
 def _helmholtz_args(u, out, enc, part, host, ndim, P, num_elements, num_nodes,
                     lambda0, lambda1, zero_range, dot_out=None,
-                    layered_extent=0, dot_slots=0):
+                    layered_extent=0, dot_slots=0, transpose=False):
   """Builds `sfem_helmholtz_args`; `part` = dict(geo_mode, geo, geo_elem,
   geo_index, elem_list), `host` = dict(dmat, weights, nodes) NumPy arrays
   (kept alive by the caller for the duration of the call)."""
@@ -526,7 +526,7 @@ def _helmholtz_args(u, out, enc, part, host, ndim, P, num_elements, num_nodes,
       layered_extent=int(layered_extent), dot_slots=int(dot_slots),
       kappa=_dptr(part.get('kappa')), sigma=_dptr(part.get('sigma')),
       coef_mode=int(part.get('coef_mode', _lib.COEF_NONE)),
-      beta=_dptr(part.get('beta')))
+      beta=_dptr(part.get('beta')), adv_transpose=int(bool(transpose)))
 
 
 _CLUSTER_LIMITS = {}
@@ -575,7 +575,7 @@ def helmholtz_kernel_name(real, P, ndim, scalar, geo_mode, part, mass,
     return 'sfem::helmholtz_cluster_kernel<%s, %d, %s, %d, %s>' % (
         real, P, b(scalar), geo_mode, b(mass))
   if part.get('beta') is not None:
-    return 'sfem::helmholtz_adv_kernel<%s, %d, %d, true, %d>' % (
+    return 'sfem::helmholtz_adv_kernel<%s, %d, %d, true, %d, false>' % (
         real, P, ndim, geo_mode)
   if part.get('coef_mode'):
     return ('sfem::helmholtz_kernel<%s, %d, %d, true, true, %d, false, %s, '
@@ -590,12 +590,13 @@ def helmholtz_kernel_name(real, P, ndim, scalar, geo_mode, part, mass,
 
 
 def helmholtz_apply(u, out, enc, parts, host, ndim, P, lambda0, lambda1,
-                    zero_range, dot_out=None):
+                    zero_range, dot_out=None, transpose=False):
   """out <- mask * scatter((l0 B + l1 A)_local(gather(u))).
 
   `parts`: one dict per geometry kind present in the mesh (see
   `_helmholtz_args`); the shared-node range of `out` is cleared by the first
-  launch only.
+  launch only.  `transpose`: the advective term of launches that carry a
+  `beta` is applied transposed (`adv_transpose`).
   """
   dev = _dev(enc)
   _check_vector_layout(u, out)
@@ -606,7 +607,8 @@ def helmholtz_apply(u, out, enc, parts, host, ndim, P, lambda0, lambda1,
     for n, part in enumerate(parts):
       args = _helmholtz_args(u, out, part.get('enc', enc), part, host, ndim,
                              P, enc.shape[0], u.shape[0], lambda0, lambda1,
-                             zero_range if n == 0 else (0, 0), dot_out)
+                             zero_range if n == 0 else (0, 0), dot_out,
+                             transpose=transpose)
       _lib.check(_lib.load().sfem_helmholtz_apply(ctypes.byref(args),
                                                   _stream(dev)),
                  'sfem_helmholtz_apply')
@@ -1125,7 +1127,8 @@ def _check_vector_layout(u, out):
     raise ValueError('u and out must share shape and memory layout')
 
 
-def helmholtz_local(u_local, parts, host, ndim, P, lambda0, lambda1):
+def helmholtz_local(u_local, parts, host, ndim, P, lambda0, lambda1,
+                    transpose=False):
   if not (u_local.is_contiguous() or is_component_major(u_local)):
     u_local = u_local.contiguous()
   dev = u_local.device
@@ -1135,10 +1138,52 @@ def helmholtz_local(u_local, parts, host, ndim, P, lambda0, lambda1):
   with torch.cuda.device(dev):
     for part in parts:
       args = _helmholtz_args(u_local, out, None, part, host, ndim, P,
-                             u_local.shape[0], 0, lambda0, lambda1, (0, 0))
+                             u_local.shape[0], 0, lambda0, lambda1, (0, 0),
+                             transpose=transpose)
       _lib.check(_lib.load().sfem_helmholtz_local(ctypes.byref(args),
                                                   _stream(dev)),
                  'sfem_helmholtz_local')
+  return out
+
+
+def helmholtz_sens(u_local, lam_local, parts, host, ndim, P, lambda0, lambda1,
+                   want=(True, True, True), out=None, ncomp=1):
+  """Per-point sensitivities of lam . (lambda0 B_c + lambda1 A_k + C_beta) u
+  (`sfem_helmholtz_sens`): `u_local`, `lam_local` (E, n) at the operator's
+  points; `parts` the launches WITHOUT coefficients (bare G and W).  Returns
+  (dkappa (E, n), dsigma (E, n), dbeta (E, n, ndim)), None where `want` is
+  false; `out`: three tensors (or None) to write instead of new ones."""
+  u_local = u_local.contiguous()
+  lam_local = lam_local.contiguous()
+  _check_vector_layout(u_local, lam_local)
+  dev = u_local.device
+  host = {k: _host(v, u_local.dtype) for k, v in host.items()}
+  E, n = u_local.shape[0], u_local.shape[1]
+  shapes = ((E, n), (E, n), (E, n, ndim))
+  if out is None:
+    out = tuple(torch.zeros(s, dtype=u_local.dtype, device=dev) if w else None
+                for s, w in zip(shapes, want))
+  for t, s in zip(out, shapes):
+    if t is not None and (tuple(t.shape) != s or not t.is_contiguous() or
+                          t.dtype != u_local.dtype or t.device != dev):
+      raise ValueError(f'sensitivity output: expected a contiguous {s} '
+                       'tensor of the field\'s dtype and device')
+  with torch.cuda.device(dev):
+    for part in parts:
+      lst = part.get('elem_list')
+      args = _lib.HelmholtzSensArgs(
+          u=u_local.data_ptr(), lam=lam_local.data_ptr(),
+          dkappa=_dptr(out[0]), dsigma=_dptr(out[1]), dbeta=_dptr(out[2]),
+          geo=_dptr(part.get('geo')), geo_elem=_dptr(part.get('geo_elem')),
+          geo_index=_dptr(part.get('geo_index')), elem_list=_dptr(lst),
+          dmat=_hptr(host['dmat']), weights=_hptr(host.get('weights')),
+          nodes=_hptr(host.get('nodes')), num_elements=E,
+          num_listed=0 if lst is None else lst.numel(), ndim=ndim, P=P,
+          ncomp=ncomp, dtype=_dtype_code(u_local), geo_mode=part['geo_mode'],
+          lambda0=float(lambda0), lambda1=float(lambda1))
+      _lib.check(_lib.load().sfem_helmholtz_sens(ctypes.byref(args),
+                                                 _stream(dev)),
+                 'sfem_helmholtz_sens')
   return out
 
 

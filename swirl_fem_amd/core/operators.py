@@ -486,8 +486,8 @@ def coefficient(value, name, num_elements, npts, points, dtype, device):
     check(torch.tensor(v, dtype=torch.float64))
     return v
   try:
-    t = torch.as_tensor(value)
-  except (TypeError, ValueError, RuntimeError):
+    t = torch.as_tensor(value).detach()     # the checks and the kernels read
+  except (TypeError, ValueError, RuntimeError):   # values, not a graph
     t = torch.zeros((), dtype=torch.bool)
   numeric = t.is_floating_point() or t.dtype in (torch.int32, torch.int64)
   if t.dim() == 0 and numeric:
@@ -629,7 +629,7 @@ def velocity_field(value, num_elements, npts, ndim, points, dtype, device):
     t = t.reshape(E, npts, d)
   else:
     try:
-      t = torch.as_tensor(value)
+      t = torch.as_tensor(value).detach()
     except (TypeError, ValueError, RuntimeError):
       t = torch.zeros((), dtype=torch.bool)
     if not (t.is_floating_point() or t.dtype in (torch.int32, torch.int64)):
@@ -654,6 +654,78 @@ def fold_velocity(fespace, b):
   advective term at a point is beta . (reference-space derivatives of u)."""
   beta = torch.einsum('eqj,eqjd->eqd', b, fespace.invjacs)
   return (beta * fespace.wdet()[..., None]).contiguous()
+
+
+def unfold_velocity_gradient(fespace, dbeta):
+  """The transpose of `fold_velocity`: the gradient (E, Q^d, d) with respect
+  to the folded velocity beta as the gradient with respect to b,
+  db[e,q,j] = W[e,q] sum_d dbeta[e,q,d] invjacs[e,q,j,d]."""
+  db = torch.einsum('eqd,eqjd->eqj', dbeta, fespace.invjacs)
+  return db * fespace.wdet()[..., None]
+
+
+def _is_callable_source(value):
+  return callable(value) and not isinstance(value, torch.Tensor)
+
+
+def reduce_coefficient_gradient(g, source):
+  """A per-point gradient `g` (E, npts) in the form of the coefficient the
+  caller passed (`coefficient`): a scalar gives the sum over all points (a
+  0-dim tensor), an (E,) tensor the sum over each element's points, an
+  (E, npts) tensor `g` itself.  None for None and for a callable."""
+  if source is None or _is_callable_source(source) or g is None:
+    return None
+  shape = tuple(torch.as_tensor(source).shape)
+  if shape == ():
+    return g.sum()
+  if shape == (g.shape[0],):
+    return g.sum(dim=1)
+  if shape == tuple(g.shape):
+    return g
+  raise ValueError(f'coefficient of shape {shape} against a gradient of '
+                   f'shape {tuple(g.shape)}')
+
+
+def reduce_velocity_gradient(g, source):
+  """A per-point gradient `g` (E, npts, d) in the form of the velocity the
+  caller passed (`velocity_field`): (d,) gives the sum over elements and
+  points, (E, d) the sum over each element's points, (E, npts, d) `g`
+  itself.  None for None and for a callable."""
+  if source is None or _is_callable_source(source) or g is None:
+    return None
+  shape = tuple(torch.as_tensor(source).shape)
+  E, _, d = g.shape
+  if shape == (d,):
+    return g.sum(dim=(0, 1))
+  if shape == (E, d):
+    return g.sum(dim=1)
+  if shape == tuple(g.shape):
+    return g
+  raise ValueError(f'velocity of shape {shape} against a gradient of shape '
+                   f'{tuple(g.shape)}')
+
+
+def _sensitivity(op, ul, ll, host_P, lambda0, lambda1, want):
+  """Shared by the two operator classes: `ul`, `ll` (E, npts) at the
+  operator's points -> the three gradients in the callers' forms."""
+  fes = op.fespace
+  src_k, src_c = op.coef_source
+  src_b = op.velocity_source
+  tensor = lambda v: v is not None and not _is_callable_source(v)
+  wk = want[0] and tensor(src_k)
+  wc = want[1] and tensor(src_c)
+  wb = want[2] and tensor(src_b)
+  if not (wk or wc or wb):
+    return None, None, None
+  # the launches without coefficients: curved launches of `parts` carry k and
+  # c folded into their stored factors, the sensitivities need bare G and W
+  dk, dc, dbeta = _ops.helmholtz_sens(
+      ul, ll, op._geo_parts, op.host, fes.mesh.ndim, host_P, lambda0, lambda1,
+      want=(wk, wc, wb))
+  db = None if dbeta is None else unfold_velocity_gradient(fes, dbeta)
+  return (reduce_coefficient_gradient(dk, src_k),
+          reduce_coefficient_gradient(dc, src_c),
+          reduce_velocity_gradient(db, src_b))
 
 
 def _check_velocity_mesh(mesh, assembly):
@@ -725,10 +797,13 @@ class _PlainLinearOperator:
   """`u -> op.apply(u, lambda0, lambda1)` without a fused `u . A(u)`: what
   `linalg.bicgstab` takes (it needs no p . Ap)."""
 
-  def __init__(self, op, lambda0, lambda1):
+  def __init__(self, op, lambda0, lambda1, transpose=False):
     self.op, self.lambda0, self.lambda1 = op, lambda0, lambda1
+    self.transpose = transpose
 
   def __call__(self, u):
+    if self.transpose:
+      return self.op.apply_transpose(u, self.lambda0, self.lambda1)
     return self.op.apply(u, self.lambda0, self.lambda1)
 
 
@@ -759,6 +834,7 @@ class HelmholtzOperator:
   velocity: torch.Tensor | None = None
   beta: torch.Tensor | None = None
   _diag_adv: torch.Tensor | None = None   # assembled diag C_b, `diagonal`
+  velocity_source: object = None      # the `velocity` the caller passed
 
   @classmethod
   def create(cls, fespace, dirichlet_mask=None, geometry='auto',
@@ -810,9 +886,10 @@ class HelmholtzOperator:
                            points, fespace.dtype, fespace.device))
       if assembly == 'auto':
         assembly = 'atomic'
-    beta = None
+    beta = velocity_source = None
     if velocity is not None:
       mesh = fespace.mesh
+      velocity_source = velocity
       velocity = velocity_field(
           velocity, mesh.num_elements, mesh.num_nodes_per_element, mesh.ndim,
           mesh.element_coords, fespace.dtype, fespace.device)
@@ -932,6 +1009,7 @@ class HelmholtzOperator:
                keep=None if mask is None else (mask == 0).to(fespace.dtype),
                coefs=coefs, coef_source=(diffusivity, reaction),
                _geo_parts=geo_parts, velocity=velocity, beta=beta,
+               velocity_source=velocity_source,
                _layer_plan=(False if coefs is not None or beta is not None
                             else None))
 
@@ -978,13 +1056,16 @@ class HelmholtzOperator:
       facet = (None if self.facet_parts is None
                else restrict(self.facet_parts, keep))
       # (each half covers part of the mesh only: no layer plan)
+      geo = (None if self._geo_parts is None
+             else restrict(self._geo_parts, keep))
       halves.append(dataclasses.replace(self, parts=parts, facet_parts=facet,
                                         _vector_parts=None, _layer_plan=False,
-                                        _diag=None, _diag_adv=None))
+                                        _diag=None, _diag_adv=None,
+                                        _geo_parts=geo))
     return tuple(halves)
 
   def apply(self, u, lambda0=0.0, lambda1=1.0, out=None, *, zero=True,
-            dot_out=None):
+            dot_out=None, _transpose=False):
     """u (N,) or (N, nc) -> mask * scatter((l0 B + l1 A)_local(gather(u))).
 
     `zero=False` skips clearing the shared-node range of `out` (the caller has
@@ -1011,7 +1092,37 @@ class HelmholtzOperator:
     return _ops.helmholtz_apply(
         u, out, self.enc, self._parts_for(u), self.host, mesh.ndim,
         mesh.gridpoints_1d.num_points, lambda0, lambda1,
-        self.zero_range if zero else (0, 0), dot_out)
+        self.zero_range if zero else (0, 0), dot_out, transpose=_transpose)
+
+  def apply_transpose(self, u, lambda0=0.0, lambda1=1.0, out=None):
+    """`apply` with the advective term transposed: mask * scatter((l0 B_c +
+    l1 A_k + C_b)^T_local(gather(u))).  Without a velocity the operator is
+    symmetric and this is `apply`.  With a Dirichlet mask the Dirichlet rows
+    of the result are zero, as `apply` zeroes them: this is the transpose of
+    `apply` on vectors that vanish on the Dirichlet nodes; without a mask it
+    is the exact transpose."""
+    if self.beta is None:
+      return self.apply(u, lambda0, lambda1, out)
+    return self.apply(u, lambda0, lambda1, out, _transpose=True)
+
+  def sensitivity(self, u, lam, lambda0=0.0, lambda1=1.0,
+                  want=(True, True, True)):
+    """The gradient of lam . (A(k, c, b) u), A = lambda0 B_c + lambda1 A_k +
+    C_b WITHOUT the Dirichlet mask, with respect to (diffusivity, reaction,
+    velocity), each in the form the caller passed to `create`: a scalar gives
+    a 0-dim tensor (the sum over all points), (E,) / (E, d) the sum over each
+    element's points, (E, n[, d]) per-point values, a (d,) velocity the sum
+    over elements and points.  None for a coefficient that was absent or a
+    callable, and where `want` is false.  `u`, `lam`: nodal (N,)."""
+    mesh = self.fespace.mesh
+    for v in (u, lam):
+      if tuple(v.shape) != (mesh.num_nodes,):
+        raise ValueError(f'expected ({mesh.num_nodes},) nodal values, got '
+                         f'{tuple(v.shape)}')
+    dt = self.fespace.dtype
+    u, lam = u.detach(), lam.detach()
+    return _sensitivity(self, mesh.gather(u.to(dt)), mesh.gather(lam.to(dt)),
+                        mesh.gridpoints_1d.num_points, lambda0, lambda1, want)
 
   def layer_plan(self):
     """The `LayerPlan` of this operator's facet launches (made on first use),
@@ -1129,8 +1240,10 @@ class HelmholtzOperator:
         want_stiff=False, dtype=self.fespace.dtype, device=self.fespace.device)
     return mass
 
-  def apply_local(self, u_local, lambda0=0.0, lambda1=1.0):
-    """Element-local action (E, n[, nc]) -> (E, n[, nc]); no gather/scatter."""
+  def apply_local(self, u_local, lambda0=0.0, lambda1=1.0, *,
+                  transpose=False):
+    """Element-local action (E, n[, nc]) -> (E, n[, nc]); no gather/scatter.
+    `transpose`: the advective term transposed (`apply_transpose`)."""
     mesh = self.fespace.mesh
     if self.coefs is not None:
       if u_local.dim() == 3 and u_local.shape[-1] != 1:
@@ -1140,15 +1253,18 @@ class HelmholtzOperator:
       raise NotImplementedError('a velocity takes scalar fields')
     return _ops.helmholtz_local(
         u_local.to(self.fespace.dtype), self.parts, self.host, mesh.ndim,
-        mesh.gridpoints_1d.num_points, lambda0, lambda1)
+        mesh.gridpoints_1d.num_points, lambda0, lambda1,
+        transpose=transpose and self.beta is not None)
 
-  def linear_operator(self, lambda0=0.0, lambda1=1.0):
+  def linear_operator(self, lambda0=0.0, lambda1=1.0, transpose=False):
     """`u -> apply(u, lambda0, lambda1)` as an object that `cg` recognises:
     it also offers `apply_with_dot(u, partials)` (fused p.Ap).  With a
     velocity the operator is not symmetric and goes to `linalg.bicgstab`,
-    which needs no p.Ap: a plain callable."""
+    which needs no p.Ap: a plain callable; `transpose=True` then gives
+    `u -> apply_transpose(u, lambda0, lambda1)` (without a velocity the
+    operator is its own transpose)."""
     if self.beta is not None:
-      return _PlainLinearOperator(self, lambda0, lambda1)
+      return _PlainLinearOperator(self, lambda0, lambda1, transpose)
     return FusedLinearOperator(self, lambda0, lambda1)
 
   def bytes_per_apply(self, lambda0=0.0, ncomp=1, layered=False):
@@ -1847,6 +1963,7 @@ class TwoGridHelmholtzOperator:
   velocity: torch.Tensor | None = None
   beta: torch.Tensor | None = None
   _diag_adv: torch.Tensor | None = None
+  velocity_source: object = None
 
   @classmethod
   def create(cls, fespace, dirichlet_mask=None, geometry='auto', *,
@@ -1877,6 +1994,7 @@ class TwoGridHelmholtzOperator:
                coefficient(reaction, 'reaction', E, nq, points,
                            fespace.dtype, dev))
     beta = None
+    velocity_source = velocity
     if velocity is not None:
       _check_velocity_mesh(mesh, 'atomic')
       nq = fespace.quadrature.num_points ** mesh.ndim
@@ -1936,7 +2054,8 @@ class TwoGridHelmholtzOperator:
                                fespace.quadrature.num_points ** mesh.ndim)
     return cls(fespace=fespace, parts=parts, host=host, mask=mask,
                coefs=coefs, coef_source=(diffusivity, reaction),
-               _geo_parts=geo_parts, velocity=velocity, beta=beta)
+               _geo_parts=geo_parts, velocity=velocity, beta=beta,
+               velocity_source=velocity_source)
 
   def point_weights(self):
     """W = w detJ (E, Q^d) at the quadrature points, without coefficients."""
@@ -1948,8 +2067,10 @@ class TwoGridHelmholtzOperator:
         want_stiff=False, dtype=self.fespace.dtype, device=self.fespace.device)
     return mass
 
-  def apply_local(self, u_local, lambda0=0.0, lambda1=1.0):
-    """(E, n[, nc]) -> (E, n[, nc])."""
+  def apply_local(self, u_local, lambda0=0.0, lambda1=1.0, *,
+                  transpose=False):
+    """(E, n[, nc]) -> (E, n[, nc]).  `transpose`: I^T (A_q)^T I, the
+    advective term of the q-grid kernel transposed."""
     fes = self.fespace
     mesh = fes.mesh
     E, n = mesh.num_elements, mesh.num_nodes_per_element
@@ -1965,7 +2086,8 @@ class TwoGridHelmholtzOperator:
     q = fes.quadrature.num_points
     uq = u3 if fes.is_collocated else fes._basis(u3, True, False)[0]
     rq = _ops.helmholtz_local(uq.contiguous(), self.parts, self.host,
-                              mesh.ndim, q, lambda0, lambda1)
+                              mesh.ndim, q, lambda0, lambda1,
+                              transpose=transpose and self.beta is not None)
     if fes.is_collocated:
       r3 = rq
     else:
@@ -1978,7 +2100,7 @@ class TwoGridHelmholtzOperator:
                              mesh.gridpoints_1d.num_points, q, nc, False)
     return r3[..., 0] if scalar else r3
 
-  def apply(self, u, lambda0=0.0, lambda1=1.0):
+  def apply(self, u, lambda0=0.0, lambda1=1.0, *, _transpose=False):
     """u (N,) or (N, nc) -> mask * scatter(local(gather(u)))."""
     mesh = self.fespace.mesh
     if u.shape[0] != mesh.num_nodes:
@@ -1986,14 +2108,42 @@ class TwoGridHelmholtzOperator:
                        f'{tuple(u.shape)}')
     u = u.to(self.fespace.dtype)
     if u.dim() == 1:
-      out = mesh.scatter(self.apply_local(mesh.gather(u), lambda0, lambda1))
+      out = mesh.scatter(self.apply_local(mesh.gather(u), lambda0, lambda1,
+                                          transpose=_transpose))
       return out if self.mask is None else out * self.mask
     loc = self.apply_local(_ops.gather_rows(u.contiguous(), mesh.elements),
                            lambda0, lambda1)
     out = _ops.scatter_add(loc, mesh.elements, mesh.num_nodes, ncomp=u.shape[1])
     return out if self.mask is None else out * self.mask[:, None]
 
-  def linear_operator(self, lambda0=0.0, lambda1=1.0):
+  def apply_transpose(self, u, lambda0=0.0, lambda1=1.0):
+    """`apply` with the advective term transposed, I^T (A_q)^T I element by
+    element; see `HelmholtzOperator.apply_transpose` for the mask."""
+    return self.apply(u, lambda0, lambda1,
+                      _transpose=self.beta is not None)
+
+  def sensitivity(self, u, lam, lambda0=0.0, lambda1=1.0,
+                  want=(True, True, True)):
+    """`HelmholtzOperator.sensitivity` at the Q^d quadrature points: `u` and
+    `lam` (N,) are interpolated there."""
+    fes = self.fespace
+    mesh = fes.mesh
+    for v in (u, lam):
+      if tuple(v.shape) != (mesh.num_nodes,):
+        raise ValueError(f'expected ({mesh.num_nodes},) nodal values, got '
+                         f'{tuple(v.shape)}')
+
+    def at_points(v):
+      vl = mesh.gather(v.detach().to(fes.dtype))
+      if fes.is_collocated:
+        return vl
+      return fes._basis(vl[..., None], True, False)[0][..., 0].contiguous()
+    return _sensitivity(self, at_points(u), at_points(lam),
+                        fes.quadrature.num_points, lambda0, lambda1, want)
+
+  def linear_operator(self, lambda0=0.0, lambda1=1.0, transpose=False):
+    if transpose:
+      return lambda u: self.apply_transpose(u, lambda0, lambda1)
     return lambda u: self.apply(u, lambda0, lambda1)
 
   def diagonal(self, lambda0=0.0, lambda1=1.0, assembled=True):

@@ -6,6 +6,7 @@
 #include "sfem_helmholtz_mfma.h"
 #include "sfem_helmholtz_facet.h"
 #include "sfem_helmholtz_adv.h"
+#include "sfem_helmholtz_sens.h"
 
 namespace sfem {
 
@@ -251,6 +252,7 @@ struct HelmholtzCall {
   const void* sigma = nullptr;
   int coef_mode = 0;
   const void* beta = nullptr;
+  int adv_transpose = 0;
 };
 
 template <typename T>
@@ -278,8 +280,10 @@ static int run_helmholtz(const HelmholtzCall& c, hipStream_t stream) {
     ap.kappa = (const T*)c.kappa;
     ap.sigma = (const T*)c.sigma;
     ap.beta = (const T*)c.beta;
-    if (c.ndim == 3) return dispatch_helmholtz_adv<T, 3>(ap, c.P, c.gs, stream);
-    return dispatch_helmholtz_adv<T, 2>(ap, c.P, c.gs, stream);
+    const bool tr = c.adv_transpose != 0;
+    if (c.ndim == 3)
+      return dispatch_helmholtz_adv<T, 3>(ap, c.P, c.gs, tr, stream);
+    return dispatch_helmholtz_adv<T, 2>(ap, c.P, c.gs, tr, stream);
   }
   if (c.coef_mode != COEF_NONE) {
     HelmholtzCoefParams<T> cp{};
@@ -547,6 +551,7 @@ int sfem_helmholtz_apply(const sfem_helmholtz_args* a, sfem_stream_t stream) {
   c.sigma = a->sigma;
   c.coef_mode = a->coef_mode;
   c.beta = a->beta;
+  c.adv_transpose = a->adv_transpose;
   SFEM_REQUIRE(!a->shared_order || (a->shared_stride > 0 &&
                                     a->shared_stride <= 0xFFFF),
                "sfem_helmholtz_apply: bad shared_stride");
@@ -734,8 +739,67 @@ int sfem_helmholtz_local(const sfem_helmholtz_args* a, sfem_stream_t stream) {
   c.sigma = a->sigma;
   c.coef_mode = a->coef_mode;
   c.beta = a->beta;
+  c.adv_transpose = a->adv_transpose;
   if (a->dtype == SFEM_F64) return run_helmholtz<double>(c, as_stream(stream));
   return run_helmholtz<float>(c, as_stream(stream));
+}
+
+int sfem_helmholtz_sens(const sfem_helmholtz_sens_args* a,
+                        sfem_stream_t stream) {
+  SFEM_REQUIRE(a, "sfem_helmholtz_sens: null args");
+  SFEM_REQUIRE(a->num_elements >= 0 && a->ncomp >= 1,
+               "sfem_helmholtz_sens: bad sizes");
+  SFEM_REQUIRE(a->dtype == SFEM_F32 || a->dtype == SFEM_F64,
+               "sfem_helmholtz_sens: unknown dtype %d", a->dtype);
+  if (a->ncomp != 1) {
+    set_error("sfem_helmholtz_sens: takes scalar fields (ncomp = %d)",
+              a->ncomp);
+    return SFEM_EUNSUPPORTED;
+  }
+  if (a->ndim != 2 && a->ndim != 3) {
+    set_error("sfem_helmholtz_sens: ndim=%d (the kernel supports 2 and 3)",
+              a->ndim);
+    return SFEM_EUNSUPPORTED;
+  }
+  if (a->P < 2 || a->P > 12) {
+    set_error("sfem_helmholtz_sens: P=%d outside the compiled range 2..12",
+              a->P);
+    return SFEM_EUNSUPPORTED;
+  }
+  if (a->num_elements == 0) return SFEM_OK;
+  SFEM_REQUIRE(a->u && a->lam && a->dmat,
+               "sfem_helmholtz_sens: null pointer");
+  if (!a->dkappa && !a->dsigma && !a->dbeta) return SFEM_OK;
+  int rc = check_geometry("sfem_helmholtz_sens", a->geo_mode, a->geo,
+                          a->geo_elem, a->weights, a->nodes);
+  if (rc) return rc;
+  if (a->geo_mode == SFEM_GEO_BOX) {
+    set_error("sfem_helmholtz_sens: does not take SFEM_GEO_BOX");
+    return SFEM_EUNSUPPORTED;
+  }
+  const int64_t work = a->elem_list ? a->num_listed : a->num_elements;
+  SFEM_REQUIRE(work >= 0 && work <= a->num_elements,
+               "sfem_helmholtz_sens: bad element list length");
+  if (work == 0) return SFEM_OK;
+  auto run = [&](auto zero) -> int {
+    using T = decltype(zero);
+    HelmholtzSensParams<T> prm{};
+    prm.u = (const T*)a->u; prm.lam = (const T*)a->lam;
+    prm.dkappa = (T*)a->dkappa; prm.dsigma = (T*)a->dsigma;
+    prm.dbeta = (T*)a->dbeta;
+    prm.geo = (const T*)a->geo; prm.geo_elem = (const T*)a->geo_elem;
+    prm.geo_index = a->geo_index; prm.geo_mode = a->geo_mode;
+    prm.dmat_host = (const T*)a->dmat; prm.weights_host = (const T*)a->weights;
+    prm.nodes_host = (const T*)a->nodes; prm.num_elements = work;
+    prm.elem_list = a->elem_list; prm.ncomp = 1; prm.node_stride = 1;
+    prm.comp_stride = 1; prm.lambda0 = (T)a->lambda0;
+    prm.lambda1 = (T)a->lambda1;
+    if (a->ndim == 3)
+      return dispatch_helmholtz_sens<T, 3>(prm, a->P, as_stream(stream));
+    return dispatch_helmholtz_sens<T, 2>(prm, a->P, as_stream(stream));
+  };
+  if (a->dtype == SFEM_F64) return run(double(0));
+  return run(float(0));
 }
 
 }  // extern "C"

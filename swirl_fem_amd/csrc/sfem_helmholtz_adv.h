@@ -20,6 +20,19 @@
 // (one form bounds the number of instantiations: Python expands scalars and
 // per-element values).  The derivative lines are always computed (C_b needs
 // them when lambda1 = 0 as well); lambda0 is tested at run time.
+//
+// TR: the transposed advective term.  B_c and A_k are symmetric, and
+//   (C_b^T v)_i = sum_q (sum_d beta[q,d] D_d phi_i(q)) v(q),
+// so at a point beta[q,d] * v(q) joins the reference-space flux of direction
+// d ahead of the transposed derivative lines and nothing joins the mass-like
+// accumulator.  For that the flux carries lambda1 from the pointwise stage on
+// (lambda1 k G g) and the final accumulation adds the transposed-derivative
+// sum unscaled.  A template argument, not a run-time flag: tested at run time
+// (wave-uniform) the forward kernels lost registers to the three beta values
+// and u that stay live across the geometry evaluation (fp64 3D affine, P = 8:
+// 192 -> 348 bytes of scratch per lane; P = 12: 0 -> 180; P = 4: 102 -> 118
+// VGPRs), so the forward instantiations compile from the code they always
+// had.
 #pragma once
 #include "sfem_helmholtz.h"
 
@@ -32,7 +45,7 @@ struct HelmholtzAdvParams : HelmholtzParams<T> {
   const T* beta;         // folded velocity (E, N, DIM), slot order
 };
 
-template <typename T, int P, int DIM, bool GS, int GM>
+template <typename T, int P, int DIM, bool GS, int GM, bool TR = false>
 __global__ void __launch_bounds__((HelmholtzTile<T, P, DIM>::BLOCK),
                                   (HelmholtzTile<T, P, DIM>::MINW))
 helmholtz_adv_kernel(HelmholtzAdvParams<T> prm, DMat<T, P> dm) {
@@ -160,9 +173,12 @@ helmholtz_adv_kernel(HelmholtzAdvParams<T> prm, DMat<T, P> dm) {
       const T g0 = d0[a], g1 = s0[o];
       [[maybe_unused]] T g2 = T(0);
       if constexpr (DIM == 3) g2 = s1[o];
-      T adv = bpt[q * DIM] * g0 + bpt[q * DIM + 1] * g1;
-      if constexpr (DIM == 3) adv += bpt[q * DIM + 2] * g2;
-      const T kq = kpt ? kpt[q] : T(1);
+      T adv = T(0);
+      if constexpr (!TR) {
+        adv = bpt[q * DIM] * g0 + bpt[q * DIM + 1] * g1;
+        if constexpr (DIM == 3) adv += bpt[q * DIM + 2] * g2;
+      }
+      const T kq = (TR ? prm.lambda1 : T(1)) * (kpt ? kpt[q] : T(1));
       T Wm;
       if constexpr (GM == GEO_MULTILINEAR && DIM == 3) {
         T o0, o1, o2;
@@ -179,6 +195,11 @@ helmholtz_adv_kernel(HelmholtzAdvParams<T> prm, DMat<T, P> dm) {
           w0[a] = kq * (G[0] * g0 + G[1] * g1);
           s0[o] = kq * (G[1] * g0 + G[3] * g1);
         }
+      }
+      if constexpr (TR) {     // beta * u joins the flux, after the geometry
+        w0[a] += bpt[q * DIM] * ua[a];
+        s0[o] += bpt[q * DIM + 1] * ua[a];
+        if constexpr (DIM == 3) s1[o] += bpt[q * DIM + 2] * ua[a];
       }
       if (has_mass) {
         if (cpt) Wm *= cpt[q];
@@ -215,7 +236,7 @@ helmholtz_adv_kernel(HelmholtzAdvParams<T> prm, DMat<T, P> dm) {
       const int o = a * SA + i * SB + j;
       T v = dt0[a] + s0[o];
       if (DIM == 3) v += s1[o];
-      acc[a] += prm.lambda1 * v;
+      acc[a] += TR ? v : prm.lambda1 * v;   // TR: lambda1 rode in with the flux
     }
   }
   // direct-stiffness summation in slot order
@@ -243,7 +264,7 @@ helmholtz_adv_kernel(HelmholtzAdvParams<T> prm, DMat<T, P> dm) {
 #undef SFEM_ADV_LINE_APPLY
 }
 
-template <typename T, int P, int DIM, bool GS>
+template <typename T, int P, int DIM, bool GS, bool TR>
 int launch_helmholtz_adv(const HelmholtzAdvParams<T>& prm, hipStream_t stream) {
   using Tile = HelmholtzTile<T, P, DIM>;
   const int64_t groups = (prm.num_elements + Tile::EPB - 1) / Tile::EPB;
@@ -255,8 +276,8 @@ int launch_helmholtz_adv(const HelmholtzAdvParams<T>& prm, hipStream_t stream) {
       make_dmat<T, P>(prm.dmat_host, prm.weights_host, prm.nodes_host);
   const dim3 grid((unsigned)groups), block(Tile::BLOCK);
 #define SFEM_LAUNCH_ADV(GMV)                                                  \
-  hipLaunchKernelGGL((helmholtz_adv_kernel<T, P, DIM, GS, GMV>), grid, block, \
-                     0, stream, prm, dm)
+  hipLaunchKernelGGL((helmholtz_adv_kernel<T, P, DIM, GS, GMV, TR>), grid,    \
+                     block, 0, stream, prm, dm)
   switch (prm.geo_mode) {
     case GEO_POINT: SFEM_LAUNCH_ADV(GEO_POINT); break;
     case GEO_AFFINE: SFEM_LAUNCH_ADV(GEO_AFFINE); break;
@@ -270,17 +291,21 @@ int launch_helmholtz_adv(const HelmholtzAdvParams<T>& prm, hipStream_t stream) {
 // Defined once per (dtype, ndim) translation unit, P = 2..12.
 template <typename T, int DIM>
 int dispatch_helmholtz_adv(const HelmholtzAdvParams<T>& prm, int P, bool gs,
-                           hipStream_t stream);
+                           bool transpose, hipStream_t stream);
 
 #define SFEM_HELMHOLTZ_ADV_CASE(PP)                                         \
   case PP:                                                                  \
-    return gs ? launch_helmholtz_adv<T, PP, DIM, true>(prm, stream)         \
-              : launch_helmholtz_adv<T, PP, DIM, false>(prm, stream);
+    if (transpose)                                                          \
+      return gs ? launch_helmholtz_adv<T, PP, DIM, true, true>(prm, stream) \
+                : launch_helmholtz_adv<T, PP, DIM, false, true>(prm,        \
+                                                                stream);    \
+    return gs ? launch_helmholtz_adv<T, PP, DIM, true, false>(prm, stream)  \
+              : launch_helmholtz_adv<T, PP, DIM, false, false>(prm, stream);
 
 #define SFEM_DEFINE_HELMHOLTZ_ADV_DISPATCH(TYPE, DIMV)                      \
   template <>                                                               \
   int dispatch_helmholtz_adv<TYPE, DIMV>(                                   \
-      const HelmholtzAdvParams<TYPE>& prm, int P, bool gs,                  \
+      const HelmholtzAdvParams<TYPE>& prm, int P, bool gs, bool transpose,  \
       hipStream_t stream) {                                                 \
     using T = TYPE;                                                         \
     constexpr int DIM = DIMV;                                               \

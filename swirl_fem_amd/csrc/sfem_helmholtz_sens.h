@@ -1,0 +1,258 @@
+// Coefficient sensitivities of the Helmholtz operator with an advective term,
+// element-local:  for A(k, c, beta) = lambda0 B_c + lambda1 A_k + C_beta and
+// two fields u, lam given on the operator's point grid, per point q
+//
+//   dkappa[q]   = d(lam . A u)/dk[q]      = lambda1 g_lam(q) . G(q) g_u(q)
+//   dsigma[q]   = d(lam . A u)/dc[q]      = lambda0 W(q) lam(q) u(q)
+//   dbeta[q,d]  = d(lam . A u)/dbeta[q,d] = lam(q) (D_d u)(q)
+//
+// with g_u, g_lam the reference-space gradients and G, W the geometric factors
+// WITHOUT any coefficient folded in.  No gather and no scatter: inputs and
+// outputs are (E, N[, DIM]) arrays indexed by element id.
+//
+// helmholtz_sens_kernel shares lane mapping, LDS tensor pair and device
+// functions (ElemGeom, line_apply*, HelmholtzTile) with helmholtz_adv_kernel.
+// The derivative stage runs once per field: the DIM * P derivatives of u are
+// kept in registers while those of lam go through the LDS pair again, so a
+// lane holds 6 P values (u, lam, three derivatives of u, the axis-0 derivative
+// of lam) next to the 2 P of a line product.  That is more than the register
+// budget of the operator kernels' launch bounds admits in fp64 from P = 7 on,
+// so the kernel asks for fewer waves per SIMD there (SensTile::MINW).
+// Outputs are written in the plane layout the per-point coefficients are read
+// in: lane t of slice a writes point a * TPE + t (coalesced), dbeta as DIM
+// consecutive reals.  An output pointer that is null skips its product and
+// its stores.
+#pragma once
+#include "sfem_helmholtz.h"
+
+namespace sfem {
+
+template <typename T>
+struct HelmholtzSensParams : HelmholtzParams<T> {
+  const T* lam;          // second field (E, N); the first is `u`
+  T* dkappa;             // (E, N) or null
+  T* dsigma;             // (E, N) or null
+  T* dbeta;              // (E, N, DIM) or null
+};
+
+template <typename T, int P>
+struct SensTile {
+  // waves per SIMD asked of the register allocator: 6 P + 2 P live values
+  static constexpr int MINW =
+      sizeof(T) == 8 ? (P <= 6 ? 4 : 2) : (P <= 8 ? 4 : 2);
+};
+
+template <typename T, int P, int DIM, int GM>
+__global__ void __launch_bounds__((HelmholtzTile<T, P, DIM>::BLOCK),
+                                  (SensTile<T, P>::MINW))
+helmholtz_sens_kernel(HelmholtzSensParams<T> prm, DMat<T, P> dm) {
+  using PRM = HelmholtzSensParams<T>;
+  using Tile = HelmholtzTile<T, P, DIM, true>;
+  constexpr int TPE = Tile::TPE, SA = Tile::SA, SB = Tile::SB;
+  constexpr int EPB = Tile::EPB, W = Tile::ELEM_WORDS;
+  constexpr int N = DIM == 3 ? P * P * P : P * P;        // points per element
+  __shared__ T lds[2 * EPB * W];
+
+  const int tid = threadIdx.x;
+  const int el = tid / TPE;                 // element within the workgroup
+  const int t = tid - el * TPE;             // lane within the element
+  const int i = DIM == 3 ? t / P : 0;
+  const int j = DIM == 3 ? t - i * P : t;
+  const bool lane_ok = el < EPB;            // tail lanes of a padded block
+  const int64_t work = (int64_t)blockIdx.x * EPB + (lane_ok ? el : 0);
+  const bool active = lane_ok && work < prm.num_elements;
+  const int64_t e =
+      prm.elem_list ? (active ? (int64_t)prm.elem_list[work] : 0) : work;
+
+  T* s0 = lds + (lane_ok ? el : 0) * 2 * W;    // becomes the axis-1 result
+  T* s1 = s0 + W;                              // becomes the axis-2 result
+  const DMat<T, P>& dmat = dm;
+  // fp32, P >= 9: matrix entries from the kernarg segment, as the parent does
+#if SFEM_DMAT_MEM
+#define SFEM_SENS_LINE_APPLY(X, Y)                                            \
+  do {                                                                        \
+    if constexpr (P >= 9 && sizeof(T) == 4)                                   \
+      line_apply_mem<T, P, false>(                                            \
+          (const SFEM_CONSTANT_AS DMat<T, P>*)((                              \
+              const SFEM_CONSTANT_AS char*)                                   \
+                  __builtin_amdgcn_kernarg_segment_ptr() +                    \
+              sizeof(PRM)),                                                   \
+          X, Y);                                                              \
+    else                                                                      \
+      line_apply<T, P, false>(dmat, X, Y);                                    \
+  } while (0)
+#else
+#define SFEM_SENS_LINE_APPLY(X, Y) line_apply<T, P, false>(dmat, X, Y)
+#endif
+  const bool want_k = prm.dkappa != nullptr;
+  const bool want_c = prm.dsigma != nullptr;
+  const bool want_b = prm.dbeta != nullptr;
+
+  ElemGeom<T, P, DIM, GM> geom;
+#if SFEM_KERNARG_PICK
+  static_assert(sizeof(PRM) % alignof(DMat<T, P>) == 0, "");
+  geom.template init<true>(prm, dm, e, active, i, j, t,
+                           kernarg_dmat<T, P>(sizeof(PRM)));
+#else
+  geom.init(prm, dm, e, active, i, j, t);
+#endif
+  const uint32_t slot_off = (uint32_t)t;
+  const T* up = prm.u + e * N;
+  const T* lp = prm.lam + e * N;
+
+  // derivative stage of one field: x[a] = the lane's values (a, i, j) in,
+  // dx0[a] = its axis-0 derivative out; the axis-1 / axis-2 derivatives at
+  // (a, i, j) are left in s0 / s1
+  auto derivatives = [&](const T (&x)[P], T (&dx0)[P]) {
+    SFEM_SENS_LINE_APPLY(x, dx0);
+    if (lane_ok) {
+#pragma unroll
+      for (int a = 0; a < P; ++a) {
+        s0[a * SA + i * SB + j] = x[a];
+        if (DIM == 3) s1[a * SA + i * SB + j] = x[a];
+      }
+    }
+    __syncthreads();
+    if (lane_ok) {  // last axis: lane owns the line [i, j, *] (3D) / [j, *]
+      T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
+      T xx[P], yy[P];
+#pragma unroll
+      for (int m = 0; m < P; ++m) xx[m] = line[m];
+      SFEM_SENS_LINE_APPLY(xx, yy);
+#pragma unroll
+      for (int m = 0; m < P; ++m) line[m] = yy[m];
+    }
+    if (DIM == 3 && lane_ok) {  // middle axis: lane owns the line [i, *, j]
+      T* line = s0 + i * SA + j;
+      T xx[P], yy[P];
+#pragma unroll
+      for (int m = 0; m < P; ++m) xx[m] = line[m * SB];
+      SFEM_SENS_LINE_APPLY(xx, yy);
+#pragma unroll
+      for (int m = 0; m < P; ++m) line[m * SB] = yy[m];
+    }
+    __syncthreads();
+  };
+
+  T ua[P], gu0[P], gu1[P];
+  [[maybe_unused]] T gu2[DIM == 3 ? P : 1];
+#pragma unroll
+  for (int a = 0; a < P; ++a)
+    ua[a] = active ? up[slot_off + a * TPE] : T(0);
+  derivatives(ua, gu0);
+#pragma unroll
+  for (int a = 0; a < P; ++a) {
+    const int o = a * SA + i * SB + j;
+    gu1[a] = lane_ok ? s0[o] : T(0);
+    if constexpr (DIM == 3) gu2[a] = lane_ok ? s1[o] : T(0);
+  }
+  __syncthreads();        // every lane has read u's derivatives: reuse the pair
+
+  T la[P], gl0[P] = {};
+#pragma unroll
+  for (int a = 0; a < P; ++a)
+    la[a] = active ? lp[slot_off + a * TPE] : T(0);
+  // lam's derivatives feed dkappa only
+  if (want_k) derivatives(la, gl0);
+
+  if (active) {
+    T* kout = want_k ? prm.dkappa + e * N : nullptr;
+    T* sout = want_c ? prm.dsigma + e * N : nullptr;
+    T* bout = want_b ? prm.dbeta + e * N * DIM : nullptr;
+#pragma unroll
+    for (int a = 0; a < P; ++a) {
+      const int o = a * SA + i * SB + j;
+      const uint32_t q = slot_off + a * TPE;
+      if (want_b) {
+        bout[q * DIM] = la[a] * gu0[a];
+        bout[q * DIM + 1] = la[a] * gu1[a];
+        if constexpr (DIM == 3) bout[q * DIM + 2] = la[a] * gu2[a];
+      }
+      if (!want_k && !want_c) continue;
+      T Wm = T(0);
+      if (want_k) {
+        const T h0 = gl0[a], h1 = s0[o];
+        T dk;
+        if constexpr (GM == GEO_MULTILINEAR && DIM == 3) {
+          T o0, o1, o2;
+          geom.apply_multilinear3(dm, a, want_c, gu0[a], gu1[a], gu2[a], o0, o1,
+                                  o2, Wm);
+          dk = h0 * o0 + h1 * o1 + s1[o] * o2;
+        } else {
+          T G[6];
+          geom.factors(dm, a, true, want_c, G, Wm);
+          if constexpr (DIM == 3) {
+            const T h2 = s1[o];
+            dk = h0 * (G[0] * gu0[a] + G[1] * gu1[a] + G[2] * gu2[a]) +
+                 h1 * (G[1] * gu0[a] + G[3] * gu1[a] + G[4] * gu2[a]) +
+                 h2 * (G[2] * gu0[a] + G[4] * gu1[a] + G[5] * gu2[a]);
+          } else {
+            dk = h0 * (G[0] * gu0[a] + G[1] * gu1[a]) +
+                 h1 * (G[1] * gu0[a] + G[3] * gu1[a]);
+          }
+        }
+        kout[q] = prm.lambda1 * dk;
+      } else {
+        T G[6];
+        geom.factors(dm, a, false, true, G, Wm);
+      }
+      if (want_c) sout[q] = prm.lambda0 * Wm * la[a] * ua[a];
+    }
+  }
+#undef SFEM_SENS_LINE_APPLY
+}
+
+template <typename T, int P, int DIM>
+int launch_helmholtz_sens(const HelmholtzSensParams<T>& prm,
+                          hipStream_t stream) {
+  using Tile = HelmholtzTile<T, P, DIM>;
+  const int64_t groups = (prm.num_elements + Tile::EPB - 1) / Tile::EPB;
+  if (groups > 0x7fffffff) {
+    set_error("helmholtz_sens: too many workgroups (%lld)", (long long)groups);
+    return SFEM_EINVAL;
+  }
+  const DMat<T, P> dm =
+      make_dmat<T, P>(prm.dmat_host, prm.weights_host, prm.nodes_host);
+  const dim3 grid((unsigned)groups), block(Tile::BLOCK);
+#define SFEM_LAUNCH_SENS(GMV)                                                 \
+  hipLaunchKernelGGL((helmholtz_sens_kernel<T, P, DIM, GMV>), grid, block, 0, \
+                     stream, prm, dm)
+  switch (prm.geo_mode) {
+    case GEO_POINT: SFEM_LAUNCH_SENS(GEO_POINT); break;
+    case GEO_AFFINE: SFEM_LAUNCH_SENS(GEO_AFFINE); break;
+    default: SFEM_LAUNCH_SENS(GEO_MULTILINEAR); break;
+  }
+#undef SFEM_LAUNCH_SENS
+  SFEM_LAUNCH_CHECK();
+  return SFEM_OK;
+}
+
+// Defined once per (dtype, ndim) translation unit, P = 2..12.
+template <typename T, int DIM>
+int dispatch_helmholtz_sens(const HelmholtzSensParams<T>& prm, int P,
+                            hipStream_t stream);
+
+#define SFEM_HELMHOLTZ_SENS_CASE(PP) \
+  case PP: return launch_helmholtz_sens<T, PP, DIM>(prm, stream);
+
+#define SFEM_DEFINE_HELMHOLTZ_SENS_DISPATCH(TYPE, DIMV)                     \
+  template <>                                                               \
+  int dispatch_helmholtz_sens<TYPE, DIMV>(                                  \
+      const HelmholtzSensParams<TYPE>& prm, int P, hipStream_t stream) {    \
+    using T = TYPE;                                                         \
+    constexpr int DIM = DIMV;                                               \
+    switch (P) {                                                            \
+      SFEM_HELMHOLTZ_SENS_CASE(2) SFEM_HELMHOLTZ_SENS_CASE(3)               \
+      SFEM_HELMHOLTZ_SENS_CASE(4) SFEM_HELMHOLTZ_SENS_CASE(5)               \
+      SFEM_HELMHOLTZ_SENS_CASE(6) SFEM_HELMHOLTZ_SENS_CASE(7)               \
+      SFEM_HELMHOLTZ_SENS_CASE(8) SFEM_HELMHOLTZ_SENS_CASE(9)               \
+      SFEM_HELMHOLTZ_SENS_CASE(10) SFEM_HELMHOLTZ_SENS_CASE(11)             \
+      SFEM_HELMHOLTZ_SENS_CASE(12)                                          \
+      default:                                                              \
+        set_error("helmholtz_sens: P=%d outside the compiled range 2..12",  \
+                  P);                                                       \
+        return SFEM_EUNSUPPORTED;                                           \
+    }                                                                       \
+  }
+
+}  // namespace sfem

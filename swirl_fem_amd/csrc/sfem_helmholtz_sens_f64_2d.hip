@@ -1,0 +1,6 @@
+// Instantiations of the Helmholtz coefficient-sensitivity kernel: double, 2D,
+// P = 2..12.
+#include "sfem_helmholtz_sens.h"
+namespace sfem {
+SFEM_DEFINE_HELMHOLTZ_SENS_DISPATCH(double, 2)
+}  // namespace sfem

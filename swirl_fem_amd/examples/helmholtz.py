@@ -42,6 +42,16 @@ On a mesh with periodic images the unknowns are the lowest-numbered node of
 each class: K = R QQ^T A QQ^T R^T with R the restriction to those nodes
 (QQ^T copies a class's only nonzero value to all its images), which keeps K
 symmetric for CG; the result is copied back to the images.
+
+Differentiation.  `solve_helmholtz` is differentiable with
+respect to `forcing` and to tensor-valued `diffusivity`, `reaction` and
+`velocity` that require grad.  With u_bar the cotangent of u, backward solves
+the transposed masked system K^T lam = mask u_bar with the forward solve's
+solver, tolerances and preconditioner (CG without a velocity, BiCGStab on the
+transposed operator with one), then forcing_bar = B lam and theta_bar =
+-d(lam . A(theta) u)/d theta with the full u = w + u_D (`op.sensitivity`),
+which covers the lift.  Neumann and Robin data are the flux k du/dn, so the
+right-hand side carries no further dependence on k.
 """
 
 from __future__ import annotations
@@ -75,6 +85,69 @@ def _nodal_values(mesh: Mesh, value, dtype, device) -> torch.Tensor:
     raise ValueError(f'a Dirichlet value must be a scalar, ({mesh.num_nodes},) '
                      f'nodal values or a callable; got {tuple(v.shape)}')
   return v
+
+
+def _requires_grad(*values) -> bool:
+  return torch.is_grad_enabled() and any(
+      isinstance(v, torch.Tensor) and v.requires_grad for v in values)
+
+
+def _detached(v):
+  return v.detach() if isinstance(v, torch.Tensor) else v
+
+
+class _HelmholtzSolve(torch.autograd.Function):
+  """`_solve` as one autograd node: the adjoint solve and the coefficient
+  sensitivities in `backward`."""
+
+  @staticmethod
+  def forward(ctx, forcing, diffusivity, reaction, velocity, mesh,
+              boundary_conditions, kwargs, holder):
+    state = {}
+    u, info = _solve(mesh, _detached(forcing), boundary_conditions,
+                     diffusivity=_detached(diffusivity),
+                     reaction=_detached(reaction),
+                     velocity=_detached(velocity), return_info=True,
+                     _state=state, **kwargs)
+    holder['info'] = info
+    ctx.state = state
+    ctx.save_for_backward(u)
+    ctx.like = [(v.dtype, v.device) if isinstance(v, torch.Tensor) else None
+                for v in (forcing, diffusivity, reaction, velocity)]
+    return u
+
+  @staticmethod
+  @torch.autograd.function.once_differentiable
+  def backward(ctx, u_bar):
+    st = ctx.state
+    l0, l1 = st['lambda0'], st['lambda1']
+    op, keep = st['op'], st['keep']
+    rhs = (u_bar.detach().to(keep.dtype) * keep).contiguous()
+    if st['advection']:
+      if st['rmass']:
+        At = lambda x: st['add_robin'](x, op.apply_transpose(x, l0, l1))
+      else:
+        At = op.linear_operator(l0, l1, transpose=True)
+      lam, info = bicgstab(At, rhs, tol=st['rtol'], atol=st['atol'],
+                           M=st['M'])
+    else:
+      lam, info = cg(st['K'], rhs, tol=st['rtol'], atol=st['atol'],
+                     M=st['M'])
+    st['adjoint_info'] = info
+    need = ctx.needs_input_grad
+    grads = [None, None, None, None]
+    if need[0]:
+      grads[0] = st['Bf'](lam)
+    if any(need[1:4]):
+      sens = op.sensitivity(ctx.saved_tensors[0], lam, l0, l1,
+                            want=tuple(need[1:4]))
+      for n, g in enumerate(sens):
+        if need[1 + n] and g is not None:
+          grads[1 + n] = -g
+    for n, like in enumerate(ctx.like):
+      if grads[n] is not None and like is not None:
+        grads[n] = grads[n].to(dtype=like[0], device=like[1])
+    return (*grads, None, None, None, None)
 
 
 def solve_helmholtz(mesh: Mesh, forcing,
@@ -115,7 +188,42 @@ def solve_helmholtz(mesh: Mesh, forcing,
   `preconditioner`: None, 'jacobi' or 'pmg', as in `solve_poisson` (on a
   mesh without periodic images).  `rtol` is relative to the norm of the
   lifted right-hand side; `info` is CG's (BiCGStab's with a velocity).
+
+  Autograd: the result is differentiable with respect to `forcing` and to
+  `diffusivity`, `reaction` and `velocity` given as tensors that require grad
+  (any of their tensor forms; the gradient has the form passed in).  Backward
+  is one adjoint solve with the forward solve's solver, `rtol`, `atol` and
+  `preconditioner` plus the sensitivity kernel (`op.sensitivity`).  Gradients
+  with respect to boundary data (Dirichlet, Neumann, Robin values) and
+  through callables are not propagated, nor are second derivatives.  It
+  needs the fused operator and a mesh without periodic images
+  (NotImplementedError otherwise).  When nothing requires grad the solve
+  runs exactly as without this feature and builds no autograd node.
   """
+  kwargs = dict(lambda0=lambda0, lambda1=lambda1, rtol=rtol, atol=atol,
+                preconditioner=preconditioner)
+  if not _requires_grad(forcing, diffusivity, reaction, velocity):
+    return _solve(mesh, forcing, boundary_conditions, diffusivity=diffusivity,
+                  reaction=reaction, velocity=velocity,
+                  return_info=return_info, **kwargs)
+  gi = mesh.exchange_gather_indices
+  if gi is not None and gi.numel() > 0:
+    raise NotImplementedError('gradients of solve_helmholtz on a mesh with '
+                              'periodic images')
+  holder = {}
+  u = _HelmholtzSolve.apply(forcing, diffusivity, reaction, velocity, mesh,
+                            boundary_conditions, kwargs, holder)
+  return (u, holder['info']) if return_info else u
+
+
+def _solve(mesh: Mesh, forcing,
+           boundary_conditions: Mapping[str, Tuple[BCType, BCValue]],
+           *, lambda0: float = 0.0, lambda1: float = 1.0,
+           rtol: float = 1e-5, atol: float = 0.,
+           return_info: bool = False, preconditioner=None,
+           diffusivity=None, reaction=None, velocity=None, _state=None):
+  """The body of `solve_helmholtz`.  `_state`: a dict that receives what the
+  adjoint solve needs (the operators, the mask, the preconditioner)."""
   if preconditioner not in (None, 'jacobi', 'pmg'):
     raise ValueError(f'unknown preconditioner {preconditioner!r}')
   if mesh.axis_name is not None or mesh.neighbor_plan is not None:
@@ -260,6 +368,10 @@ def solve_helmholtz(mesh: Mesh, forcing,
     raise NotImplementedError(
         'diffusivity / reaction need the fused operator: '
         f'{operators.supports_two_grid(fespace)}')
+  elif _state is not None:
+    raise NotImplementedError(
+        'gradients of solve_helmholtz need the fused operator: '
+        f'{operators.supports_two_grid(fespace)}')
   else:
     def l(u, v):
       return lambda x: u(x) * v(x)
@@ -303,6 +415,10 @@ def solve_helmholtz(mesh: Mesh, forcing,
   if periodic:
     w = mesh.exchange(w)
   u = w + u_D
+  if _state is not None:
+    _state.update(op=op, K=K, Bf=Bf, M=M, keep=keep, rmass=rmass,
+                  add_robin=add_robin, advection=advection, lambda0=lambda0,
+                  lambda1=lambda1, rtol=rtol, atol=atol)
   if return_info:
     return u, info
   return u

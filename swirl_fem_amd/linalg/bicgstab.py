@@ -187,4 +187,36 @@ def bicgstab(A, b, x0=None, *, tol=1e-5, atol=0.0, maxiter=None, M=None,
   return run.x, info
 
 
-__all__ = ['BiCGStabRunner', 'bicgstab']
+class _TransposeSolve(torch.autograd.Function):
+  """x = A^-1 b with the adjoint A^-T g solved by the same routine on At."""
+
+  @staticmethod
+  def forward(ctx, b, A, At, kwargs, info_out):
+    x, info = bicgstab(A, b.detach(), **kwargs)
+    if info_out is not None:
+      info_out.update(info)
+    ctx.At, ctx.kwargs = At, kwargs
+    return x
+
+  @staticmethod
+  @torch.autograd.function.once_differentiable
+  def backward(ctx, grad_x):
+    # d<x, g>/db = A^-T g
+    grad_b, _ = bicgstab(ctx.At, grad_x.detach().contiguous(), **ctx.kwargs)
+    return grad_b, None, None, None, None
+
+
+def transpose_solve(A, At, b, info_out=None, **kwargs):
+  """`bicgstab(A, b, **kwargs)[0]` that autograd can differentiate with
+  respect to `b`: the cotangent is obtained by a second BiCGStab solve with
+  `At`, a callable that applies the transpose of `A` (for a Helmholtz
+  operator with a velocity: `op.linear_operator(l0, l1, transpose=True)`) --
+  the counterpart of `linalg.cg.symmetric_solve` for operators that are not
+  symmetric.  The same `kwargs` (tolerances, `M`, `maxiter`) serve both
+  solves; a preconditioner `M` should suit both A and A^T, as a Jacobi
+  diagonal does.  Gradients with respect to tensors hidden inside `A` are not
+  propagated.  `info_out`: a dict that receives the forward solve's `info`."""
+  return _TransposeSolve.apply(b, A, At, kwargs, info_out)
+
+
+__all__ = ['BiCGStabRunner', 'bicgstab', 'transpose_solve']

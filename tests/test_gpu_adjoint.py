@@ -1,0 +1,614 @@
+"""The adjoint side of the Helmholtz family on the GPU: the
+transposed operator, the coefficient-sensitivity kernel, `op.sensitivity`,
+`transpose_solve` and the gradients of `solve_helmholtz`, against the NumPy
+reference `tests/adjoint_reference.py`."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from swirl_fem_amd import _lib, _ops
+from swirl_fem_amd.core import operators
+from swirl_fem_amd.core.fespace import FiniteElementSpace
+from swirl_fem_amd.core.interpolation import NodeType, Quadrature1D
+from swirl_fem_amd.examples.helmholtz import BCType, solve_helmholtz
+from tests import adjoint_reference as AJ
+from tests import geometry_cases as G
+from tests.fp32util import F32Rng, f32r, tolerance
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+GLL, GL = NodeType.GAUSS_LOBATTO_LEGENDRE, NodeType.GAUSS_LEGENDRE
+F64, F32 = torch.float64, torch.float32
+ORDERS = [(ndim, P) for ndim in (2, 3) for P in range(2, 13)]
+
+
+def _dev(a, dtype=F64):
+  return torch.as_tensor(np.asarray(a), dtype=dtype, device=DEV)
+
+
+def _np(t):
+  return t.detach().double().cpu().numpy()
+
+
+def _rel(a, b):
+  return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
+
+
+def _tol(dtype, P):
+  """fp64: 1e-11, the bound of the forward advection tests; fp32: the
+  project's 1e-5 (2e-5 at P >= 11)."""
+  return 1e-11 if dtype == F64 else tolerance(F32, P)
+
+
+@functools.lru_cache(maxsize=None)
+def _setup(name, ndim, P, quad, dtype):
+  """(mesh, boundary mask, fespace, reference space) of one geometry case,
+  made once and shared by the tests (none of which changes it)."""
+  n = 3 if name in ('three_kinds', 'affine_curved') else 2
+  case = getattr(G, name)(n, ndim, P)
+  mesh, bm, rp = case.finalize(DEV, dtype)
+  q = (Quadrature1D.create(P, GLL) if quad is None
+       else Quadrature1D.create(quad, GL))
+  fes = FiniteElementSpace.create(mesh, q)
+  ref = AJ.space(rp.node_coords, rp.elements, P,
+                 (P, 'gll') if quad is None else (quad, 'gl'))
+  return mesh, bm, fes, ref
+
+
+def _coefficients(ref, rng, r=lambda x: x):
+  """Per-point k, per-element c, per-point b on the reference's points."""
+  xq = AJ.quad_points(ref)
+  E, Q, d = xq.shape
+  k = r(1.0 + xq[..., 0] ** 2 + 0.5 * np.sin(3.0 * xq[..., 0]))
+  c = r(0.5 + rng.random(E))
+  b = r(np.stack([1.0 + xq[..., 0] * xq[..., d - 1],
+                  np.sin(2.0 * xq[..., 0]) - 0.5] +
+                 ([0.5 - xq[..., 1] ** 2 + xq[..., 2]] if d == 3 else []),
+                 axis=-1))
+  return k, c, b
+
+
+# ------------------------------------------- 1. transposed apply vs reference
+@pytest.mark.parametrize('ndim,P', ORDERS)
+def test_transpose_matches_reference(ndim, P):
+  """Every order on the mesh that holds all three geometry kinds: geometry
+  'auto' / 'multilinear' / 'stored', atomic and coloured assembly, masked and
+  unmasked, velocity alone and with per-point k and per-element c, both
+  lambdas zero in turn, `apply_local`; fp64, 1e-11."""
+  mesh, bm, fes, ref = _setup('three_kinds', ndim, P, None, F64)
+  rng = np.random.default_rng(P + 10 * ndim)
+  k, c, b = _coefficients(ref, rng)
+  E, Q = k.shape
+  cq = AJ.expand_coefficient(c, E, Q)
+  v = rng.standard_normal(mesh.num_nodes)
+  keep = 1.0 - _np(bm)
+  worst = 0.0
+  for geometry in ('auto', 'multilinear', 'stored'):
+    # coloured assembly differs in the launch lists only: once, on the mesh
+    # split that has the most launches
+    for assembly in ('atomic', 'colored') if geometry == 'auto' else (
+        'atomic',):
+      op = fes.helmholtz_operator(bm, geometry, assembly, diffusivity=_dev(k),
+                                  reaction=_dev(c), velocity=_dev(b))
+      assert isinstance(op, operators.HelmholtzOperator)
+      for l0, l1 in ((0.7, 1.3), (0.7, 0.0), (0.0, 1.3)):
+        got = _np(op.apply_transpose(_dev(v), l0, l1))
+        want = AJ.apply_transpose(ref, v, l0, l1, k, cq, b, keep)
+        worst = max(worst, _rel(got, want))
+        assert _rel(got, want) <= 1e-11, (geometry, assembly, l0, l1)
+      # (atomic assembly: two applies agree to rounding, not bitwise)
+      lin = op.linear_operator(0.7, 1.3, transpose=True)
+      assert _rel(_np(lin(_dev(v))),
+                  _np(op.apply_transpose(_dev(v), 0.7, 1.3))) <= 1e-13
+    # the velocity alone, no mask; the element-local form
+    op = fes.helmholtz_operator(None, geometry, velocity=_dev(b))
+    got = _np(op.apply_transpose(_dev(v), 0.7, 1.3))
+    assert _rel(got, AJ.apply_transpose(ref, v, 0.7, 1.3, b_q=b)) <= 1e-11
+    vl = ref.gather(v)
+    got = _np(op.apply_local(_dev(vl), 0.7, 1.3, transpose=True))
+    want = AJ.local_apply_transpose(ref, vl, 0.7, 1.3, b_q=b)
+    assert _rel(got, want) <= 1e-11, geometry
+  # the forward apply is what it was
+  got = _np(op.apply(_dev(v), 0.7, 1.3))
+  assert _rel(got, AJ.apply(ref, v, 0.7, 1.3, b_q=b)) <= 1e-11
+  print(f'ndim={ndim} P={P}: worst rel err {worst:.2e}')
+  # without a velocity the operator is symmetric: apply_transpose is apply
+  sym = fes.helmholtz_operator(bm, diffusivity=_dev(k))
+  assert sym.linear_operator(0.7, 1.3, transpose=True).op is sym
+  assert _rel(_np(sym.apply_transpose(_dev(v), 0.7, 1.3)),
+              _np(sym.apply(_dev(v), 0.7, 1.3))) <= 1e-13
+
+
+@pytest.mark.parametrize('name,ndim,P,quad', [
+    ('three_kinds', 2, 4, 5), ('three_kinds', 3, 3, 4),
+    ('multilinear', 2, 11, 12), ('affine', 3, 5, 6)])
+def test_two_grid_transpose_matches_reference(name, ndim, P, quad):
+  mesh, bm, fes, ref = _setup(name, ndim, P, quad, F64)
+  rng = np.random.default_rng(P)
+  k, c, b = _coefficients(ref, rng)
+  E, Q = k.shape
+  cq = AJ.expand_coefficient(c, E, Q)
+  v = rng.standard_normal(mesh.num_nodes)
+  u = rng.standard_normal(mesh.num_nodes)
+  for mask in (bm, None):
+    keep = None if mask is None else 1.0 - _np(mask)
+    op = fes.helmholtz_operator(mask, diffusivity=_dev(k), reaction=_dev(c),
+                                velocity=_dev(b))
+    assert isinstance(op, operators.TwoGridHelmholtzOperator)
+    for l0, l1 in ((0.7, 1.3), (0.0, 1.0)):
+      got = _np(op.apply_transpose(_dev(v), l0, l1))
+      want = AJ.apply_transpose(ref, v, l0, l1, k, cq, b, keep)
+      assert _rel(got, want) <= 1e-11, (mask is None, l0, l1)
+    lin = op.linear_operator(0.7, 1.3, transpose=True)
+    assert _rel(_np(lin(_dev(v))),
+                _np(op.apply_transpose(_dev(v), 0.7, 1.3))) <= 1e-13
+  # adjoint identity of the unmasked operator
+  au = _np(op.apply(_dev(u), 0.7, 1.3))
+  atv = _np(op.apply_transpose(_dev(v), 0.7, 1.3))
+  scale = np.linalg.norm(v) * np.linalg.norm(au)
+  assert abs(v @ au - atv @ u) <= 1e-11 * scale
+  vl = ref.gather(v)
+  got = _np(op.apply_local(_dev(vl), 0.7, 1.3, transpose=True))
+  want = AJ.local_apply_transpose(ref, vl, 0.7, 1.3, k, cq, b)
+  assert _rel(got, want) <= 1e-11
+
+
+@pytest.mark.parametrize('ndim,P', ORDERS)
+def test_transpose_fp32_within_policy(ndim, P):
+  mesh, bm, fes, ref = _setup('three_kinds', ndim, P, None, F32)
+  rng = F32Rng(P)
+  k, c, b = _coefficients(ref, rng, f32r)
+  E, Q = k.shape
+  op = fes.helmholtz_operator(None, diffusivity=_dev(k, F32),
+                              reaction=_dev(c, F32), velocity=_dev(b, F32))
+  v = rng.standard_normal(mesh.num_nodes)
+  got = _np(op.apply_transpose(_dev(v, F32), 0.7, 1.3))
+  want = AJ.apply_transpose(ref, v, 0.7, 1.3, k,
+                            AJ.expand_coefficient(c, E, Q), b)
+  err = _rel(got, want)
+  print(f'fp32 transpose ndim={ndim} P={P}: rel err {err:.3e}')
+  assert err <= tolerance(F32, P)
+
+
+# ------------------------------------------------------- 2. adjoint identity
+@pytest.mark.parametrize('ndim,P', [(2, 5), (2, 12), (3, 4), (3, 8), (3, 9)])
+def test_adjoint_identity(ndim, P):
+  """<v, A u> = <A^T v, u>: unmasked on random vectors; masked with u, v zero
+  on the Dirichlet nodes.  Both sides are sums of N products of entries of
+  size |v| |A u| / N, computed to 1e-11 each."""
+  mesh, bm, fes, ref = _setup('three_kinds', ndim, P, None, F64)
+  rng = np.random.default_rng(P)
+  k, c, b = _coefficients(ref, rng)
+  u = rng.standard_normal(mesh.num_nodes)
+  v = rng.standard_normal(mesh.num_nodes)
+  for mask in (None, bm):
+    if mask is not None:
+      u, v = u * (1.0 - _np(bm)), v * (1.0 - _np(bm))
+    for assembly in ('atomic', 'colored'):
+      op = fes.helmholtz_operator(mask, 'auto', assembly, diffusivity=_dev(k),
+                                  reaction=_dev(c), velocity=_dev(b))
+      au = _np(op.apply(_dev(u), 0.7, 1.3))
+      atv = _np(op.apply_transpose(_dev(v), 0.7, 1.3))
+      scale = np.linalg.norm(v) * np.linalg.norm(au)
+      assert abs(v @ au - atv @ u) <= 1e-11 * scale, (mask is None, assembly)
+      # not symmetric: the identity is not trivially true
+      av = _np(op.apply(_dev(v), 0.7, 1.3))
+      assert abs(v @ au - av @ u) > 1e-6 * scale
+
+
+# ------------------------------------------------ 3. axis and component cases
+@pytest.mark.parametrize('ndim', [2, 3])
+def test_one_component_one_axis(ndim):
+  """A velocity with the single non-zero component d on sheared (affine, not
+  axis-aligned) elements, the field a monomial in one coordinate m, the
+  lambdas zero so that the term stands alone: a swapped axis or a missing
+  transpose of the inverse Jacobian shows up in one of the d x m cases, for
+  the transposed apply and for dbeta[..., d] of the sensitivity kernel."""
+  P = 4
+  mesh, bm, fes, ref = _setup('affine', ndim, P, None, F64)
+  xq = AJ.quad_points(ref)
+  x = np.asarray(ref.node_coords)
+  rng = np.random.default_rng(ndim)
+  lam = rng.standard_normal(mesh.num_nodes)
+  plain = fes.helmholtz_operator(None)
+  for d in range(ndim):
+    bq = np.zeros(xq.shape)
+    bq[..., d] = 1.0 + 4.0 * xq[..., (d + 1) % ndim] ** 2
+    op = fes.helmholtz_operator(None, velocity=_dev(bq))
+    for m in range(ndim):
+      v = x[:, m] ** 2
+      got = _np(op.apply_transpose(_dev(v), 0.0, 0.0))
+      want = AJ.apply_transpose(ref, v, 0.0, 0.0, b_q=bq)
+      assert _rel(got, want) <= 1e-11, (d, m)
+      # the folded velocity with only REFERENCE component d: dbeta[..., d]
+      ul, ll = ref.gather(v), ref.gather(lam)
+      _, _, dbeta = _ops.helmholtz_sens(
+          _dev(ul), _dev(ll), plain.parts, plain.host, ndim, P, 0.0, 0.0,
+          want=(False, False, True))
+      # (a component can vanish identically -- a monomial in x_m has no
+      # derivative along another physical axis --, so the error of component
+      # d is measured against the size of the whole gradient)
+      _, _, ref_dbeta = AJ.kernel_sensitivities(ref, ul, ll, 0.0, 0.0)
+      assert np.abs(_np(dbeta)[..., d] - ref_dbeta[..., d]).max() <= \
+          1e-11 * np.abs(ref_dbeta).max(), (d, m)
+      # and through the operator: the gradient with respect to b
+      _, _, db = op.sensitivity(_dev(v), _dev(lam), 0.0, 0.0)
+      _, _, ref_db = AJ.sensitivities(ref, v, lam, 0.0, 0.0)
+      assert np.abs(_np(db)[..., d] - ref_db[..., d]).max() <= \
+          1e-11 * np.abs(ref_db).max(), (d, m)
+      assert _rel(_np(db), ref_db) <= 1e-11, (d, m)
+
+
+# ------------------------------------------- 4. sensitivity kernel vs reference
+@pytest.mark.parametrize('dtype', [F64, F32], ids=['fp64', 'fp32'])
+@pytest.mark.parametrize('ndim,P', ORDERS)
+def test_sensitivity_kernel_matches_reference(ndim, P, dtype):
+  """Every order, each geometry kind (the mesh holds all three under 'auto';
+  'multilinear' and 'stored' move the elements between the kinds), all three
+  outputs together and each alone; an output that is not asked for is not
+  written."""
+  mesh, bm, fes, ref = _setup('three_kinds', ndim, P, None, dtype)
+  rng = np.random.default_rng(P) if dtype == F64 else F32Rng(P)
+  E, n = mesh.num_elements, mesh.num_nodes_per_element
+  ul = rng.standard_normal((E, n))
+  ll = rng.standard_normal((E, n))
+  l0, l1 = 0.75, 1.25
+  want = AJ.kernel_sensitivities(ref, ul, ll, l0, l1)
+  tol = _tol(dtype, P)
+  names = ('dkappa', 'dsigma', 'dbeta')
+  for geometry in ('auto', 'multilinear', 'stored'):
+    op = fes.helmholtz_operator(None, geometry, 'atomic')
+    if geometry == 'auto' and dtype == F64:
+      # (two points per direction cannot bend an element)
+      assert op.num_affine and op.num_multilinear and (op.num_curved or P == 2)
+    run = lambda **kw: _ops.helmholtz_sens(
+        _dev(ul, dtype), _dev(ll, dtype), op.parts, op.host, ndim, P, l0, l1,
+        **kw)
+    together = run()
+    for name, g, w in zip(names, together, want):
+      err = _rel(_np(g), w)
+      print(f'{name} ndim={ndim} P={P} {geometry}: rel err {err:.2e}')
+      assert err <= tol, (name, geometry)
+    for only in range(3):
+      flags = tuple(q == only for q in range(3))
+      sentinel = [torch.full_like(t, 7.0) for t in together]
+      out = tuple(s if f else None for s, f in zip(sentinel, flags))
+      alone = run(want=flags, out=out)
+      assert alone[only] is sentinel[only]
+      # the same arithmetic, up to how the compiler contracted the copies
+      assert _rel(_np(alone[only]), _np(together[only])) <= (
+          1e-14 if dtype == F64 else 1e-6), names[only]
+      assert all(a is None for q, a in enumerate(alone) if q != only)
+      # the tensors that were not passed keep their sentinel
+      for q in range(3):
+        if q != only:
+          assert bool((sentinel[q] == 7.0).all())
+
+
+@pytest.mark.parametrize('ndim,P', [(2, 5), (3, 4), (3, 9)])
+def test_sensitivity_uses_bare_factors(ndim, P):
+  """An operator built with coefficients folds k and c into the stored factors
+  of its curved launches; the sensitivities need G and W without them
+  (`_geo_parts`)."""
+  mesh, bm, fes, ref = _setup('three_kinds', ndim, P, None, F64)
+  rng = np.random.default_rng(P)
+  k, c, b = _coefficients(ref, rng)
+  u = rng.standard_normal(mesh.num_nodes)
+  lam = rng.standard_normal(mesh.num_nodes)
+  op = fes.helmholtz_operator(bm, diffusivity=_dev(k), reaction=_dev(c),
+                              velocity=_dev(b))
+  assert op.num_curved > 0
+  dk, dc, db = op.sensitivity(_dev(u), _dev(lam), 0.7, 1.3)
+  rk, rc, rb = AJ.sensitivities(ref, u, lam, 0.7, 1.3)
+  assert _rel(_np(dk), rk) <= 1e-11
+  assert _rel(_np(dc), AJ.reduce_coefficient(rc, 'elem')) <= 1e-11
+  assert _rel(_np(db), rb) <= 1e-11
+  # bitwise what the operator without coefficients gives ...
+  bare = fes.helmholtz_operator(None)
+  ul, ll = mesh.gather(_dev(u)), mesh.gather(_dev(lam))
+  args = (op.host, ndim, P, 0.7, 1.3)
+  a = _ops.helmholtz_sens(ul, ll, op._geo_parts, *args)
+  bb = _ops.helmholtz_sens(ul, ll, bare.parts, *args)
+  assert all(torch.equal(x, y) for x, y in zip(a, bb))
+  # ... and not what the folded launches would give
+  folded = [{q: p[q] for q in ('geo_mode', 'geo', 'geo_elem', 'geo_index',
+                               'elem_list') if q in p} for p in op.parts]
+  wrong = _ops.helmholtz_sens(ul, ll, folded, *args)
+  assert _rel(_np(wrong[0]), _np(a[0])) > 1e-3
+
+
+# ------------------------------------------------------- 5. op.sensitivity
+@pytest.mark.parametrize('name,ndim,P,quad', [
+    ('three_kinds', 2, 5, None), ('three_kinds', 3, 4, None),
+    ('three_kinds', 2, 4, 5), ('three_kinds', 3, 3, 4)])
+def test_operator_sensitivity_forms(name, ndim, P, quad):
+  """Every coefficient form against the reduced reference, collocated and
+  two-grid; None for absent and callable coefficients."""
+  mesh, bm, fes, ref = _setup(name, ndim, P, quad, F64)
+  rng = np.random.default_rng(P)
+  xq = AJ.quad_points(ref)
+  E, Q, d = xq.shape
+  u = rng.standard_normal(mesh.num_nodes)
+  lam = rng.standard_normal(mesh.num_nodes)
+  l0, l1 = 0.7, 1.3
+  rk, rc, rb = AJ.sensitivities(ref, u, lam, l0, l1)
+  coef = {'scalar': 2.5, 'elem': 0.5 + rng.random(E),
+          'point': 1.0 + rng.random((E, Q))}
+  vel = {'constant': np.array([0.7, -1.1, 0.4][:d]),
+         'elem': rng.standard_normal((E, d)),
+         'point': rng.standard_normal((E, Q, d))}
+  arg = lambda v: _dev(v) if isinstance(v, np.ndarray) else v
+  combos = [('scalar', 'elem', 'point'), ('elem', 'point', 'constant'),
+            ('point', 'scalar', 'elem')]
+  for fk, fc, fb in combos:
+    op = fes.helmholtz_operator(bm, diffusivity=arg(coef[fk]),
+                                reaction=arg(coef[fc]), velocity=arg(vel[fb]))
+    dk, dc, db = op.sensitivity(_dev(u), _dev(lam), l0, l1)
+    # a reduced entry is a sum of per-point values: 1e-11 of the sum of
+    # their magnitudes
+    for got, want, scale, src in (
+        (dk, AJ.reduce_coefficient(rk, fk),
+         np.max(AJ.reduce_coefficient(np.abs(rk), fk)), coef[fk]),
+        (dc, AJ.reduce_coefficient(rc, fc),
+         np.max(AJ.reduce_coefficient(np.abs(rc), fc)), coef[fc]),
+        (db, AJ.reduce_velocity(rb, fb),
+         np.max(AJ.reduce_velocity(np.abs(rb), fb)), vel[fb])):
+      assert tuple(got.shape) == np.shape(src), (fk, fc, fb)
+      assert np.abs(_np(got) - want).max() <= 1e-11 * scale, (fk, fc, fb)
+    only_k = op.sensitivity(_dev(u), _dev(lam), l0, l1,
+                            want=(True, False, False))
+    assert only_k[1] is None and only_k[2] is None
+    assert _rel(_np(only_k[0]), _np(dk)) <= 1e-14
+  # absent and callable coefficients
+  op = fes.helmholtz_operator(bm, diffusivity=lambda x: 1.0 + x[:, 0] ** 2,
+                              velocity=_dev(vel['constant']))
+  dk, dc, db = op.sensitivity(_dev(u), _dev(lam), l0, l1)
+  assert dk is None and dc is None
+  assert _rel(_np(db), AJ.reduce_velocity(rb, 'constant')) <= 1e-11
+  op = fes.helmholtz_operator(bm, reaction=_dev(coef['elem']),
+                              velocity=lambda x: torch.ones_like(x))
+  dk, dc, db = op.sensitivity(_dev(u), _dev(lam), l0, l1)
+  assert dk is None and db is None and dc is not None
+  assert fes.helmholtz_operator(bm).sensitivity(
+      _dev(u), _dev(lam), l0, l1) == (None, None, None)
+
+
+# ------------------------------------------- 6. solve gradients vs dense solve
+D, N, RB = BCType.DIRICHLET, BCType.NEUMANN, BCType.ROBIN
+
+
+@functools.lru_cache(maxsize=None)
+def _solve_setup(ndim, advection):
+  """The problem of `adjoint_reference.solve_problem` on the GPU next to its
+  dense reference, with the reference gradient computed once."""
+  rp, P, quad = AJ.solve_problem(ndim)
+  mesh = rp.finalize(device=DEV)
+  facets = {g: f.cpu().numpy().astype(np.int64)
+            for g, f in mesh.boundary_facets.items()}
+  x = np.asarray(rp.node_coords, np.float64)
+  dmask = mesh.physical_masks['x0'].cpu().numpy().astype(bool)
+  ref = AJ.space(x, rp.elements, P, (quad, 'gl'))
+  f, w, dvals, k_q, c_e, b_q = AJ.problem_data(ref, x, dmask, ndim, advection)
+  E, Q = k_q.shape
+  c_q = AJ.expand_coefficient(c_e, E, Q)
+  prob = AJ.DenseProblem(rp, facets, P, quad, AJ.L0, AJ.L1, dvals, AJ.ROBIN,
+                         AJ.NEUMANN)
+  u, cond = prob.solve(f, k_q, c_q, b_q, want_cond=True)
+  grads = prob.gradient(w, f, k_q, c_q, b_q)
+  t = lambda fn: (lambda y: _dev(fn(_np(y))))
+  bcs = {'x0': (D, _dev(np.nan_to_num(dvals))),
+         'x1': (RB, (AJ.ROBIN[0][1], t(AJ.ROBIN[0][2]))),
+         'y1': (N, t(AJ.NEUMANN[0][1]))}
+  return dict(mesh=mesh, prob=prob, f=f, w=w, k_q=k_q, c_e=c_e, c_q=c_q,
+              b_q=b_q, u=u, cond=cond, grads=grads, bcs=bcs)
+
+
+def _gpu_loss(s, pc, k, c, b, f=None, rtol=1e-13):
+  f = _dev(s['f']) if f is None else f
+  u, info = solve_helmholtz(s['mesh'], f, s['bcs'], lambda0=AJ.L0,
+                            lambda1=AJ.L1, rtol=rtol, return_info=True,
+                            preconditioner=pc, diffusivity=k, reaction=c,
+                            velocity=b)
+  assert info['status'] == 'converged'
+  return (u * _dev(s['w'])).sum(), u
+
+
+@pytest.mark.parametrize('ndim,advection,pc', [
+    (2, False, None), (2, False, 'jacobi'), (2, False, 'pmg'),
+    (2, True, None), (2, True, 'jacobi'),
+    (3, False, None), (3, False, 'jacobi'), (3, False, 'pmg'),
+    (3, True, None), (3, True, 'jacobi')])
+def test_solve_gradients_match_dense_reference(ndim, advection, pc):
+  """`.grad` of the forcing, a per-point k, a per-element c, a per-point b and
+  a scalar k of the loss (w * u).sum() against the dense adjoint solve, on
+  the jittered meshes with Dirichlet (x0, with values), Robin (x1) and
+  Neumann (y1) groups.  Bound 100 cond 1e-12 relative, cond from the dense
+  matrix."""
+  s = _solve_setup(ndim, advection)
+  bound = 100.0 * s['cond'] * 1e-12
+  print(f'ndim={ndim} advection={advection}: cond {s["cond"]:.3e}, bound '
+        f'{bound:.2e}')
+  assert bound <= 1e-7
+  leaf = lambda a: _dev(a).requires_grad_(True)
+  f, k, c = leaf(s['f']), leaf(s['k_q']), leaf(s['c_e'])
+  b = leaf(s['b_q']) if advection else None
+  loss, u = _gpu_loss(s, pc, k, c, b, f)
+  assert _rel(_np(u), s['u']) <= bound
+  loss.backward()
+  gf, gk, gc, gb = s['grads']
+  E = gc.shape[0]
+  checks = [('forcing', f.grad, gf), ('k', k.grad, gk),
+            ('c', c.grad, AJ.reduce_coefficient(gc, 'elem'))]
+  if advection:
+    checks.append(('b', b.grad, gb))
+  for name, got, want in checks:
+    assert got is not None and tuple(got.shape) == want.shape, name
+    err = _rel(_np(got), want)
+    print(f'  {pc} d/d{name}: rel err {err:.2e}')
+    assert err <= bound, name
+  # a scalar diffusivity: its gradient is the sum of the per-point one at
+  # k = const
+  ks = torch.tensor(1.7, dtype=F64, device=DEV, requires_grad=True)
+  loss, _ = _gpu_loss(s, pc, ks, _dev(s['c_e']), None if b is None
+                      else _dev(s['b_q']))
+  loss.backward()
+  k_const = np.full_like(s['k_q'], 1.7)
+  _, gk, _, _ = s['prob'].gradient(s['w'], s['f'], k_const, s['c_q'],
+                                   s['b_q'])
+  assert ks.grad.shape == ()
+  assert abs(float(ks.grad) - gk.sum()) <= bound * np.abs(gk).sum()
+
+
+@pytest.mark.parametrize('ndim', [2, 3])
+def test_central_difference_through_the_solve(ndim):
+  """One central difference along one random direction of k and one of b
+  through the GPU solve against its own `.grad`.  The dense reference, on
+  the same problem, directions and step, sets the floor of truncation and
+  rounding (`test_adjoint_host`, which asserts it); 10 x that is allowed for
+  the solver tolerance.
+
+  The solves of this test run at rtol = 1e-15, not the 1e-13 of the gradient
+  tests: a loss known to rtol |loss| enters the difference quotient as
+  rtol |loss| / (2 h |derivative|), and in 3D |loss| = 16.6 stands against a
+  directional derivative of 0.035 along b, so rtol = 1e-13 alone is 2.4e-7,
+  over the allowance of 7.2e-9, whatever the gradient code does; 1e-15 is
+  2.4e-9.  Measured on an MI355X, relative discrepancy of b in 3D: 2.1e-7
+  (rtol 1e-13), 4.3e-8 (1e-14), 2.1e-10 (1e-15), reference 7.2e-10; of k:
+  4.6e-10, 2.1e-10, 1.2e-9, reference 1.4e-9; in 2D k 2.8e-8 at every rtol
+  (reference 2.8e-8, truncation), b 8.7e-11 .. 1.6e-9 (reference 9.0e-10)."""
+  s = _solve_setup(ndim, True)
+  rk, rb, dk, db, _, _ = AJ.central_difference(
+      s['prob'], s['w'], s['f'], s['k_q'], s['c_q'], s['b_q'],
+      np.random.default_rng(11))
+  leaf = lambda a: _dev(a).requires_grad_(True)
+  k, b = leaf(s['k_q']), leaf(s['b_q'])
+  c = _dev(s['c_e'])
+  rtol = 1e-15
+  loss, _ = _gpu_loss(s, 'jacobi', k, c, b, rtol=rtol)
+  loss.backward()
+  an_k = float((k.grad * _dev(dk)).sum())
+  an_b = float((b.grad * _dev(db)).sum())
+  h = AJ.CD_H
+  val = lambda kk, bb: float(_gpu_loss(s, 'jacobi', _dev(kk), c, _dev(bb),
+                                       rtol=rtol)[0])
+  cd_k = (val(s['k_q'] + h * dk, s['b_q']) -
+          val(s['k_q'] - h * dk, s['b_q'])) / (2 * h)
+  cd_b = (val(s['k_q'], s['b_q'] + h * db) -
+          val(s['k_q'], s['b_q'] - h * db)) / (2 * h)
+  ek, eb = abs(cd_k - an_k) / abs(an_k), abs(cd_b - an_b) / abs(an_b)
+  print(f'ndim={ndim}: k {ek:.2e} (reference {rk:.2e}), b {eb:.2e} '
+        f'(reference {rb:.2e})')
+  assert ek <= 10.0 * rk and eb <= 10.0 * rb
+
+
+# --------------------------------------------------------- 7. transpose_solve
+def test_transpose_solve():
+  from swirl_fem_amd.linalg.bicgstab import transpose_solve
+  rng = np.random.default_rng(7)
+  n = 200
+  A = 0.5 * rng.standard_normal((n, n)) / np.sqrt(n)
+  A += np.diag(1.0 + rng.random(n))
+  b, w = rng.standard_normal(n), rng.standard_normal(n)
+  cond = np.linalg.cond(A)
+  bound = 100.0 * cond * 1e-12
+  Ad = _dev(A)
+  bd = _dev(b).requires_grad_(True)
+  info = {}
+  x = transpose_solve(lambda v: Ad @ v, lambda v: Ad.T @ v, bd, info_out=info,
+                      tol=1e-13)
+  assert info['status'] == 'converged'
+  assert _rel(_np(x), np.linalg.solve(A, b)) <= bound
+  (x * _dev(w)).sum().backward()
+  assert _rel(_np(bd.grad), np.linalg.solve(A.T, w)) <= bound
+  # with the wrong (untransposed) operator the gradient is wrong
+  bd2 = _dev(b).requires_grad_(True)
+  x = transpose_solve(lambda v: Ad @ v, lambda v: Ad @ v, bd2, tol=1e-13)
+  (x * _dev(w)).sum().backward()
+  assert _rel(_np(bd2.grad), np.linalg.solve(A.T, w)) > 1e-3
+
+
+# ------------------------------------------------------ 8. unchanged behaviour
+def test_forward_result_unchanged_and_no_node_without_grad(monkeypatch):
+  """With grad-requiring inputs the autograd node hands the solve's body the
+  detached inputs and returns its result: what the body returned IS the
+  value of the tracked `u` (`torch.equal`, within one call).  Across calls
+  the solves are not bitwise reproducible -- shared nodes and inner products
+  are summed with atomics, so two identical calls without grad already differ
+  in the last bits (measured: 2.1e-14) -- hence two calls are compared to
+  what their tolerance allows, 2 cond rtol, with cond of the dense matrix."""
+  from swirl_fem_amd.examples import helmholtz as hz
+  body = hz._solve
+  seen = []
+
+  def recording(mesh, forcing, bcs, **kw):
+    out = body(mesh, forcing, bcs, **kw)
+    seen.append((forcing, kw, out, out[0].clone()))
+    return out
+  monkeypatch.setattr(hz, '_solve', recording)
+  for advection in (False, True):
+    s = _solve_setup(2, advection)
+    bound = 2.0 * s['cond'] * 1e-13
+    k, c = _dev(s['k_q']), _dev(s['c_e'])
+    b = _dev(s['b_q']) if advection else None
+    del seen[:]
+    _, plain = _gpu_loss(s, 'jacobi', k, c, b)
+    assert plain.grad_fn is None and not plain.requires_grad
+    assert len(seen) == 1 and seen[0][2][0] is plain    # the body's own result
+    assert '_state' not in seen[0][1]
+    kg = _dev(s['k_q']).requires_grad_(True)
+    fg = _dev(s['f']).requires_grad_(True)
+    del seen[:]
+    _, tracked = _gpu_loss(s, 'jacobi', kg, c, b, fg)
+    assert tracked.grad_fn is not None
+    assert len(seen) == 1
+    forcing, kw, _, u_body = seen[0]               # a copy of the body's u
+    # the body saw the values, detached, and nothing else changed
+    assert not forcing.requires_grad and torch.equal(forcing, fg.detach())
+    assert not kw['diffusivity'].requires_grad
+    assert torch.equal(kw['diffusivity'], k)
+    assert torch.equal(kw['reaction'], c)
+    assert kw['velocity'] is None if b is None else torch.equal(
+        kw['velocity'], b)
+    assert torch.equal(tracked.detach(), u_body)
+    err = _rel(_np(tracked), _np(plain))
+    print(f'advection={advection}: tracked vs plain call {err:.2e}, bound '
+          f'{bound:.2e}')
+    assert err <= bound
+    del seen[:]
+    with torch.no_grad():
+      _, quiet = _gpu_loss(s, 'jacobi', kg, c, b)
+    assert quiet.grad_fn is None and '_state' not in seen[0][1]
+    assert _rel(_np(quiet), _np(plain)) <= bound
+
+
+# ----------------------------------------------------------------- 9. refusals
+def test_refusals():
+  from swirl_fem_amd.common.premesh_commons import unit_cube_mesh
+  from swirl_fem_amd.core.interpolation import Nodes1D
+  from swirl_fem_amd.core.mesh_refiner import refine_premesh
+  pm = unit_cube_mesh(3, ndim=2, periodic_dims=(0,))
+  mesh = refine_premesh(pm, Nodes1D.create(4, GLL)).finalize(device=DEV)
+  f = torch.zeros(mesh.num_nodes, dtype=F64, device=DEV, requires_grad=True)
+  with pytest.raises(NotImplementedError, match='periodic'):
+    solve_helmholtz(mesh, f, {}, lambda0=1.0)
+  # without grad the periodic solve runs as before
+  solve_helmholtz(mesh, f.detach(), {}, lambda0=1.0)
+  # the C entry point
+  mesh, bm, fes, ref = _setup('affine', 3, 4, None, F64)
+  op = fes.helmholtz_operator(None)
+  E, n = mesh.num_elements, mesh.num_nodes_per_element
+  ul = torch.zeros((E, n), dtype=F64, device=DEV)
+  with pytest.raises(_lib.SfemError, match='status -3'):     # a vector field
+    _ops.helmholtz_sens(ul, ul, op.parts, op.host, 3, 4, 0.0, 1.0, ncomp=3)
+  with pytest.raises(_lib.SfemError, match='status -3'):     # P out of range
+    _ops.helmholtz_sens(ul, ul, op.parts, op.host, 3, 13, 0.0, 1.0)
+  import ctypes
+  args = _lib.HelmholtzSensArgs(
+      u=None, lam=None, dkappa=ul.data_ptr(), num_elements=E, ndim=3, P=4,
+      ncomp=1, dtype=_lib.SFEM_F64, geo_mode=_lib.GEO_AFFINE)
+  rc = _lib.load().sfem_helmholtz_sens(ctypes.byref(args), None)
+  assert rc == -1, rc                                        # SFEM_EINVAL
+  with pytest.raises(ValueError):
+    op.sensitivity(ul, ul, 0.0, 1.0)                         # not nodal
