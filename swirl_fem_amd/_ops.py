@@ -736,28 +736,83 @@ def fold_layers_at(ext, idx, count, layers):
   return ext
 
 
-def fdm_solve(r, pel, S, cases, inv_ev, ndim, Pp):
+def _fdm_check(who, r, pel, S, cases, inv_ev, ndim, Pp, weights=None):
+  """Refuses operands `sfem_fdm_solve` would read out of bounds; returns
+  (device, E).  (The range of Pp is the library's own check.)"""
+  dev = _dev(r, pel, S, cases, inv_ev, weights)
+  ndim, Pp = int(ndim), int(Pp)
+  if not 1 <= ndim <= 3 or Pp < 1:
+    raise ValueError(f'{who}: ndim 1..3 and Pp >= 1; got {ndim}, {Pp}')
+  if cases.dtype != torch.int32:
+    raise TypeError(f'{who}: cases must be int32; got {cases.dtype}')
+  if cases.dim() != 2 or cases.shape[0] != ndim:
+    raise ValueError(f'{who}: cases must be (ndim, E) = ({ndim}, E); got '
+                     f'{tuple(cases.shape)}')
+  E = cases.shape[1]
+  n = Pp ** ndim
+  _dtype_code(r)
+  if S.dtype != r.dtype or inv_ev.dtype != r.dtype or (
+      weights is not None and weights.dtype != r.dtype):
+    raise TypeError(f'{who}: S, inv_ev and weights must have the dtype of r '
+                    f'({r.dtype})')
+  if S.numel() == 0 or S.numel() % (Pp * Pp):
+    raise ValueError(f'{who}: S must be (cases, Pp, Pp); got '
+                     f'{tuple(S.shape)} for Pp = {Pp}')
+  if inv_ev.numel() != E * n:
+    raise ValueError(f'{who}: inv_ev must hold E Pp^d = {E * n} values; got '
+                     f'{inv_ev.numel()}')
+  if pel is None:
+    if r.numel() != E * n:
+      raise ValueError(f'{who}: r must hold E Pp^d = {E * n} values without '
+                       f'pel; got {r.numel()}')
+  else:
+    if pel.dtype != torch.int64:
+      raise TypeError(f'{who}: pel must be int64; got {pel.dtype}')
+    if pel.numel() != E * n:
+      raise ValueError(f'{who}: pel must hold E Pp^d = {E * n} node ids; got '
+                       f'{pel.numel()}')
+  if weights is not None and weights.numel() != r.numel():
+    raise ValueError(f'{who}: weights must have the size of r')
+  return dev, E
+
+
+def fdm_solve(r, pel, S, cases, inv_ev, ndim, Pp, out=None):
   """z_e = (S (x) ..) [inv_ev_e .* (S (x) ..)^T r_e] for every element
   (`sfem_fdm_solve`); `pel` (E, Pp^d) int64 or None for element-contiguous
-  numbering; `cases` (ndim, E) int32."""
-  dev = _dev(r, pel, S, cases, inv_ev)
-  z = torch.empty_like(r)
+  numbering; `cases` (ndim, E) int32; `out`: z to write into."""
+  dev, E = _fdm_check('fdm_solve', r, pel, S, cases, inv_ev, ndim, Pp)
+  z = _fdm_out('fdm_solve', out, r, r.shape, dev)
   with torch.cuda.device(dev):
     _lib.check(_lib.load().sfem_fdm_solve(
         _ptr(r), _ptr(z), _ptr(pel), _ptr(S), _ptr(cases), _ptr(inv_ev),
-        cases.shape[1], int(ndim), int(Pp), _dtype_code(r), _stream(dev)),
+        E, int(ndim), int(Pp), _dtype_code(r), _stream(dev)),
         'sfem_fdm_solve')
   return z
 
 
-def fdm_solve_sums(r, pel, S, cases, inv_ev, weights, ndim, Pp):
+def _fdm_out(who, out, like, shape, dev):
+  """`out` checked against the result's shape, or a fresh tensor."""
+  if out is None:
+    return torch.empty(shape, dtype=like.dtype, device=like.device)
+  if (_dev(out) != dev or out.dtype != like.dtype or
+      tuple(out.shape) != tuple(shape)):
+    raise ValueError(f'{who}: out must be a contiguous {like.dtype} tensor of '
+                     f'shape {tuple(shape)} on {dev}')
+  return out
+
+
+def fdm_solve_sums(r, pel, S, cases, inv_ev, weights, ndim, Pp, out=None):
   """`fdm_solve` that also returns the element sums of r and the elements'
-  shares of weights . z (`sfem_fdm_solve_sums`)."""
-  dev = _dev(r, pel, S, cases, inv_ev, weights)
-  E = cases.shape[1]
-  z = torch.empty_like(r)
-  elem_sum = torch.empty(E, dtype=r.dtype, device=r.device)
-  weighted = torch.empty(E, dtype=r.dtype, device=r.device)
+  shares of weights . z (`sfem_fdm_solve_sums`); `out`: (z, elem_sum,
+  weighted_sum) to write into."""
+  dev, E = _fdm_check('fdm_solve_sums', r, pel, S, cases, inv_ev, ndim, Pp,
+                      weights)
+  if weights is None:
+    raise ValueError('fdm_solve_sums: weights required')
+  zo, so, wo = (None, None, None) if out is None else out
+  z = _fdm_out('fdm_solve_sums', zo, r, r.shape, dev)
+  elem_sum = _fdm_out('fdm_solve_sums', so, r, (E,), dev)
+  weighted = _fdm_out('fdm_solve_sums', wo, r, (E,), dev)
   with torch.cuda.device(dev):
     _lib.check(_lib.load().sfem_fdm_solve_sums(
         _ptr(r), _ptr(z), _ptr(pel), _ptr(S), _ptr(cases), _ptr(inv_ev),
@@ -769,32 +824,59 @@ def fdm_solve_sums(r, pel, S, cases, inv_ev, weights, ndim, Pp):
 def add_element_constants_(z, yc, shift, n, elems_per_member):
   """In place: z[e n + i] += yc[e] - shift[e // elems_per_member]."""
   dev = _dev(z, yc, shift)
-  if not z.is_contiguous() or z.numel() != yc.numel() * n:
-    raise ValueError('add_element_constants_: z is (E n,) contiguous')
+  n, epm = int(n), int(elems_per_member)
+  E = yc.numel()
+  if n < 1 or epm < 1 or z.numel() != E * n:
+    raise ValueError('add_element_constants_: z is (E n,) contiguous, n >= 1 '
+                     'and elems_per_member >= 1')
+  if yc.dtype != z.dtype or shift.dtype != z.dtype:
+    raise TypeError('add_element_constants_: one real dtype for z, yc, shift')
+  if E % epm:
+    raise ValueError(f'add_element_constants_: {E} elements are no multiple '
+                     f'of elems_per_member = {epm}')
+  if shift.numel() < E // epm:
+    raise ValueError(f'add_element_constants_: shift holds {shift.numel()} '
+                     f'values for {E // epm} members')
   with torch.cuda.device(dev):
     _lib.check(_lib.load().sfem_add_element_constants(
-        _ptr(z), _ptr(yc.contiguous()), _ptr(shift.contiguous()), yc.numel(),
-        int(n), int(elems_per_member), _dtype_code(z), _stream(dev)),
-        'sfem_add_element_constants')
+        _ptr(z), _ptr(yc), _ptr(shift), E, n, epm, _dtype_code(z),
+        _stream(dev)), 'sfem_add_element_constants')
   return z
 
 
 def ell_chebyshev(cols, vals, dinv, b, steps, lmin, lmax, work=None,
                   out=None):
   """x = Chebyshev polynomial of the Jacobi-scaled ELL matrix applied to b
-  (`sfem_ell_chebyshev`); cols / vals (width, n) int32 / real."""
-  dev = _dev(cols, vals, dinv, b)
+  (`sfem_ell_chebyshev`); cols / vals (width, n) int32 / real; `work`: 3 n
+  values of scratch."""
+  dev = _dev(cols, vals, dinv, b, work, out)
   n = b.numel()
+  if (cols.dim() != 2 or cols.shape != vals.shape or cols.shape[0] < 1 or
+      cols.shape[1] != n or dinv.numel() != n):
+    raise ValueError('ell_chebyshev: cols / vals must be (width, n), dinv and '
+                     'b (n,)')
+  if cols.dtype != torch.int32 or vals.dtype != b.dtype or (
+      dinv.dtype != b.dtype):
+    raise TypeError('ell_chebyshev: int32 columns, one real dtype for vals, '
+                    'dinv, b')
+  steps, lmin, lmax = int(steps), float(lmin), float(lmax)
+  if steps < 1 or not 0.0 < lmin < lmax:
+    raise ValueError(f'ell_chebyshev: steps >= 1 and 0 < lmin < lmax; got '
+                     f'{steps}, {lmin}, {lmax}')
+  if out is not None and (out.dtype != b.dtype or out.numel() != n):
+    raise ValueError('ell_chebyshev: out must have the dtype and size of b')
   x = torch.empty_like(b) if out is None else out
   if work is None:
     work = torch.empty(3 * n, dtype=b.dtype, device=b.device)
+  elif work.dtype != b.dtype or work.numel() < 3 * n:
+    raise ValueError(f'ell_chebyshev: work must hold 3 n = {3 * n} values of '
+                     f'{b.dtype}; got {work.numel()} of {work.dtype}')
   with torch.cuda.device(dev):
     _lib.check(_lib.load().sfem_ell_chebyshev(
         _ptr(cols), _ptr(vals), _ptr(dinv), _ptr(b), _ptr(x), _ptr(work), n,
-        cols.shape[0], int(steps), float(lmin), float(lmax), _dtype_code(b),
-        _stream(dev)), 'sfem_ell_chebyshev')
+        cols.shape[0], steps, lmin, lmax, _dtype_code(b), _stream(dev)),
+        'sfem_ell_chebyshev')
   return x
-
 
 
 def ell_spmv(cols, vals, x, y, rows=None, row_range=None):
