@@ -543,6 +543,52 @@ int sfem_stokes_grad_t(const sfem_stokes_args* args, sfem_stream_t stream);
 int sfem_stokes_e_first(const sfem_stokes_args* args, sfem_stream_t stream);
 int sfem_stokes_e_second(const sfem_stokes_args* args, sfem_stream_t stream);
 
+/* ------------------------------------------- scalar transport: BDF/EXT rhs ---
+ * The explicit right-hand side of a BDFk/EXTk step of
+ *   dT/dt + u . grad T - div(k grad T) = s
+ * on a collocated grid of P points per direction (the quadrature grid of the
+ * implicit Helmholtz solve, after interpolation to it), element-local:
+ *
+ *   out[e,q] = wdet[e,q] (source[e,q] + sum_j mass_coef[j] T_j[e,q])
+ *            + sum_j conv_coef[j] sum_a (sum_c Kw[a][c] u_j,c[e,q])
+ *                                       d T_j / d xi_a [e,q]
+ *
+ * over num_levels <= SFEM_TRANSPORT_LEVELS time levels j, with
+ * Kw[a][c] = w_q detJ_q d xi_a / d x_c the weighted cofactors of
+ * sfem_stokes_convect_local (same geometry arguments: SFEM_GEO_AFFINE /
+ * SFEM_GEO_MULTILINEAR from `geo_elem`, SFEM_GEO_POINT from `kfac` with
+ * `geo_index`; `elem_list` / `num_listed` select the elements of a launch)
+ * and wdet = w_q detJ_q given per point.  Arrays are indexed by element id,
+ * points in slot order (lexicographic, axis 0 slowest), a velocity with ndim
+ * consecutive reals per point.  A level with velocity[j] NULL or
+ * conv_coef[j] = 0 contributes its mass term only.  `source` is optional;
+ * `wdet` may be NULL when every mass_coef is 0 and there is no source.
+ * ndim outside 2..3, P outside 2..12, more than SFEM_TRANSPORT_LEVELS levels
+ * and any other geo_mode return SFEM_EUNSUPPORTED; a NULL out, dmat, scalar[j]
+ * (j < num_levels), a missing geometry array or a missing required wdet is
+ * SFEM_EINVAL.  ABI version 10.                                              */
+#define SFEM_TRANSPORT_LEVELS 3
+typedef struct sfem_transport_args {
+  const void* scalar[SFEM_TRANSPORT_LEVELS];    /* T_j (E, n)                 */
+  const void* velocity[SFEM_TRANSPORT_LEVELS];  /* u_j (E, n, ndim) or NULL   */
+  double mass_coef[SFEM_TRANSPORT_LEVELS];
+  double conv_coef[SFEM_TRANSPORT_LEVELS];
+  const void* source;     /* (E, n) or NULL                                   */
+  const void* wdet;       /* (E, n) or NULL                                   */
+  void* out;              /* (E, n)                                           */
+  const void* kfac;       /* per-point weighted cofactors or NULL             */
+  const void* geo_elem;   /* (E, 24) or NULL                                  */
+  const int32_t* geo_index; /* (E,) slot of element e in kfac, or NULL = e    */
+  const int32_t* elem_list; /* element ids of this launch, or NULL = all      */
+  const void* dmat;       /* HOST (P, P)                                      */
+  const void* weights;    /* HOST (P,)                                        */
+  const void* nodes;      /* HOST (P,)                                        */
+  int64_t num_elements;
+  int64_t num_listed;
+  int32_t num_levels, ndim, P, dtype, geo_mode;
+} sfem_transport_args;
+int sfem_transport_rhs(const sfem_transport_args* args, sfem_stream_t stream);
+
 /* ------------------------------------------------------------ CG kernels ---
  * Preconditioned CG of linalg/cg.py:30-97 with device-resident scalars: no
  * host synchronisation inside an iteration (the reference keeps its loop on

@@ -1194,6 +1194,66 @@ def stokes_convect_local(u_local, parts, host, ndim, P):
   return out
 
 
+def transport_rhs(levels, parts, host, ndim, P, source=None, wdet=None):
+  """The BDF/EXT right-hand side of scalar transport on a collocated grid
+  (`sfem_transport_rhs`).  `levels`: up to three tuples (T (E, P^d), u
+  (E, P^d, d) or None, mass_coef, conv_coef); `source`, `wdet` (E, P^d) or
+  None.  Returns (E, P^d):
+  wdet (source + sum_j mass_j T_j) + sum_j conv_j w detJ u_j . grad T_j."""
+  levels = list(levels)
+  if not 1 <= len(levels) <= _lib.SFEM_TRANSPORT_LEVELS:
+    raise ValueError(f'expected 1..{_lib.SFEM_TRANSPORT_LEVELS} levels, got '
+                     f'{len(levels)}')
+  first = levels[0][0]
+  dev = _dev(first)
+  shape = (first.shape[0], P ** ndim)
+  tensors = []
+
+  def field(t, name, trailing=()):
+    if t is None:
+      return None
+    if tuple(t.shape) != shape + trailing:
+      raise ValueError(f'{name}: expected {shape + trailing}, got '
+                       f'{tuple(t.shape)}')
+    if t.dtype != first.dtype or t.device != first.device:
+      raise ValueError(f'{name}: expected the dtype and device of the first '
+                       'scalar')
+    t = t.contiguous()
+    tensors.append(t)         # keeps the copy alive until the launches
+    return t
+  args = _lib.TransportArgs(num_levels=len(levels))
+  mass = source is not None
+  for n, (T, u, mc, cc) in enumerate(levels):
+    args.scalar[n] = _dptr(field(T, f'level {n}: scalar'))
+    args.velocity[n] = _dptr(field(u, f'level {n}: velocity', (ndim,)))
+    args.mass_coef[n], args.conv_coef[n] = float(mc), float(cc)
+    mass = mass or float(mc) != 0.0
+  if mass and wdet is None:
+    raise ValueError('mass terms and a source need `wdet`')
+  args.source = _dptr(field(source, 'source'))
+  args.wdet = _dptr(field(wdet, 'wdet'))
+  out = torch.empty(shape, dtype=first.dtype, device=dev)
+  host = {k: _host(v, first.dtype) for k, v in host.items()}
+  args.out = out.data_ptr()
+  args.dmat, args.weights = _hptr(host['dmat']), _hptr(host['weights'])
+  args.nodes = _hptr(host['nodes'])
+  args.num_elements, args.ndim, args.P = shape[0], ndim, P
+  args.dtype = _dtype_code(first)
+  with torch.cuda.device(dev):
+    for part in parts:
+      lst = part.get('elem_list')
+      args.kfac = _dptr(part.get('kfac'))
+      args.geo_elem = _dptr(part.get('geo_elem'))
+      args.geo_index = _dptr(part.get('geo_index'))
+      args.elem_list = _dptr(lst)
+      args.num_listed = 0 if lst is None else lst.numel()
+      args.geo_mode = part['geo_mode']
+      _lib.check(_lib.load().sfem_transport_rhs(ctypes.byref(args),
+                                                _stream(dev)),
+                 'sfem_transport_rhs')
+  return out
+
+
 from swirl_fem_amd.core.layout import is_component_major  # noqa: E402
 
 

@@ -2256,3 +2256,118 @@ class ConvectionOperator:
     return _ops.basis_eval_t(cq, None, i1, g1, None, ones, mesh.ndim,
                              mesh.gridpoints_1d.num_points, q, mesh.ndim,
                              False)
+
+
+# ---------------------------------------------------------------------------
+# Scalar transport: the explicit right-hand side of a BDF/EXT step
+# ---------------------------------------------------------------------------
+@dataclasses.dataclass(eq=False)
+class TransportRhs:
+  """`sum_j (m_j B T_j + c_j C(u_j) T_j) + B s` for up to three time levels
+  in one pass: B the mass matrix, `C(u)[i,k] = sum_q W_q phi_i(q) u_q . grad
+  phi_k(q)` the convective form of `TwoGridHelmholtzOperator`.
+  Interpolate each level's scalar and nodal velocity to the quadrature grid
+  (`sfem_basis_eval`, d + 1 components), one fused kernel there
+  (`sfem_transport_rhs`: collocated derivative lines, cofactor geometry,
+  contravariant velocity, product, mass terms), transposed interpolation
+  (`sfem_basis_eval_t`).  No folded velocity (E, Q^d, d) is built."""
+  fespace: object
+  parts: list
+  host: dict
+  _wdet: torch.Tensor | None = None
+
+  @classmethod
+  def create(cls, fespace, geometry='auto') -> 'TransportRhs':
+    why = supports_two_grid(fespace)
+    if why is not None:
+      raise NotImplementedError(f'fused transport unavailable: {why}')
+    parts = _grid_geometry_parts(fespace, _ops.stokes_setup, geometry)
+    host = {'dmat': _quadrature_dmat(fespace),
+            'weights': np.asarray(fespace.quadrature.weights),
+            'nodes': np.asarray(fespace.quadrature.nodes.node_values)}
+    return cls(fespace=fespace, parts=parts, host=host)
+
+  def point_weights(self):
+    """W = w detJ (E, Q^d), what `TwoGridHelmholtzOperator.point_weights`
+    returns."""
+    if self._wdet is None:
+      self._wdet = self.fespace.wdet()
+    return self._wdet
+
+  def apply_local(self, levels, source_q=None):
+    """`levels`: tuples (T_q (E, Q^d), u_q (E, Q^d, d) or None, mass_coef,
+    conv_coef) on the quadrature grid -> (E, Q^d), the integrand times W."""
+    fes = self.fespace
+    levels = list(levels)
+    mass = source_q is not None or any(float(l[2]) != 0.0 for l in levels)
+    return _ops.transport_rhs(
+        levels, self.parts, self.host, fes.mesh.ndim,
+        fes.quadrature.num_points, source=source_q,
+        wdet=self.point_weights() if mass else None)
+
+  def _point_velocity(self, u):
+    """A level's velocity that needs no interpolation as (E, Q^d, d), or
+    None for nodal values."""
+    fes = self.fespace
+    mesh = fes.mesh
+    E, d = mesh.num_elements, mesh.ndim
+    nq = fes.quadrature.num_points ** d
+    u = torch.as_tensor(u, dtype=fes.dtype, device=fes.device)
+    if tuple(u.shape) == (d,):
+      return u[None, None, :].expand(E, nq, d).contiguous()
+    if tuple(u.shape) == (E, nq, d):
+      return u
+    if tuple(u.shape) == (mesh.num_nodes, d):
+      return None
+    raise ValueError(f'velocity: shape {tuple(u.shape)}; expected ({d},), '
+                     f'({mesh.num_nodes}, {d}) or ({E}, {nq}, {d})')
+
+  def apply(self, levels, source=None):
+    """`levels`: tuples (T (N,), u, mass_coef, conv_coef) with `u` nodal (N, d)
+    in any strides, a (d,) constant, (E, Q^d, d) point values or None;
+    `source`: None, (N,) nodal or (E, Q^d) point values.  Returns the
+    assembled (N,) vector  B s + sum_j (m_j B + c_j C(u_j)) T_j."""
+    fes = self.fespace
+    mesh = fes.mesh
+    d = mesh.ndim
+    nq = fes.quadrature.num_points ** d
+
+    def at_points(nodal):      # (N, nc) -> (E, Q^d, nc)
+      loc = _ops.gather_rows(nodal.contiguous(), mesh.elements)
+      return loc if fes.is_collocated else fes._basis(loc, True, False)[0]
+    local = []
+    for T, u, mc, cc in levels:
+      T = torch.as_tensor(T, dtype=fes.dtype, device=fes.device)
+      if tuple(T.shape) != (mesh.num_nodes,):
+        raise ValueError(f'expected ({mesh.num_nodes},) nodal values, got '
+                         f'{tuple(T.shape)}')
+      uq = None if u is None else self._point_velocity(u)
+      if u is not None and uq is None and float(cc) != 0.0:
+        u = torch.as_tensor(u, dtype=fes.dtype, device=fes.device)
+        both = at_points(torch.cat([T[:, None], u], dim=1))
+        Tq, uq = both[..., 0].contiguous(), both[..., 1:].contiguous()
+      else:
+        Tq = at_points(T[:, None])[..., 0].contiguous()
+      local.append((Tq, uq, mc, cc))
+    sq = None
+    if source is not None:
+      s = torch.as_tensor(source, dtype=fes.dtype, device=fes.device)
+      if tuple(s.shape) == (mesh.num_elements, nq):
+        sq = s
+      elif tuple(s.shape) == (mesh.num_nodes,):
+        sq = at_points(s[:, None])[..., 0].contiguous()
+      else:
+        raise ValueError(f'source: shape {tuple(s.shape)}; expected '
+                         f'({mesh.num_nodes},) or ({mesh.num_elements}, {nq})')
+    rq = self.apply_local(local, sq)
+    if fes.is_collocated:
+      return mesh.scatter(rq)
+    i1, g1 = fes._matrices()
+    ones = fes._cache.get('ones_eq')
+    if ones is None:
+      ones = fes._cache['ones_eq'] = torch.ones(
+          (mesh.num_elements, nq), dtype=fes.dtype, device=fes.device)
+    r3 = _ops.basis_eval_t(rq[..., None], None, i1, g1, None, ones, d,
+                           mesh.gridpoints_1d.num_points,
+                           fes.quadrature.num_points, 1, False)
+    return mesh.scatter(r3[..., 0])

@@ -1,0 +1,215 @@
+// Explicit right-hand side of BDFk/EXTk scalar transport,
+//   dT/dt + u . grad T - div(k grad T) = s,
+// on a collocated grid of P points per direction (the quadrature grid of the
+// Helmholtz solve, reached by interpolation):
+//
+//   out[e,q] = W[e,q] (source[e,q] + sum_j mass_coef[j] T_j[e,q])
+//            + sum_j conv_coef[j] sum_a (sum_c Kw[a][c] u_j,c[e,q]) d T_j / d xi_a
+//
+// for up to SFEM_TRANSPORT_LEVELS time levels j, with W = w detJ (`wdet`) and
+// Kw[a][c] = w detJ d xi_a / d x_c the weighted cofactors of ElemCof.  The
+// stepper passes mass_coef = -bdf[j] / dt and conv_coef = -ext[j].
+//
+// transport_rhs_kernel is a sibling of stokes_convect_kernel (sfem_stokes.h):
+// the same lane mapping (lane (i, j) owns the points (*, i, j)), the same LDS
+// tensor pair, ElemCof, line_apply and HelmholtzTile.  What differs:
+//   * the differentiated field is a scalar and the advecting velocity is data
+//     of its own, so a level's velocity is needed at the pointwise stage only
+//     and is read there, DIM reals per point, instead of being held as
+//     DIM x P registers across the derivative lines;
+//   * the levels run one after another through the one LDS tensor pair into
+//     one accumulator of P values per lane;
+//   * a level without a velocity (null pointer) or with conv_coef = 0 skips
+//     its derivative stage and its barriers.  Both are kernel arguments, so
+//     the test is uniform over the workgroup and the barriers stay outside
+//     the `active` / `lane_ok` branches.
+// Element-local in and out; interpolation, its transpose, gather and scatter
+// are separate kernels.
+#pragma once
+#include "sfem_stokes.h"
+
+namespace sfem {
+
+template <typename T>
+struct TransportParams {
+  StokesParams<T> geo;   // kfac / geo_elem / geo_index / elem_list /
+                         // num_elements / geo_mode / *_host; the rest unused
+  const T* scalar[SFEM_TRANSPORT_LEVELS];    // T_j (E, N)
+  const T* velocity[SFEM_TRANSPORT_LEVELS];  // u_j (E, N, DIM) or null
+  T mass_coef[SFEM_TRANSPORT_LEVELS];
+  T conv_coef[SFEM_TRANSPORT_LEVELS];
+  const T* source;       // (E, N) or null
+  const T* wdet;         // (E, N) w detJ; null only without mass terms / source
+  T* out;                // (E, N)
+  int num_levels;
+};
+
+template <typename T, int P, int DIM, int GM>
+__global__ void __launch_bounds__((HelmholtzTile<T, P, DIM>::BLOCK),
+                                  (HelmholtzTile<T, P, DIM>::MINW))
+transport_rhs_kernel(TransportParams<T> tp, DMat<T, P> dm) {
+  using Tile = HelmholtzTile<T, P, DIM>;
+  constexpr int TPE = Tile::TPE, SA = Tile::SA, SB = Tile::SB;
+  constexpr int EPB = Tile::EPB, W = Tile::ELEM_WORDS;
+  constexpr int N = DIM == 3 ? P * P * P : P * P;
+  __shared__ T lds[2 * EPB * W];
+  const StokesParams<T>& prm = tp.geo;
+  const int tid = threadIdx.x;
+  const int el = tid / TPE;
+  const int t = tid - el * TPE;
+  const int i = DIM == 3 ? t / P : 0;
+  const int j = DIM == 3 ? t - i * P : t;
+  const bool lane_ok = el < EPB;
+  const int64_t work = (int64_t)blockIdx.x * EPB + (lane_ok ? el : 0);
+  const bool active = lane_ok && work < prm.num_elements;
+  const int64_t e =
+      prm.elem_list ? (active ? (int64_t)prm.elem_list[work] : 0) : work;
+  T* s0 = lds + (lane_ok ? el : 0) * 2 * W;
+  T* s1 = s0 + W;
+  (void)s1;
+  ElemCof<T, P, DIM, GM> geom;
+  geom.init(prm, dm, e, active, i, j, t);
+  // per-point arrays of this element: lane t of slice a reads point
+  // a * TPE + t (coalesced); a velocity holds DIM consecutive reals per point
+  const T* wd = tp.wdet ? tp.wdet + e * N : nullptr;
+
+  T acc[P];
+#pragma unroll
+  for (int a = 0; a < P; ++a) acc[a] = T(0);
+
+#pragma unroll 1
+  for (int lev = 0; lev < tp.num_levels; ++lev) {
+    const T mc = tp.mass_coef[lev], cc = tp.conv_coef[lev];
+    const T* ve = tp.velocity[lev];
+    const bool conv = ve != nullptr && cc != T(0);
+    if (!conv && mc == T(0)) continue;
+    const T* te = tp.scalar[lev] + e * N;
+    T ua[P];
+#pragma unroll
+    for (int a = 0; a < P; ++a) ua[a] = active ? te[t + a * TPE] : T(0);
+    if (mc != T(0) && active) {
+#pragma unroll
+      for (int a = 0; a < P; ++a) acc[a] += mc * wd[t + a * TPE] * ua[a];
+    }
+    if (!conv) continue;
+    ve += e * N * DIM;
+    cof_fence(geom);
+    T d0[P];
+    line_apply<T, P, false>(dm, ua, d0);
+    if (lane_ok) {
+#pragma unroll
+      for (int a = 0; a < P; ++a) {
+        s0[a * SA + i * SB + j] = ua[a];
+        if (DIM == 3) s1[a * SA + i * SB + j] = ua[a];
+      }
+    }
+    __syncthreads();
+    if (lane_ok) {  // last axis
+      T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
+      T x[P], y[P];
+#pragma unroll
+      for (int m = 0; m < P; ++m) x[m] = line[m];
+      line_apply<T, P, false>(dm, x, y);
+#pragma unroll
+      for (int m = 0; m < P; ++m) line[m] = y[m];
+    }
+    if (DIM == 3 && lane_ok) {  // middle axis
+      T* line = s0 + i * SA + j;
+      T x[P], y[P];
+#pragma unroll
+      for (int m = 0; m < P; ++m) x[m] = line[m * SB];
+      line_apply<T, P, false>(dm, x, y);
+#pragma unroll
+      for (int m = 0; m < P; ++m) line[m * SB] = y[m];
+    }
+    __syncthreads();
+    if (active) {
+#pragma unroll
+      for (int a = 0; a < P; ++a) {
+        const int o = a * SA + i * SB + j;
+        const T* vq = ve + (int64_t)(t + a * TPE) * DIM;
+        T vel[DIM];
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) vel[c] = vq[c];
+        T K[DIM * DIM];
+        geom.cof(dm, a, K);
+        T v = T(0);
+#pragma unroll
+        for (int ax = 0; ax < DIM; ++ax) {
+          T U = T(0);                 // contravariant velocity along xi_ax
+#pragma unroll
+          for (int c = 0; c < DIM; ++c) U += K[ax * DIM + c] * vel[c];
+          const T g = ax == 0 ? d0[a] : (ax == 1 ? s0[o] : s1[o]);
+          v += U * g;
+        }
+        acc[a] += cc * v;
+      }
+    }
+    __syncthreads();   // the next level overwrites the tensor pair
+  }
+
+  if (active) {
+    const T* se = tp.source ? tp.source + e * N : nullptr;
+    T* oe = tp.out + e * N;
+#pragma unroll
+    for (int a = 0; a < P; ++a) {
+      const int q = t + a * TPE;
+      T v = acc[a];
+      if (se) v += wd[q] * se[q];
+      oe[q] = v;
+    }
+  }
+}
+
+template <typename T, int P, int DIM>
+int launch_transport_rhs(const TransportParams<T>& tp, hipStream_t stream) {
+  using Tile = HelmholtzTile<T, P, DIM>;
+  const StokesParams<T>& prm = tp.geo;
+  const int64_t groups = (prm.num_elements + Tile::EPB - 1) / Tile::EPB;
+  if (groups > 0x7fffffff) {
+    set_error("transport_rhs: too many workgroups (%lld)", (long long)groups);
+    return SFEM_EINVAL;
+  }
+  const DMat<T, P> dm =
+      make_dmat<T, P>(prm.dmat_host, prm.weights_host, prm.nodes_host);
+  const dim3 grid((unsigned)groups), block(Tile::BLOCK);
+#define SFEM_LAUNCH_TRANSPORT(GMV)                                           \
+  hipLaunchKernelGGL((transport_rhs_kernel<T, P, DIM, GMV>), grid, block, 0, \
+                     stream, tp, dm)
+  switch (prm.geo_mode) {
+    case GEO_POINT: SFEM_LAUNCH_TRANSPORT(GEO_POINT); break;
+    case GEO_AFFINE: SFEM_LAUNCH_TRANSPORT(GEO_AFFINE); break;
+    default: SFEM_LAUNCH_TRANSPORT(GEO_MULTILINEAR); break;
+  }
+#undef SFEM_LAUNCH_TRANSPORT
+  SFEM_LAUNCH_CHECK();
+  return SFEM_OK;
+}
+
+// Defined once per (dtype, ndim) translation unit, P = 2..12.
+template <typename T, int DIM>
+int dispatch_transport_rhs(const TransportParams<T>& tp, int P,
+                           hipStream_t stream);
+
+#define SFEM_TRANSPORT_CASE(PP_) \
+  case PP_: return launch_transport_rhs<T, PP_, DIM>(tp, stream);
+
+#define SFEM_DEFINE_TRANSPORT_DISPATCH(TYPE, DIMV)                           \
+  template <>                                                                \
+  int dispatch_transport_rhs<TYPE, DIMV>(const TransportParams<TYPE>& tp,    \
+                                         int P, hipStream_t stream) {        \
+    using T = TYPE;                                                          \
+    constexpr int DIM = DIMV;                                                \
+    switch (P) {                                                             \
+      SFEM_TRANSPORT_CASE(2) SFEM_TRANSPORT_CASE(3) SFEM_TRANSPORT_CASE(4)   \
+      SFEM_TRANSPORT_CASE(5) SFEM_TRANSPORT_CASE(6) SFEM_TRANSPORT_CASE(7)   \
+      SFEM_TRANSPORT_CASE(8) SFEM_TRANSPORT_CASE(9) SFEM_TRANSPORT_CASE(10)  \
+      SFEM_TRANSPORT_CASE(11) SFEM_TRANSPORT_CASE(12)                        \
+      default:                                                               \
+        set_error("transport_rhs: P=%d outside the compiled range 2..12",    \
+                  P);                                                        \
+        return SFEM_EUNSUPPORTED;                                            \
+    }                                                                        \
+  }
+
+}  // namespace sfem
