@@ -589,6 +589,56 @@ typedef struct sfem_transport_args {
 } sfem_transport_args;
 int sfem_transport_rhs(const sfem_transport_args* args, sfem_stream_t stream);
 
+/* The vector-Jacobian product of sfem_transport_rhs.  The right-hand side is
+ * linear in the source and bilinear in (T_j, u_j); with `cotangent` = lam the
+ * cotangent of `out`, per element and point
+ *
+ *   dsource[q]         = wdet[q] lam[q]
+ *   dscalar[j][q]      = mass_coef[j] wdet[q] lam[q]
+ *                      + conv_coef[j] sum_a (D_a^T (U_j,a . lam))[q],
+ *                        U_j,a = sum_c Kw[a][c] u_j,c
+ *   dvelocity[j][q][c] = conv_coef[j] lam[q] sum_a Kw[a][c][q] (D_a T_j)[q]
+ *
+ * with D_a the derivative along reference axis a.  Geometry arguments, array
+ * layouts, `elem_list` / `num_listed` and the level conventions are those of
+ * sfem_transport_args; element-local, no atomics.  Every output is optional
+ * (NULL skips its work and its stores): without dvelocity[j] the level does
+ * not read scalar[j], which may then be NULL; without dscalar[j] the
+ * transposed derivative stage is skipped.  A level with velocity[j] NULL or
+ * conv_coef[j] = 0 contributes its mass term to dscalar[j] only (a
+ * dvelocity[j] given with conv_coef[j] = 0 is written as zeros).  Rows of
+ * elements outside the launch are not written.  `wdet` may be NULL when no
+ * dscalar[j] with mass_coef[j] != 0 and no dsource is asked for.
+ * ndim outside 2..3, P outside 2..12, more than SFEM_TRANSPORT_LEVELS levels
+ * and any other geo_mode return SFEM_EUNSUPPORTED; a NULL cotangent or dmat,
+ * a dvelocity[j] without scalar[j] or velocity[j], a missing geometry array
+ * or a missing required wdet is SFEM_EINVAL.  ABI version 10 (a pure
+ * addition).                                                                */
+typedef struct sfem_transport_vjp_args {
+  const void* cotangent;                        /* lam (E, n)                  */
+  const void* scalar[SFEM_TRANSPORT_LEVELS];    /* T_j; may be NULL when       */
+                                                /* dvelocity[j] is NULL        */
+  const void* velocity[SFEM_TRANSPORT_LEVELS];  /* u_j (E, n, ndim) or NULL    */
+  double mass_coef[SFEM_TRANSPORT_LEVELS];
+  double conv_coef[SFEM_TRANSPORT_LEVELS];
+  const void* wdet;       /* (E, n) or NULL                                   */
+  void* dscalar[SFEM_TRANSPORT_LEVELS];         /* (E, n) or NULL              */
+  void* dvelocity[SFEM_TRANSPORT_LEVELS];       /* (E, n, ndim) or NULL        */
+  void* dsource;          /* (E, n) or NULL                                   */
+  const void* kfac;       /* per-point weighted cofactors or NULL             */
+  const void* geo_elem;   /* (E, 24) or NULL                                  */
+  const int32_t* geo_index; /* (E,) slot of element e in kfac, or NULL = e    */
+  const int32_t* elem_list; /* element ids of this launch, or NULL = all      */
+  const void* dmat;       /* HOST (P, P)                                      */
+  const void* weights;    /* HOST (P,)                                        */
+  const void* nodes;      /* HOST (P,)                                        */
+  int64_t num_elements;
+  int64_t num_listed;
+  int32_t num_levels, ndim, P, dtype, geo_mode;
+} sfem_transport_vjp_args;
+int sfem_transport_rhs_vjp(const sfem_transport_vjp_args* args,
+                           sfem_stream_t stream);
+
 /* ------------------------------------------------------------ CG kernels ---
  * Preconditioned CG of linalg/cg.py:30-97 with device-resident scalars: no
  * host synchronisation inside an iteration (the reference keeps its loop on

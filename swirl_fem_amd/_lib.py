@@ -124,6 +124,25 @@ class TransportArgs(ctypes.Structure):
   ]
 
 
+class TransportVjpArgs(ctypes.Structure):
+  """Mirror of `struct sfem_transport_vjp_args`."""
+  _fields_ = [
+      ('cotangent', c_ptr),
+      ('scalar', c_ptr * SFEM_TRANSPORT_LEVELS),
+      ('velocity', c_ptr * SFEM_TRANSPORT_LEVELS),
+      ('mass_coef', c_dbl * SFEM_TRANSPORT_LEVELS),
+      ('conv_coef', c_dbl * SFEM_TRANSPORT_LEVELS),
+      ('wdet', c_ptr),
+      ('dscalar', c_ptr * SFEM_TRANSPORT_LEVELS),
+      ('dvelocity', c_ptr * SFEM_TRANSPORT_LEVELS),
+      ('dsource', c_ptr), ('kfac', c_ptr),
+      ('geo_elem', c_ptr), ('geo_index', c_ptr), ('elem_list', c_ptr),
+      ('dmat', c_ptr), ('weights', c_ptr), ('nodes', c_ptr),
+      ('num_elements', c_i64), ('num_listed', c_i64), ('num_levels', c_i32),
+      ('ndim', c_i32), ('P', c_i32), ('dtype', c_i32), ('geo_mode', c_i32),
+  ]
+
+
 class DiagArgs(ctypes.Structure):
   """Mirror of `struct sfem_diag_args`."""
   _fields_ = [
@@ -248,6 +267,7 @@ SIGNATURES = {
     'sfem_stokes_e_second': [c_ptr, c_ptr],
     'sfem_stokes_convect_local': [c_ptr, c_ptr],
     'sfem_transport_rhs': [ctypes.POINTER(TransportArgs), c_ptr],
+    'sfem_transport_rhs_vjp': [ctypes.POINTER(TransportVjpArgs), c_ptr],
     'sfem_pmg_prolong': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64,
                          c_i32, c_i32, c_i32, c_i32, c_i32, c_ptr],
     'sfem_pmg_restrict': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64,

@@ -1254,6 +1254,88 @@ def transport_rhs(levels, parts, host, ndim, P, source=None, wdet=None):
   return out
 
 
+def transport_rhs_vjp(cotangent, levels, parts, host, ndim, P, wdet, want):
+  """The vector-Jacobian product of `transport_rhs`
+  (`sfem_transport_rhs_vjp`).  `cotangent` (E, P^d); `levels` as for
+  `transport_rhs` (a level's T may be None when its velocity gradient is not
+  wanted); `want` = ([(scalar?, velocity?) per level], source?).  One launch
+  per geometry part covers all levels.  Returns ([(dT (E, P^d), du (E, P^d,
+  d)) per level], dsource (E, P^d)) with None where not wanted; rows of
+  elements that no part lists stay zero."""
+  levels = list(levels)
+  want_levels, want_source = want
+  want_levels = [(bool(a), bool(b)) for a, b in want_levels]
+  if ndim not in (2, 3) or not 2 <= P <= 12:
+    raise NotImplementedError(
+        f'transport_rhs_vjp: ndim={ndim}, P={P} outside the compiled range '
+        '(ndim 2..3, P 2..12)')
+  if not 1 <= len(levels) <= _lib.SFEM_TRANSPORT_LEVELS:
+    raise ValueError(f'expected 1..{_lib.SFEM_TRANSPORT_LEVELS} levels, got '
+                     f'{len(levels)}')
+  if len(want_levels) != len(levels):
+    raise ValueError(f'`want` names {len(want_levels)} levels, `levels` has '
+                     f'{len(levels)}')
+  if cotangent is None:
+    raise ValueError('transport_rhs_vjp needs a cotangent')
+  dev = _dev(cotangent)
+  shape = (cotangent.shape[0], P ** ndim)
+  tensors = []
+
+  def field(t, name, trailing=()):
+    if t is None:
+      return None
+    if tuple(t.shape) != shape + trailing:
+      raise ValueError(f'{name}: expected {shape + trailing}, got '
+                       f'{tuple(t.shape)}')
+    if t.dtype != cotangent.dtype or t.device != cotangent.device:
+      raise ValueError(f'{name}: expected the dtype and device of the '
+                       'cotangent')
+    t = t.contiguous()
+    tensors.append(t)         # keeps the copy alive until the launches
+    return t
+  lam = field(cotangent, 'cotangent')
+  args = _lib.TransportVjpArgs(num_levels=len(levels),
+                               cotangent=lam.data_ptr())
+  zeros = lambda s: torch.zeros(s, dtype=lam.dtype, device=dev)
+  mass = bool(want_source)
+  out = []
+  for n, ((T, u, mc, cc), (wT, wu)) in enumerate(zip(levels, want_levels)):
+    if wu and (T is None or u is None):
+      raise ValueError(f'level {n}: the velocity gradient needs the level\'s '
+                       'scalar and velocity')
+    args.scalar[n] = _dptr(field(T if wu else None, f'level {n}: scalar'))
+    args.velocity[n] = _dptr(field(u, f'level {n}: velocity', (ndim,)))
+    args.mass_coef[n], args.conv_coef[n] = float(mc), float(cc)
+    mass = mass or (wT and float(mc) != 0.0)
+    dT = zeros(shape) if wT else None
+    du = zeros(shape + (ndim,)) if wu else None
+    args.dscalar[n], args.dvelocity[n] = _dptr(dT), _dptr(du)
+    out.append((dT, du))
+  if mass and wdet is None:
+    raise ValueError('mass terms and the source gradient need `wdet`')
+  args.wdet = _dptr(field(wdet, 'wdet'))
+  dsource = zeros(shape) if want_source else None
+  args.dsource = _dptr(dsource)
+  host = {k: _host(v, lam.dtype) for k, v in host.items()}
+  args.dmat, args.weights = _hptr(host['dmat']), _hptr(host['weights'])
+  args.nodes = _hptr(host['nodes'])
+  args.num_elements, args.ndim, args.P = shape[0], ndim, P
+  args.dtype = _dtype_code(lam)
+  with torch.cuda.device(dev):
+    for part in parts:
+      lst = part.get('elem_list')
+      args.kfac = _dptr(part.get('kfac'))
+      args.geo_elem = _dptr(part.get('geo_elem'))
+      args.geo_index = _dptr(part.get('geo_index'))
+      args.elem_list = _dptr(lst)
+      args.num_listed = 0 if lst is None else lst.numel()
+      args.geo_mode = part['geo_mode']
+      _lib.check(_lib.load().sfem_transport_rhs_vjp(ctypes.byref(args),
+                                                    _stream(dev)),
+                 'sfem_transport_rhs_vjp')
+  return out, dsource
+
+
 from swirl_fem_amd.core.layout import is_component_major  # noqa: E402
 
 

@@ -24,6 +24,10 @@ q-function path):
     helmholtz local  y = L u         ->  u_bar = L y_bar
     stokes div       y = D u         ->  u_bar = D^T y_bar  (unmasked grad_t)
     stokes grad_t    y = M D^T p     ->  p_bar = D (M y_bar)
+
+The right-hand side of a scalar-transport step (`_ops.transport_rhs`) is
+linear in the source and bilinear in each level's (T, u); its cotangents come
+from one fused kernel (`_ops.transport_rhs_vjp`).
 """
 
 from __future__ import annotations
@@ -216,6 +220,50 @@ class _StokesGradT(torch.autograd.Function):
     if ctx.keep is not None:
       g = g * ctx.keep[:, None]
     return ctx.op.div(g), None, None
+
+
+class _TransportRhsLocal(torch.autograd.Function):
+  """`_ops.transport_rhs` of a `TransportRhs` on the quadrature grid.  The
+  tensors after the fixed arguments are (T_0, u_0, T_1, u_1, ..., source), None
+  where a level has no velocity / there is no source."""
+
+  @staticmethod
+  def forward(ctx, op, coefs, *tensors):
+    fes = op.fespace
+    ctx.op, ctx.coefs = op, coefs
+    ctx.save_for_backward(*tensors)
+    vals = [None if t is None else t.detach() for t in tensors]
+    levels = [(vals[2 * n], vals[2 * n + 1], mc, cc)
+              for n, (mc, cc) in enumerate(coefs)]
+    source = vals[-1]
+    mass = source is not None or any(mc != 0.0 for mc, _ in coefs)
+    return _ops.transport_rhs(
+        levels, op.parts, op.host, fes.mesh.ndim, fes.quadrature.num_points,
+        source=source, wdet=op.point_weights() if mass else None)
+
+  @staticmethod
+  @torch.autograd.function.once_differentiable
+  def backward(ctx, g):
+    op, coefs = ctx.op, ctx.coefs
+    fes = op.fespace
+    vals = ctx.saved_tensors
+    need = ctx.needs_input_grad[2:]
+    levels = [(vals[2 * n], vals[2 * n + 1], mc, cc)
+              for n, (mc, cc) in enumerate(coefs)]
+    want = [(need[2 * n], need[2 * n + 1]) for n in range(len(coefs))]
+    dlevels, dsource = _ops.transport_rhs_vjp(
+        g, levels, op.parts, op.host, fes.mesh.ndim,
+        fes.quadrature.num_points, op.point_weights(), (want, need[-1]))
+    return (None, None) + tuple(t for pair in dlevels for t in pair) + (
+        dsource,)
+
+
+def transport_rhs_local(op, levels, source_q=None):
+  """`op.apply_local(levels, source_q)` of a `TransportRhs` under autograd."""
+  levels = list(levels)
+  coefs = tuple((float(mc), float(cc)) for _, _, mc, cc in levels)
+  tensors = [t for T, u, _, _ in levels for t in (T, u)] + [source_q]
+  return _TransportRhsLocal.apply(op, coefs, *tensors)
 
 
 def helmholtz_apply(op, op_free, keep, u, l0, l1):

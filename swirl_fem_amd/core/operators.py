@@ -28,6 +28,7 @@ import torch
 
 from swirl_fem_amd import switches
 from swirl_fem_amd import _ops
+from swirl_fem_amd.core import autodiff
 
 MAX_FUSED_P = 12
 
@@ -2299,6 +2300,8 @@ class TransportRhs:
     conv_coef) on the quadrature grid -> (E, Q^d), the integrand times W."""
     fes = self.fespace
     levels = list(levels)
+    if autodiff.needs_grad(source_q, *[t for l in levels for t in l[:2]]):
+      return autodiff.transport_rhs_local(self, levels, source_q)
     mass = source_q is not None or any(float(l[2]) != 0.0 for l in levels)
     return _ops.transport_rhs(
         levels, self.parts, self.host, fes.mesh.ndim,
@@ -2332,8 +2335,15 @@ class TransportRhs:
     d = mesh.ndim
     nq = fes.quadrature.num_points ** d
 
+    levels = list(levels)
+    # under autograd the gather and the transposed interpolation take the
+    # routes that carry their transposes; `_basis` and `scatter` switch alone
+    grad = autodiff.needs_grad(source, *[t for l in levels for t in l[:2]])
+    gather_rows = autodiff.gather_rows if grad else _ops.gather_rows
+    basis_eval_t = autodiff.basis_eval_t if grad else _ops.basis_eval_t
+
     def at_points(nodal):      # (N, nc) -> (E, Q^d, nc)
-      loc = _ops.gather_rows(nodal.contiguous(), mesh.elements)
+      loc = gather_rows(nodal.contiguous(), mesh.elements)
       return loc if fes.is_collocated else fes._basis(loc, True, False)[0]
     local = []
     for T, u, mc, cc in levels:
@@ -2367,7 +2377,7 @@ class TransportRhs:
     if ones is None:
       ones = fes._cache['ones_eq'] = torch.ones(
           (mesh.num_elements, nq), dtype=fes.dtype, device=fes.device)
-    r3 = _ops.basis_eval_t(rq[..., None], None, i1, g1, None, ones, d,
-                           mesh.gridpoints_1d.num_points,
-                           fes.quadrature.num_points, 1, False)
+    r3 = basis_eval_t(rq[..., None], None, i1, g1, None, ones, d,
+                      mesh.gridpoints_1d.num_points,
+                      fes.quadrature.num_points, 1, False)
     return mesh.scatter(r3[..., 0])

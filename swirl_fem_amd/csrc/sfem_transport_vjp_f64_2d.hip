@@ -1,0 +1,6 @@
+// Instantiations of the vector-Jacobian product of the scalar-transport
+// right-hand side: double, 2D, P = 2..12.
+#include "sfem_transport_vjp.h"
+namespace sfem {
+SFEM_DEFINE_TRANSPORT_VJP_DISPATCH(double, 2)
+}  // namespace sfem
