@@ -466,6 +466,24 @@ def _dptr(t):
   return None if t is None else t.data_ptr()
 
 
+def _launch_fields(part, host=None, key='geo'):
+  """What every launch description hands to its `*Args` struct, as keyword
+  arguments: the per-point data under `key` ('geo' or 'kfac'), the
+  multilinear coefficients, the element list with its length and the
+  geometry kind; with `host` (`_host`-converted NumPy tables) their
+  pointers as well."""
+  lst = part.get('elem_list')
+  fields = {key: _dptr(part.get(key)), 'geo_elem': _dptr(part.get('geo_elem')),
+            'geo_index': _dptr(part.get('geo_index')),
+            'elem_list': _dptr(lst),
+            'num_listed': 0 if lst is None else lst.numel(),
+            'geo_mode': part['geo_mode']}
+  if host is not None:
+    fields.update(dmat=_hptr(host['dmat']), weights=_hptr(host.get('weights')),
+                  nodes=_hptr(host.get('nodes')))
+  return fields
+
+
 def _helmholtz_args(u, out, enc, part, host, ndim, P, num_elements, num_nodes,
                     lambda0, lambda1, zero_range, dot_out=None,
                     layered_extent=0, dot_slots=0, transpose=False):
@@ -479,7 +497,6 @@ def _helmholtz_args(u, out, enc, part, host, ndim, P, num_elements, num_nodes,
     # component-major storage viewed as (..., ncomp): every component is a
     # contiguous strip
     node_stride, comp_stride = 1, u.stride(-1)
-  lst = part.get('elem_list')
   so = part.get('shared_order')
   cl = part.get('cluster') if enc is not None else None
   if cl is not None:
@@ -501,13 +518,10 @@ def _helmholtz_args(u, out, enc, part, host, ndim, P, num_elements, num_nodes,
       ch = part.get('chains')        # (offsets, elems) int32 device tensors
   return _lib.HelmholtzArgs(
       u=u.data_ptr(), out=out.data_ptr(), enc=_dptr(enc),
-      geo=_dptr(part.get('geo')), geo_elem=_dptr(part.get('geo_elem')),
-      geo_index=_dptr(part.get('geo_index')), elem_list=_dptr(lst),
-      dmat=_hptr(host['dmat']), weights=_hptr(host.get('weights')),
-      nodes=_hptr(host.get('nodes')), num_elements=num_elements,
-      num_listed=0 if lst is None else lst.numel(), num_nodes=num_nodes,
-      zero_begin=int(zero_range[0]), zero_end=int(zero_range[1]), ndim=ndim,
-      P=P, ncomp=ncomp, dtype=_dtype_code(u), geo_mode=part['geo_mode'],
+      **_launch_fields(part, host), num_elements=num_elements,
+      num_nodes=num_nodes, zero_begin=int(zero_range[0]),
+      zero_end=int(zero_range[1]), ndim=ndim, P=P, ncomp=ncomp,
+      dtype=_dtype_code(u),
       colored=int(bool(part.get('colored', False))), lambda0=float(lambda0),
       lambda1=float(lambda1), node_stride=node_stride,
       comp_stride=comp_stride,
@@ -1036,7 +1050,6 @@ def _stokes_args(vec, enc, penc, part, host, ndim, P, zero_range,
   node_stride = comp_stride = 0
   if not vec.is_contiguous():
     node_stride, comp_stride = 1, vec.stride(-1)
-  lst = part.get('elem_list')
   ft = part.get('facet_table')
   ch = part.get('chains') if ft is not None else None
   if ft is not None:
@@ -1044,15 +1057,11 @@ def _stokes_args(vec, enc, penc, part, host, ndim, P, zero_range,
                 chain_elems=_dptr(ch[1]), num_chains=ch[0].numel() - 1)
     shared_order = None
   return _lib.StokesArgs(
-      enc=_dptr(enc), penc=_dptr(penc), kfac=_dptr(part.get('kfac')),
-      geo_elem=_dptr(part.get('geo_elem')),
-      geo_index=_dptr(part.get('geo_index')), elem_list=_dptr(lst),
-      dmat=_hptr(host['dmat']), weights=_hptr(host['weights']),
-      nodes=_hptr(host['nodes']), interp=_hptr(host['interp']),
-      num_elements=enc.shape[0], num_listed=0 if lst is None else lst.numel(),
+      enc=_dptr(enc), penc=_dptr(penc), **_launch_fields(part, host, 'kfac'),
+      interp=_hptr(host['interp']), num_elements=enc.shape[0],
       num_nodes=vec.shape[0], zero_begin=int(zero_range[0]),
       zero_end=int(zero_range[1]), ndim=ndim, P=P, dtype=_dtype_code(vec),
-      geo_mode=part['geo_mode'], node_stride=node_stride,
+      node_stride=node_stride,
       comp_stride=comp_stride, shared_order=_dptr(shared_order),
       shared_stride=0 if shared_order is None else shared_order.shape[1],
       **ptrs)
@@ -1179,19 +1188,31 @@ def stokes_convect_local(u_local, parts, host, ndim, P):
   host = {k: _host(v, u_local.dtype) for k, v in host.items()}
   with torch.cuda.device(dev):
     for part in parts:
-      lst = part.get('elem_list')
       args = _lib.StokesArgs(
           u=u_local.data_ptr(), out=out.data_ptr(),
-          kfac=_dptr(part.get('kfac')), geo_elem=_dptr(part.get('geo_elem')),
-          geo_index=_dptr(part.get('geo_index')), elem_list=_dptr(lst),
-          dmat=_hptr(host['dmat']), weights=_hptr(host['weights']),
-          nodes=_hptr(host['nodes']), num_elements=E,
-          num_listed=0 if lst is None else lst.numel(), ndim=ndim, P=P,
-          dtype=_dtype_code(u_local), geo_mode=part['geo_mode'])
+          **_launch_fields(part, host, 'kfac'), num_elements=E, ndim=ndim,
+          P=P, dtype=_dtype_code(u_local))
       _lib.check(_lib.load().sfem_stokes_convect_local(ctypes.byref(args),
                                                        _stream(dev)),
                  'sfem_stokes_convect_local')
   return out
+
+
+def _field(t, name, shape, ref, ref_name, keep):
+  """An optional input of the transport entry points: None, or `t` made
+  contiguous after checking `shape` and the dtype and device of `ref`
+  (`ref_name` in the error text).  `keep` collects the result, which holds a
+  possible copy alive until the launches."""
+  if t is None:
+    return None
+  if tuple(t.shape) != shape:
+    raise ValueError(f'{name}: expected {shape}, got {tuple(t.shape)}')
+  if t.dtype != ref.dtype or t.device != ref.device:
+    raise ValueError(f'{name}: expected the dtype and device of the '
+                     f'{ref_name}')
+  t = t.contiguous()
+  keep.append(t)
+  return t
 
 
 def transport_rhs(levels, parts, host, ndim, P, source=None, wdet=None):
@@ -1208,19 +1229,8 @@ def transport_rhs(levels, parts, host, ndim, P, source=None, wdet=None):
   dev = _dev(first)
   shape = (first.shape[0], P ** ndim)
   tensors = []
-
-  def field(t, name, trailing=()):
-    if t is None:
-      return None
-    if tuple(t.shape) != shape + trailing:
-      raise ValueError(f'{name}: expected {shape + trailing}, got '
-                       f'{tuple(t.shape)}')
-    if t.dtype != first.dtype or t.device != first.device:
-      raise ValueError(f'{name}: expected the dtype and device of the first '
-                       'scalar')
-    t = t.contiguous()
-    tensors.append(t)         # keeps the copy alive until the launches
-    return t
+  field = lambda t, name, trailing=(): _field(
+      t, name, shape + trailing, first, 'first scalar', tensors)
   args = _lib.TransportArgs(num_levels=len(levels))
   mass = source is not None
   for n, (T, u, mc, cc) in enumerate(levels):
@@ -1235,19 +1245,12 @@ def transport_rhs(levels, parts, host, ndim, P, source=None, wdet=None):
   out = torch.empty(shape, dtype=first.dtype, device=dev)
   host = {k: _host(v, first.dtype) for k, v in host.items()}
   args.out = out.data_ptr()
-  args.dmat, args.weights = _hptr(host['dmat']), _hptr(host['weights'])
-  args.nodes = _hptr(host['nodes'])
   args.num_elements, args.ndim, args.P = shape[0], ndim, P
   args.dtype = _dtype_code(first)
   with torch.cuda.device(dev):
     for part in parts:
-      lst = part.get('elem_list')
-      args.kfac = _dptr(part.get('kfac'))
-      args.geo_elem = _dptr(part.get('geo_elem'))
-      args.geo_index = _dptr(part.get('geo_index'))
-      args.elem_list = _dptr(lst)
-      args.num_listed = 0 if lst is None else lst.numel()
-      args.geo_mode = part['geo_mode']
+      for name, value in _launch_fields(part, host, 'kfac').items():
+        setattr(args, name, value)
       _lib.check(_lib.load().sfem_transport_rhs(ctypes.byref(args),
                                                 _stream(dev)),
                  'sfem_transport_rhs')
@@ -1280,19 +1283,8 @@ def transport_rhs_vjp(cotangent, levels, parts, host, ndim, P, wdet, want):
   dev = _dev(cotangent)
   shape = (cotangent.shape[0], P ** ndim)
   tensors = []
-
-  def field(t, name, trailing=()):
-    if t is None:
-      return None
-    if tuple(t.shape) != shape + trailing:
-      raise ValueError(f'{name}: expected {shape + trailing}, got '
-                       f'{tuple(t.shape)}')
-    if t.dtype != cotangent.dtype or t.device != cotangent.device:
-      raise ValueError(f'{name}: expected the dtype and device of the '
-                       'cotangent')
-    t = t.contiguous()
-    tensors.append(t)         # keeps the copy alive until the launches
-    return t
+  field = lambda t, name, trailing=(): _field(
+      t, name, shape + trailing, cotangent, 'cotangent', tensors)
   lam = field(cotangent, 'cotangent')
   args = _lib.TransportVjpArgs(num_levels=len(levels),
                                cotangent=lam.data_ptr())
@@ -1317,19 +1309,12 @@ def transport_rhs_vjp(cotangent, levels, parts, host, ndim, P, wdet, want):
   dsource = zeros(shape) if want_source else None
   args.dsource = _dptr(dsource)
   host = {k: _host(v, lam.dtype) for k, v in host.items()}
-  args.dmat, args.weights = _hptr(host['dmat']), _hptr(host['weights'])
-  args.nodes = _hptr(host['nodes'])
   args.num_elements, args.ndim, args.P = shape[0], ndim, P
   args.dtype = _dtype_code(lam)
   with torch.cuda.device(dev):
     for part in parts:
-      lst = part.get('elem_list')
-      args.kfac = _dptr(part.get('kfac'))
-      args.geo_elem = _dptr(part.get('geo_elem'))
-      args.geo_index = _dptr(part.get('geo_index'))
-      args.elem_list = _dptr(lst)
-      args.num_listed = 0 if lst is None else lst.numel()
-      args.geo_mode = part['geo_mode']
+      for name, value in _launch_fields(part, host, 'kfac').items():
+        setattr(args, name, value)
       _lib.check(_lib.load().sfem_transport_rhs_vjp(ctypes.byref(args),
                                                     _stream(dev)),
                  'sfem_transport_rhs_vjp')
@@ -1394,16 +1379,11 @@ def helmholtz_sens(u_local, lam_local, parts, host, ndim, P, lambda0, lambda1,
                        'tensor of the field\'s dtype and device')
   with torch.cuda.device(dev):
     for part in parts:
-      lst = part.get('elem_list')
       args = _lib.HelmholtzSensArgs(
           u=u_local.data_ptr(), lam=lam_local.data_ptr(),
           dkappa=_dptr(out[0]), dsigma=_dptr(out[1]), dbeta=_dptr(out[2]),
-          geo=_dptr(part.get('geo')), geo_elem=_dptr(part.get('geo_elem')),
-          geo_index=_dptr(part.get('geo_index')), elem_list=_dptr(lst),
-          dmat=_hptr(host['dmat']), weights=_hptr(host.get('weights')),
-          nodes=_hptr(host.get('nodes')), num_elements=E,
-          num_listed=0 if lst is None else lst.numel(), ndim=ndim, P=P,
-          ncomp=ncomp, dtype=_dtype_code(u_local), geo_mode=part['geo_mode'],
+          **_launch_fields(part, host), num_elements=E, ndim=ndim, P=P,
+          ncomp=ncomp, dtype=_dtype_code(u_local),
           lambda0=float(lambda0), lambda1=float(lambda1))
       _lib.check(_lib.load().sfem_helmholtz_sens(ctypes.byref(args),
                                                  _stream(dev)),
@@ -1606,16 +1586,12 @@ def helmholtz_diag(parts, num_elements, ndim, P, dtil, weights, nodes,
            if want_stiff else None)
   with torch.cuda.device(dev):
     for part in parts:
-      lst = part.get('elem_list')
-      geo, geo_elem = part.get('geo'), part.get('geo_elem')
-      _dev(geo, geo_elem, lst, part.get('geo_index'), dt_d)
+      _dev(part.get('geo'), part.get('geo_elem'), part.get('elem_list'),
+           part.get('geo_index'), dt_d)
       args = _lib.DiagArgs(
-          mass_out=_ptr(mass), stiff_out=_ptr(stiff), geo=_ptr(geo),
-          geo_elem=_ptr(geo_elem), geo_index=_ptr(part.get('geo_index')),
-          elem_list=_ptr(lst), bmat=_ptr(b_d), dtil=_ptr(dt_d),
-          weights=_ptr(w_d), nodes=_ptr(x_d), num_elements=num_elements,
-          num_listed=0 if lst is None else lst.numel(), ndim=ndim, P=P, Q=Q,
-          dtype=_DT[dtype], geo_mode=part['geo_mode'],
+          mass_out=_ptr(mass), stiff_out=_ptr(stiff), **_launch_fields(part),
+          bmat=_ptr(b_d), dtil=_ptr(dt_d), weights=_ptr(w_d), nodes=_ptr(x_d),
+          num_elements=num_elements, ndim=ndim, P=P, Q=Q, dtype=_DT[dtype],
           kappa=_ptr(part.get('kappa')), sigma=_ptr(part.get('sigma')),
           coef_mode=int(part.get('coef_mode', _lib.COEF_NONE)))
       _lib.check(_lib.load().sfem_helmholtz_diag(ctypes.byref(args),

@@ -273,6 +273,27 @@ class FiniteElementSpace:
         self.mesh.gridpoints_1d.num_points, self.quadrature.num_points,
         self.is_collocated, want_val, want_grad)
 
+  def _interpolate(self, u3):
+    """Element-local values (E, n, nc) at the quadrature points (E, Q^d, nc):
+    the values of `_basis`; `u3` itself when collocated."""
+    return u3 if self.is_collocated else self._basis(u3, True, False)[0]
+
+  def _interpolate_t(self, rq, grad=False):
+    """The bare transpose of `_interpolate`, (E, Q^d, nc) -> (E, n, nc): no
+    weights (`sfem_basis_eval_t` with ones for w detJ); `rq` itself when
+    collocated.  `grad`: the route that carries its own transpose."""
+    if self.is_collocated:
+      return rq
+    mesh, q = self.mesh, self.quadrature.num_points
+    i1, g1 = self._matrices()
+    key = 'ones_eq'
+    if key not in self._cache:
+      self._cache[key] = torch.ones((mesh.num_elements, q ** mesh.ndim),
+                                    dtype=self.dtype, device=self.device)
+    ev = autodiff.basis_eval_t if grad else _ops.basis_eval_t
+    return ev(rq, None, i1, g1, None, self._cache[key], mesh.ndim,
+              mesh.gridpoints_1d.num_points, q, rq.shape[-1], False)
+
   # ------------------------------------------------------------ q-functions
   def _evaluate(self, f) -> torch.Tensor:
     """Evaluates a q-function at every element's quadrature points."""
@@ -507,8 +528,7 @@ class FiniteElementSpace:
     scalar = u.dim() == 1
     loc = (self.mesh.gather(u)[..., None] if scalar
            else _ops.gather_rows(u.contiguous(), self.mesh.elements))
-    vals = loc if self.is_collocated else self._basis(loc.contiguous(), True,
-                                                      False)[0]
+    vals = self._interpolate(loc.contiguous())
     return (vals[..., 0] if scalar else vals).contiguous()
 
   def helmholtz_operator(self, dirichlet_mask=None, geometry='auto',

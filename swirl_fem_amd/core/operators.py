@@ -106,6 +106,72 @@ STOKES_FACET_P = (6, 7, 8)     # ... and the facet-table Stokes kernels
 BOX_TOL = {torch.float64: 1e-13, torch.float32: 5e-7}
 
 
+def _geometry_parts(fespace, key, point_setup, geometry, *, multilinear=False,
+                    corners=False):
+  """One launch description per geometry kind present, for kernels on the
+  quadrature grid of `fespace`: `geo_mode`; `elem_list` when the kind is a
+  strict subset of the elements; for curved elements the stored per-point
+  data `point_setup(invjacs, jacdets, w)` under `key` ('geo' or 'kfac') with
+  `geo_index` (element -> row) when they are a subset; otherwise `geo_elem`,
+  the multilinear coefficients.  `geometry`: 'auto', 'stored' (per-point data
+  for every element) and, where the caller accepts it (`multilinear`),
+  'multilinear' (no affine shortcut).  `corners`: node families without end
+  points have no corner nodes to read the coefficients from and take 'stored'.
+  Returns (parts, the (E, 24) coefficients or None, elements per kind)."""
+  mesh = fespace.mesh
+  E, dev = mesh.num_elements, fespace.device
+  if corners:
+    from swirl_fem_amd.core.interpolation import NodeType
+    if mesh.gridpoints_1d.node_type not in (
+        NodeType.GAUSS_LOBATTO_LEGENDRE, NodeType.NEWTON_COTES):
+      geometry = 'stored'
+  if geometry == 'stored':
+    kind = torch.zeros(E, dtype=torch.int32, device=dev)
+    coef = None
+  else:
+    kind, coef = classify_geometry(fespace)
+    if multilinear and geometry == 'multilinear':
+      kind = torch.where(kind == _GEO_AFFINE,
+                         torch.full_like(kind, _GEO_MULTILINEAR), kind)
+  w = torch.as_tensor(fespace.quadrature.weights_nd(mesh.ndim),
+                      dtype=fespace.dtype, device=dev)
+  counts = {k: int((kind == k).sum()) for k in
+            (_GEO_POINT, _GEO_AFFINE, _GEO_MULTILINEAR)}
+  parts = []
+  for k in (_GEO_AFFINE, _GEO_MULTILINEAR, _GEO_POINT):
+    if counts[k] == 0:
+      continue
+    part = {'geo_mode': k}
+    sel = kind == k
+    if counts[k] < E:
+      part['elem_list'] = torch.nonzero(sel).reshape(-1).to(
+          torch.int32).contiguous()
+    if k != _GEO_POINT:
+      part['geo_elem'] = coef
+    elif counts[k] < E:
+      part[key] = point_setup(fespace.invjacs[sel].contiguous(),
+                              fespace.jacdets[sel].contiguous(), w)
+      part['geo_index'] = (torch.cumsum(sel, 0) - 1).to(
+          torch.int32).contiguous()
+    else:
+      part[key] = point_setup(fespace.invjacs, fespace.jacdets, w)
+    parts.append(part)
+  return parts, coef, counts
+
+
+def _host_tables(fespace, quadrature_grid):
+  """The host tables of a launch (NumPy): differentiation matrix, weights and
+  points of the grid the kernels work on -- the nodes of a collocated
+  operator, or the quadrature points (`quadrature_grid`)."""
+  if quadrature_grid:
+    dmat, grid = _quadrature_dmat(fespace), fespace.quadrature.nodes
+  else:
+    dmat = fespace.interpolator._differentiation_matrix_1d()
+    grid = fespace.mesh.gridpoints_1d
+  return {'dmat': dmat, 'weights': np.asarray(fespace.quadrature.weights),
+          'nodes': np.asarray(grid.node_values)}
+
+
 def chain_segment_length(num_elements):
   """Elements per chain segment (= per workgroup of a chain launch): 8 on
   large meshes; shorter when that would leave the 256 CUs x 16 waves of an
@@ -706,10 +772,15 @@ def reduce_velocity_gradient(g, source):
                    f'{tuple(g.shape)}')
 
 
-def _sensitivity(op, ul, ll, host_P, lambda0, lambda1, want):
-  """Shared by the two operator classes: `ul`, `ll` (E, npts) at the
+def _sensitivity(op, u, lam, lambda0, lambda1, want):
+  """Shared by the two operator classes: nodal `u`, `lam` (N,), taken to the
   operator's points -> the three gradients in the callers' forms."""
   fes = op.fespace
+  mesh = fes.mesh
+  for v in (u, lam):
+    if tuple(v.shape) != (mesh.num_nodes,):
+      raise ValueError(f'expected ({mesh.num_nodes},) nodal values, got '
+                       f'{tuple(v.shape)}')
   src_k, src_c = op.coef_source
   src_b = op.velocity_source
   tensor = lambda v: v is not None and not _is_callable_source(v)
@@ -718,11 +789,13 @@ def _sensitivity(op, ul, ll, host_P, lambda0, lambda1, want):
   wb = want[2] and tensor(src_b)
   if not (wk or wc or wb):
     return None, None, None
+  ul, ll = (fes._interpolate(mesh.gather(v.detach().to(fes.dtype))[..., None])
+            [..., 0].contiguous() for v in (u, lam))
   # the launches without coefficients: curved launches of `parts` carry k and
   # c folded into their stored factors, the sensitivities need bare G and W
   dk, dc, dbeta = _ops.helmholtz_sens(
-      ul, ll, op._geo_parts, op.host, fes.mesh.ndim, host_P, lambda0, lambda1,
-      want=(wk, wc, wb))
+      ul, ll, op._geo_parts, op.host, mesh.ndim, len(op.host['nodes']),
+      lambda0, lambda1, want=(wk, wc, wb))
   db = None if dbeta is None else unfold_velocity_gradient(fes, dbeta)
   return (reduce_coefficient_gradient(dk, src_k),
           reduce_coefficient_gradient(dc, src_c),
@@ -754,6 +827,32 @@ def _advection_parts(parts, beta, num_elements, npts):
                   coef_mode=_lib.COEF_POINT)
     out.append(part)
   return out
+
+
+def _coefficient_intake(fespace, assembly, npts, points, parts, diffusivity,
+                        reaction, velocity):
+  """What `create` makes of its coefficients and velocity at the operator's
+  `npts` points per element (`points()`: their coordinates (E, npts, d),
+  built only if a callable asks for them): (coefs, velocity, beta, parts) --
+  the normal forms of `coefficient` and `velocity_field`, the folded velocity
+  and `parts` with all of them attached; None / `parts` itself without."""
+  mesh = fespace.mesh
+  E = mesh.num_elements
+  coefs = beta = None
+  if diffusivity is not None or reaction is not None:
+    _check_coefficient_mesh(mesh, assembly)
+    coefs = tuple(coefficient(value, name, E, npts, points, fespace.dtype,
+                              fespace.device)
+                  for value, name in ((diffusivity, 'diffusivity'),
+                                      (reaction, 'reaction')))
+    parts = _coefficient_parts(parts, *coefs, E, npts, mesh.ndim)
+  if velocity is not None:
+    _check_velocity_mesh(mesh, assembly)
+    velocity = velocity_field(velocity, E, npts, mesh.ndim, points,
+                              fespace.dtype, fespace.device)
+    beta = fold_velocity(fespace, velocity)
+    parts = _advection_parts(parts, beta, E, npts)
+  return coefs, velocity, beta, parts
 
 
 def _advection_diagonal(fespace, parts, beta, dq, keep, bmat):
@@ -875,76 +974,22 @@ class HelmholtzOperator:
       _check_velocity_mesh(fespace.mesh, assembly)
     if assembly not in ('auto', 'cluster', 'atomic', 'colored'):
       raise ValueError(f'unknown assembly mode {assembly!r}')
-    coefs = None
-    if diffusivity is not None or reaction is not None:
-      mesh = fespace.mesh
-      _check_coefficient_mesh(mesh, assembly)
-      npts = mesh.num_nodes_per_element
-      points = mesh.element_coords
-      coefs = (coefficient(diffusivity, 'diffusivity', mesh.num_elements, npts,
-                           points, fespace.dtype, fespace.device),
-               coefficient(reaction, 'reaction', mesh.num_elements, npts,
-                           points, fespace.dtype, fespace.device))
-      if assembly == 'auto':
-        assembly = 'atomic'
-    beta = velocity_source = None
-    if velocity is not None:
-      mesh = fespace.mesh
-      velocity_source = velocity
-      velocity = velocity_field(
-          velocity, mesh.num_elements, mesh.num_nodes_per_element, mesh.ndim,
-          mesh.element_coords, fespace.dtype, fespace.device)
-      beta = fold_velocity(fespace, velocity)
-      if assembly == 'auto':
-        assembly = 'atomic'
+    mesh = fespace.mesh
+    E = mesh.num_elements
+    geo_parts, coef, counts = _geometry_parts(
+        fespace, 'geo', _ops.helmholtz_setup, geometry, multilinear=True)
+    velocity_source = velocity
+    coefs, velocity, beta, parts = _coefficient_intake(
+        fespace, assembly, mesh.num_nodes_per_element, mesh.element_coords,
+        geo_parts, diffusivity, reaction, velocity)
+    if assembly == 'auto' and (coefs is not None or beta is not None):
+      assembly = 'atomic'
     requested = assembly
     if assembly == 'auto':
       assembly = ('cluster' if _cluster_limits(fespace) is not None and
                   switches.get('SFEM_CLUSTER') == '1' else 'atomic')
     elif assembly == 'cluster' and _cluster_limits(fespace) is None:
       raise NotImplementedError('cluster assembly needs ndim = 3, P = 4..8')
-    mesh = fespace.mesh
-    E = mesh.num_elements
-    w = torch.as_tensor(fespace.quadrature.weights_nd(mesh.ndim),
-                        dtype=fespace.dtype, device=fespace.device)
-    if geometry == 'stored':
-      kind = torch.zeros(E, dtype=torch.int32, device=fespace.device)
-      coef = None
-    else:
-      kind, coef = classify_geometry(fespace)
-      if geometry == 'multilinear':
-        kind = torch.where(kind == _GEO_AFFINE,
-                           torch.full_like(kind, _GEO_MULTILINEAR), kind)
-    counts = {k: int((kind == k).sum()) for k in
-              (_GEO_POINT, _GEO_AFFINE, _GEO_MULTILINEAR)}
-    parts = []
-    for k in (_GEO_AFFINE, _GEO_MULTILINEAR, _GEO_POINT):
-      if counts[k] == 0:
-        continue
-      part = {'geo_mode': k}
-      sel = kind == k
-      if counts[k] < E:
-        part['elem_list'] = torch.nonzero(sel).reshape(-1).to(
-            torch.int32).contiguous()
-      if k == _GEO_POINT:
-        if counts[k] < E:
-          part['geo'] = _ops.helmholtz_setup(
-              fespace.invjacs[sel].contiguous(),
-              fespace.jacdets[sel].contiguous(), w)
-          part['geo_index'] = (torch.cumsum(sel, 0) - 1).to(
-              torch.int32).contiguous()
-        else:
-          part['geo'] = _ops.helmholtz_setup(fespace.invjacs, fespace.jacdets,
-                                             w)
-      else:
-        part['geo_elem'] = coef
-      parts.append(part)
-    geo_parts = parts
-    if coefs is not None:
-      parts = _coefficient_parts(parts, *coefs, E, mesh.num_nodes_per_element,
-                                 mesh.ndim)
-    if beta is not None:
-      parts = _advection_parts(parts, beta, E, mesh.num_nodes_per_element)
     plan = mesh.assembly_plan()
     mask = None
     if dirichlet_mask is not None:
@@ -1000,11 +1045,9 @@ class HelmholtzOperator:
         mesh.gridpoints_1d.num_points in FACET_P and
         switches.get('SFEM_FACET') != '0'):
       facet_parts = _facet_parts(fespace, parts, mask, plan.multiplicity, coef)
-    host = {'dmat': fespace.interpolator._differentiation_matrix_1d(),
-            'weights': np.asarray(fespace.quadrature.weights),
-            'nodes': np.asarray(mesh.gridpoints_1d.node_values)}
-    return cls(fespace=fespace, parts=parts, enc=enc, host=host,
-               zero_range=zero_range, num_affine=counts[_GEO_AFFINE],
+    return cls(fespace=fespace, parts=parts, enc=enc,
+               host=_host_tables(fespace, False), zero_range=zero_range,
+               num_affine=counts[_GEO_AFFINE],
                num_multilinear=counts[_GEO_MULTILINEAR],
                num_curved=counts[_GEO_POINT], facet_parts=facet_parts,
                keep=None if mask is None else (mask == 0).to(fespace.dtype),
@@ -1115,15 +1158,7 @@ class HelmholtzOperator:
     element's points, (E, n[, d]) per-point values, a (d,) velocity the sum
     over elements and points.  None for a coefficient that was absent or a
     callable, and where `want` is false.  `u`, `lam`: nodal (N,)."""
-    mesh = self.fespace.mesh
-    for v in (u, lam):
-      if tuple(v.shape) != (mesh.num_nodes,):
-        raise ValueError(f'expected ({mesh.num_nodes},) nodal values, got '
-                         f'{tuple(v.shape)}')
-    dt = self.fespace.dtype
-    u, lam = u.detach(), lam.detach()
-    return _sensitivity(self, mesh.gather(u.to(dt)), mesh.gather(lam.to(dt)),
-                        mesh.gridpoints_1d.num_points, lambda0, lambda1, want)
+    return _sensitivity(self, u, lam, lambda0, lambda1, want)
 
   def layer_plan(self):
     """The `LayerPlan` of this operator's facet launches (made on first use),
@@ -1216,30 +1251,12 @@ class HelmholtzOperator:
     constants -- the same values up to rounding.  The mass and stiffness
     parts are computed once per operator (`sfem_helmholtz_diag`) and combined
     here."""
-    if self._diag is None:
-      self._diag = _assembled_diagonal(self.fespace, self.parts, self.host,
-                                       self.keep, None)
-    lambda0, lambda1 = _scaled(self.coefs, lambda0, lambda1)
-    d = _combine_diagonal(self._diag, lambda0, lambda1, assembled,
-                          self.fespace.mesh)
-    if self.beta is not None:      # + diag C_b, which no lambda scales
-      if self._diag_adv is None:
-        self._diag_adv = _advection_diagonal(
-            self.fespace, self.parts, self.beta, self.host['dmat'], self.keep,
-            None)
-      d = d + self._diag_adv
-    return d
+    return _diagonal(self, self.keep, None, lambda0, lambda1, assembled)
 
   def point_weights(self):
     """W = w detJ (E, n) at the operator's points, without coefficients (the
     weights of the coarse-level mean in `linalg/pmg.py`)."""
-    mesh = self.fespace.mesh
-    P = mesh.gridpoints_1d.num_points
-    mass, _ = _ops.helmholtz_diag(
-        self._geo_parts or self.parts, mesh.num_elements, mesh.ndim, P,
-        self.host['dmat'], self.host['weights'], self.host['nodes'], None,
-        want_stiff=False, dtype=self.fespace.dtype, device=self.fespace.device)
-    return mass
+    return _point_weights(self)
 
   def apply_local(self, u_local, lambda0=0.0, lambda1=1.0, *,
                   transpose=False):
@@ -1507,38 +1524,8 @@ class StokesDivGrad:
     if geometry not in ('auto', 'multilinear', 'stored'):
       raise ValueError(f'unknown geometry mode {geometry!r}')
     mesh = vspace.mesh
-    E = mesh.num_elements
-    w = torch.as_tensor(vspace.quadrature.weights_nd(mesh.ndim),
-                        dtype=vspace.dtype, device=vspace.device)
-    if geometry == 'stored':
-      kind = torch.zeros(E, dtype=torch.int32, device=vspace.device)
-      coef = None
-    else:
-      kind, coef = classify_geometry(vspace)
-      if geometry == 'multilinear':
-        kind = torch.where(kind == _GEO_AFFINE,
-                           torch.full_like(kind, _GEO_MULTILINEAR), kind)
-    parts = []
-    for k in (_GEO_AFFINE, _GEO_MULTILINEAR, _GEO_POINT):
-      sel = kind == k
-      count = int(sel.sum())
-      if count == 0:
-        continue
-      part = {'geo_mode': k}
-      if count < E:
-        part['elem_list'] = torch.nonzero(sel).reshape(-1).to(
-            torch.int32).contiguous()
-      if k == _GEO_POINT:
-        if count < E:
-          part['kfac'] = _ops.stokes_setup(vspace.invjacs[sel].contiguous(),
-                                           vspace.jacdets[sel].contiguous(), w)
-          part['geo_index'] = (torch.cumsum(sel, 0) - 1).to(
-              torch.int32).contiguous()
-        else:
-          part['kfac'] = _ops.stokes_setup(vspace.invjacs, vspace.jacdets, w)
-      else:
-        part['geo_elem'] = coef
-      parts.append(part)
+    parts, _, _ = _geometry_parts(vspace, 'kfac', _ops.stokes_setup, geometry,
+                                  multilinear=True)
     plan = mesh.assembly_plan()
     mask = None
     if dirichlet_mask is not None:
@@ -1549,10 +1536,8 @@ class StokesDivGrad:
     ident = torch.arange(pel.numel(), device=pel.device,
                          dtype=pel.dtype).reshape(pel.shape)
     penc = None if torch.equal(pel, ident) else pel.to(torch.int32).contiguous()
-    host = {'dmat': vspace.interpolator._differentiation_matrix_1d(),
-            'weights': np.asarray(vspace.quadrature.weights),
-            'nodes': np.asarray(mesh.gridpoints_1d.node_values),
-            'interp': pspace.interpolator._interpolation_matrix_1d()}
+    host = dict(_host_tables(vspace, False),
+                interp=pspace.interpolator._interpolation_matrix_1d())
     facet_parts = None
     if (mesh.ndim == 3 and mesh.gridpoints_1d.num_points in STOKES_FACET_P and
         switches.get('SFEM_FACET') != '0' and
@@ -1912,6 +1897,37 @@ def _combine_diagonal(parts, lambda0, lambda1, assembled, mesh):
   return d
 
 
+def _diagonal(op, keep, interpolator, lambda0, lambda1, assembled):
+  """`diagonal` of both operator classes.  `keep` (N,) zeroes the Dirichlet
+  rows; `interpolator`: that of a two-grid operator, whose (Q, P) matrix
+  enters the element diagonals, None for a collocated one.  The parts that
+  no lambda scales are computed once and kept on `op`."""
+  fes = op.fespace
+  bmat = lambda: None if interpolator is None else np.asarray(
+      interpolator._interpolation_matrix_1d(), dtype=np.float64)
+  if op._diag is None:
+    op._diag = _assembled_diagonal(fes, op.parts, op.host, keep, bmat())
+  lambda0, lambda1 = _scaled(op.coefs, lambda0, lambda1)
+  d = _combine_diagonal(op._diag, lambda0, lambda1, assembled, fes.mesh)
+  if op.beta is not None:      # + diag C_b, which no lambda scales
+    if op._diag_adv is None:
+      op._diag_adv = _advection_diagonal(fes, op.parts, op.beta,
+                                         op.host['dmat'], keep, bmat())
+    d = d + op._diag_adv
+  return d
+
+
+def _point_weights(op):
+  """`point_weights` of both operator classes: the mass diagonal of the
+  launches without coefficients on the grid of `op.host`."""
+  fes, host = op.fespace, op.host
+  mass, _ = _ops.helmholtz_diag(
+      op._geo_parts or op.parts, fes.mesh.num_elements, fes.mesh.ndim,
+      len(host['nodes']), host['dmat'], host['weights'], host['nodes'], None,
+      want_stiff=False, dtype=fes.dtype, device=fes.device)
+  return mass
+
+
 def supports_two_grid(fespace) -> str | None:
   """None if `TwoGridHelmholtzOperator` applies, else the reason."""
   mesh = fespace.mesh
@@ -1980,101 +1996,33 @@ class TwoGridHelmholtzOperator:
     if geometry not in ('auto', 'stored'):
       raise ValueError(f'unknown geometry mode {geometry!r}')
     mesh = fespace.mesh
-    E, dev = mesh.num_elements, fespace.device
-    coefs = None
-    if diffusivity is not None or reaction is not None:
-      _check_coefficient_mesh(mesh, 'atomic')
-      nq = fespace.quadrature.num_points ** mesh.ndim
-      # the values-only interpolation of the element coordinates, not
-      # `quad_coords` (which builds the whole geometry)
-      points = lambda: (mesh.element_coords() if fespace.is_collocated else
-                        fespace._basis(mesh.element_coords(), True,
-                                       False)[0])
-      coefs = (coefficient(diffusivity, 'diffusivity', E, nq, points,
-                           fespace.dtype, dev),
-               coefficient(reaction, 'reaction', E, nq, points,
-                           fespace.dtype, dev))
-    beta = None
+    geo_parts, _, _ = _geometry_parts(fespace, 'geo', _ops.helmholtz_setup,
+                                      geometry, corners=True)
+    # the values-only interpolation of the element coordinates, not
+    # `quad_coords` (which builds the whole geometry)
+    points = lambda: fespace._interpolate(mesh.element_coords())
     velocity_source = velocity
-    if velocity is not None:
-      _check_velocity_mesh(mesh, 'atomic')
-      nq = fespace.quadrature.num_points ** mesh.ndim
-      points = lambda: (mesh.element_coords() if fespace.is_collocated else
-                        fespace._basis(mesh.element_coords(), True,
-                                       False)[0])
-      velocity = velocity_field(velocity, E, nq, mesh.ndim, points,
-                                fespace.dtype, dev)
-      beta = fold_velocity(fespace, velocity)
-    w = torch.as_tensor(fespace.quadrature.weights_nd(mesh.ndim),
-                        dtype=fespace.dtype, device=dev)
-    from swirl_fem_amd.core.interpolation import NodeType
-    corners = mesh.gridpoints_1d.node_type in (
-        NodeType.GAUSS_LOBATTO_LEGENDRE, NodeType.NEWTON_COTES)
-    if geometry == 'stored' or not corners:
-      kind = torch.zeros(E, dtype=torch.int32, device=dev)
-      coef = None
-    else:
-      kind, coef = classify_geometry(fespace)
-    parts = []
-    for k in (_GEO_AFFINE, _GEO_MULTILINEAR, _GEO_POINT):
-      sel = kind == k
-      count = int(sel.sum())
-      if count == 0:
-        continue
-      part = {'geo_mode': k}
-      if count < E:
-        part['elem_list'] = torch.nonzero(sel).reshape(-1).to(
-            torch.int32).contiguous()
-      if k == _GEO_POINT:
-        if count < E:
-          part['geo'] = _ops.helmholtz_setup(
-              fespace.invjacs[sel].contiguous(),
-              fespace.jacdets[sel].contiguous(), w)
-          part['geo_index'] = (torch.cumsum(sel, 0) - 1).to(
-              torch.int32).contiguous()
-        else:
-          part['geo'] = _ops.helmholtz_setup(fespace.invjacs, fespace.jacdets,
-                                             w)
-      else:
-        part['geo_elem'] = coef
-      parts.append(part)
+    coefs, velocity, beta, parts = _coefficient_intake(
+        fespace, 'atomic', fespace.quadrature.num_points ** mesh.ndim, points,
+        geo_parts, diffusivity, reaction, velocity)
     mask = None
     if dirichlet_mask is not None:
-      mask = (torch.as_tensor(dirichlet_mask, device=dev) == 0).to(
+      mask = (torch.as_tensor(dirichlet_mask, device=fespace.device) == 0).to(
           fespace.dtype)
-    host = {'dmat': _quadrature_dmat(fespace),
-            'weights': np.asarray(fespace.quadrature.weights),
-            'nodes': np.asarray(fespace.quadrature.nodes.node_values)}
-    geo_parts = parts
-    if coefs is not None:
-      parts = _coefficient_parts(parts, *coefs, E,
-                                 fespace.quadrature.num_points ** mesh.ndim,
-                                 mesh.ndim)
-    if beta is not None:
-      parts = _advection_parts(parts, beta, E,
-                               fespace.quadrature.num_points ** mesh.ndim)
-    return cls(fespace=fespace, parts=parts, host=host, mask=mask,
-               coefs=coefs, coef_source=(diffusivity, reaction),
+    return cls(fespace=fespace, parts=parts, host=_host_tables(fespace, True),
+               mask=mask, coefs=coefs, coef_source=(diffusivity, reaction),
                _geo_parts=geo_parts, velocity=velocity, beta=beta,
                velocity_source=velocity_source)
 
   def point_weights(self):
     """W = w detJ (E, Q^d) at the quadrature points, without coefficients."""
-    mesh = self.fespace.mesh
-    q = self.fespace.quadrature.num_points
-    mass, _ = _ops.helmholtz_diag(
-        self._geo_parts or self.parts, mesh.num_elements, mesh.ndim, q,
-        self.host['dmat'], self.host['weights'], self.host['nodes'], None,
-        want_stiff=False, dtype=self.fespace.dtype, device=self.fespace.device)
-    return mass
+    return _point_weights(self)
 
   def apply_local(self, u_local, lambda0=0.0, lambda1=1.0, *,
                   transpose=False):
     """(E, n[, nc]) -> (E, n[, nc]).  `transpose`: I^T (A_q)^T I, the
     advective term of the q-grid kernel transposed."""
     fes = self.fespace
-    mesh = fes.mesh
-    E, n = mesh.num_elements, mesh.num_nodes_per_element
     scalar = u_local.dim() == 2
     u3 = (u_local[..., None] if scalar else u_local).to(fes.dtype)
     nc = u3.shape[-1]
@@ -2084,21 +2032,11 @@ class TwoGridHelmholtzOperator:
       lambda0, lambda1 = _scaled(self.coefs, lambda0, lambda1)
     if self.beta is not None and nc != 1:
       raise NotImplementedError('a velocity takes scalar fields')
-    q = fes.quadrature.num_points
-    uq = u3 if fes.is_collocated else fes._basis(u3, True, False)[0]
-    rq = _ops.helmholtz_local(uq.contiguous(), self.parts, self.host,
-                              mesh.ndim, q, lambda0, lambda1,
-                              transpose=transpose and self.beta is not None)
-    if fes.is_collocated:
-      r3 = rq
-    else:
-      i1, g1 = fes._matrices()
-      ones = fes._cache.get('ones_eq')
-      if ones is None:
-        ones = fes._cache['ones_eq'] = torch.ones(
-            (E, q ** mesh.ndim), dtype=fes.dtype, device=fes.device)
-      r3 = _ops.basis_eval_t(rq, None, i1, g1, None, ones, mesh.ndim,
-                             mesh.gridpoints_1d.num_points, q, nc, False)
+    rq = _ops.helmholtz_local(
+        fes._interpolate(u3).contiguous(), self.parts, self.host,
+        fes.mesh.ndim, fes.quadrature.num_points, lambda0, lambda1,
+        transpose=transpose and self.beta is not None)
+    r3 = fes._interpolate_t(rq)
     return r3[..., 0] if scalar else r3
 
   def apply(self, u, lambda0=0.0, lambda1=1.0, *, _transpose=False):
@@ -2127,20 +2065,7 @@ class TwoGridHelmholtzOperator:
                   want=(True, True, True)):
     """`HelmholtzOperator.sensitivity` at the Q^d quadrature points: `u` and
     `lam` (N,) are interpolated there."""
-    fes = self.fespace
-    mesh = fes.mesh
-    for v in (u, lam):
-      if tuple(v.shape) != (mesh.num_nodes,):
-        raise ValueError(f'expected ({mesh.num_nodes},) nodal values, got '
-                         f'{tuple(v.shape)}')
-
-    def at_points(v):
-      vl = mesh.gather(v.detach().to(fes.dtype))
-      if fes.is_collocated:
-        return vl
-      return fes._basis(vl[..., None], True, False)[0][..., 0].contiguous()
-    return _sensitivity(self, at_points(u), at_points(lam),
-                        fes.quadrature.num_points, lambda0, lambda1, want)
+    return _sensitivity(self, u, lam, lambda0, lambda1, want)
 
   def linear_operator(self, lambda0=0.0, lambda1=1.0, transpose=False):
     if transpose:
@@ -2151,65 +2076,18 @@ class TwoGridHelmholtzOperator:
     """The assembled diagonal of `apply(u, lambda0, lambda1)` (N,), see
     `HelmholtzOperator.diagonal`: the element diagonals of I^T H_q I with
     I the (Q, P) interpolation and D_q I its derivative."""
-    interp = self.fespace.interpolator
-    if self._diag is None:
-      bmat = np.asarray(interp._interpolation_matrix_1d(), dtype=np.float64)
-      self._diag = _assembled_diagonal(self.fespace, self.parts, self.host,
-                                       self.mask, bmat)
-    lambda0, lambda1 = _scaled(self.coefs, lambda0, lambda1)
-    d = _combine_diagonal(self._diag, lambda0, lambda1, assembled,
-                          self.fespace.mesh)
-    if self.beta is not None:
-      if self._diag_adv is None:
-        bmat = np.asarray(interp._interpolation_matrix_1d(), dtype=np.float64)
-        self._diag_adv = _advection_diagonal(
-            self.fespace, self.parts, self.beta, self.host['dmat'], self.mask,
-            bmat)
-      d = d + self._diag_adv
-    return d
+    return _diagonal(self, self.mask, self.fespace.interpolator, lambda0,
+                     lambda1, assembled)
 
 
 # ---------------------------------------------------------------------------
 # Over-integrated convection
 # ---------------------------------------------------------------------------
 def _grid_geometry_parts(fespace, point_setup, geometry='auto'):
-  """One launch description per geometry kind for kernels that work on the
-  quadrature grid of `fespace` (`point_setup(invjacs, jacdets, w)` builds the
-  stored per-point data of curved elements)."""
-  from swirl_fem_amd.core.interpolation import NodeType
-  mesh = fespace.mesh
-  E, dev = mesh.num_elements, fespace.device
-  w = torch.as_tensor(fespace.quadrature.weights_nd(mesh.ndim),
-                      dtype=fespace.dtype, device=dev)
-  corners = mesh.gridpoints_1d.node_type in (
-      NodeType.GAUSS_LOBATTO_LEGENDRE, NodeType.NEWTON_COTES)
-  if geometry == 'stored' or not corners:
-    kind = torch.zeros(E, dtype=torch.int32, device=dev)
-    coef = None
-  else:
-    kind, coef = classify_geometry(fespace)
-  parts = []
-  for k in (_GEO_AFFINE, _GEO_MULTILINEAR, _GEO_POINT):
-    sel = kind == k
-    count = int(sel.sum())
-    if count == 0:
-      continue
-    part = {'geo_mode': k}
-    if count < E:
-      part['elem_list'] = torch.nonzero(sel).reshape(-1).to(
-          torch.int32).contiguous()
-    if k == _GEO_POINT:
-      if count < E:
-        part['kfac'] = point_setup(fespace.invjacs[sel].contiguous(),
-                                   fespace.jacdets[sel].contiguous(), w)
-        part['geo_index'] = (torch.cumsum(sel, 0) - 1).to(
-            torch.int32).contiguous()
-      else:
-        part['kfac'] = point_setup(fespace.invjacs, fespace.jacdets, w)
-    else:
-      part['geo_elem'] = coef
-    parts.append(part)
-  return parts
+  """The launches (`_geometry_parts`) of the cofactor kernels that work on the
+  quadrature grid of `fespace`."""
+  return _geometry_parts(fespace, 'kfac', point_setup, geometry,
+                         corners=True)[0]
 
 
 @dataclasses.dataclass(eq=False)
@@ -2233,30 +2111,15 @@ class ConvectionOperator:
     if why is not None:
       raise NotImplementedError(f'fused convection unavailable: {why}')
     parts = _grid_geometry_parts(fespace, _ops.stokes_setup, geometry)
-    host = {'dmat': _quadrature_dmat(fespace),
-            'weights': np.asarray(fespace.quadrature.weights),
-            'nodes': np.asarray(fespace.quadrature.nodes.node_values)}
-    return cls(fespace=fespace, parts=parts, host=host)
+    return cls(fespace=fespace, parts=parts, host=_host_tables(fespace, True))
 
   def apply_local(self, u_local):
     """(E, n, d) nodal velocity -> (E, n, d) local convection covector."""
     fes = self.fespace
-    mesh = fes.mesh
-    q = fes.quadrature.num_points
-    u3 = u_local.to(fes.dtype)
-    uq = u3 if fes.is_collocated else fes._basis(u3, True, False)[0]
-    cq = _ops.stokes_convect_local(uq, self.parts, self.host, mesh.ndim, q)
-    if fes.is_collocated:
-      return cq
-    i1, g1 = fes._matrices()
-    ones = fes._cache.get('ones_eq')
-    if ones is None:
-      ones = fes._cache['ones_eq'] = torch.ones(
-          (mesh.num_elements, q ** mesh.ndim), dtype=fes.dtype,
-          device=fes.device)
-    return _ops.basis_eval_t(cq, None, i1, g1, None, ones, mesh.ndim,
-                             mesh.gridpoints_1d.num_points, q, mesh.ndim,
-                             False)
+    uq = fes._interpolate(u_local.to(fes.dtype))
+    cq = _ops.stokes_convect_local(uq, self.parts, self.host, fes.mesh.ndim,
+                                   fes.quadrature.num_points)
+    return fes._interpolate_t(cq)
 
 
 # ---------------------------------------------------------------------------
@@ -2283,10 +2146,7 @@ class TransportRhs:
     if why is not None:
       raise NotImplementedError(f'fused transport unavailable: {why}')
     parts = _grid_geometry_parts(fespace, _ops.stokes_setup, geometry)
-    host = {'dmat': _quadrature_dmat(fespace),
-            'weights': np.asarray(fespace.quadrature.weights),
-            'nodes': np.asarray(fespace.quadrature.nodes.node_values)}
-    return cls(fespace=fespace, parts=parts, host=host)
+    return cls(fespace=fespace, parts=parts, host=_host_tables(fespace, True))
 
   def point_weights(self):
     """W = w detJ (E, Q^d), what `TwoGridHelmholtzOperator.point_weights`
@@ -2340,11 +2200,9 @@ class TransportRhs:
     # routes that carry their transposes; `_basis` and `scatter` switch alone
     grad = autodiff.needs_grad(source, *[t for l in levels for t in l[:2]])
     gather_rows = autodiff.gather_rows if grad else _ops.gather_rows
-    basis_eval_t = autodiff.basis_eval_t if grad else _ops.basis_eval_t
 
     def at_points(nodal):      # (N, nc) -> (E, Q^d, nc)
-      loc = gather_rows(nodal.contiguous(), mesh.elements)
-      return loc if fes.is_collocated else fes._basis(loc, True, False)[0]
+      return fes._interpolate(gather_rows(nodal.contiguous(), mesh.elements))
     local = []
     for T, u, mc, cc in levels:
       T = torch.as_tensor(T, dtype=fes.dtype, device=fes.device)
@@ -2370,14 +2228,4 @@ class TransportRhs:
         raise ValueError(f'source: shape {tuple(s.shape)}; expected '
                          f'({mesh.num_nodes},) or ({mesh.num_elements}, {nq})')
     rq = self.apply_local(local, sq)
-    if fes.is_collocated:
-      return mesh.scatter(rq)
-    i1, g1 = fes._matrices()
-    ones = fes._cache.get('ones_eq')
-    if ones is None:
-      ones = fes._cache['ones_eq'] = torch.ones(
-          (mesh.num_elements, nq), dtype=fes.dtype, device=fes.device)
-    r3 = basis_eval_t(rq[..., None], None, i1, g1, None, ones, d,
-                      mesh.gridpoints_1d.num_points,
-                      fes.quadrature.num_points, 1, False)
-    return mesh.scatter(r3[..., 0])
+    return mesh.scatter(fes._interpolate_t(rq[..., None], grad)[..., 0])

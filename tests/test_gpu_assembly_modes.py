@@ -219,3 +219,83 @@ def test_assembly_path_matches_oracle(cid, build, args, path, geometry, dtype,
         if path in ('colored', 'layered'):
           again = _apply(op, ud, l0, l1, path, rng, None)
           assert torch.equal(got, again), what
+
+
+# ---------------------------------------------------------------------------
+# One launch list per geometry kind, the same for every operator of a mesh
+# ---------------------------------------------------------------------------
+# name -> key of the per-point data of its curved launches
+LAUNCH_DATA = {'helmholtz': 'geo', 'two_grid': 'geo', 'stokes': 'kfac',
+               'convection': 'kfac', 'transport': 'kfac'}
+
+
+def _launch_lists(mesh_kind, ndim, geometry):
+  """({operator: parts}, E) of the five operators that launch once per
+  geometry kind, on one mesh: the collocated Helmholtz operator with atomic
+  assembly, and the two-grid Helmholtz, convection and transport operators on
+  4 Gauss points per direction.  'three_kinds_padded' is the padded mixed mesh
+  at 3 points per direction; the Stokes pair needs P >= 4 and a pressure mesh
+  that holds the same geometry, so it joins on 'stokes_pair', the velocity mesh
+  of the smallest curved P_N - P_{N-2} pair (`numbering_cases`)."""
+  from swirl_fem_amd.core.interpolation import NodeType
+  from tests import numbering_cases as NC
+  pair = None
+  if mesh_kind == 'three_kinds_padded':
+    mesh, _, _ = G.three_kinds(2, ndim, 3, pad=1).finalize(DEV, F64)
+  else:
+    pair = NC.stokes_spaces(
+        NC.build_pair('refiner', 'identity', 'three_kinds', 3, 5, ndim), DEV,
+        F64)
+    mesh = pair[0].mesh
+  fes = FiniteElementSpace.create(
+      mesh, Quadrature1D.create_from_nodes_1d(mesh.gridpoints_1d))
+  grid = FiniteElementSpace.create(
+      mesh, Quadrature1D.create(4, NodeType.GAUSS_LEGENDRE))
+  ops = {
+      'helmholtz': operators.HelmholtzOperator.create(fes, None, geometry,
+                                                      'atomic'),
+      'two_grid': operators.TwoGridHelmholtzOperator.create(grid, None,
+                                                            geometry),
+      'convection': operators.ConvectionOperator.create(grid, geometry),
+      'transport': operators.TransportRhs.create(grid, geometry)}
+  if pair is None:
+    assert operators.supports_fused_stokes(fes, fes) == 'P=3 < 4'
+  else:
+    ops['stokes'] = operators.StokesDivGrad.create(*pair, None, geometry)
+  return {name: op.parts for name, op in ops.items()}, mesh.num_elements
+
+
+@pytest.mark.parametrize('ndim', [2, 3])
+@pytest.mark.parametrize('mesh_kind', ['three_kinds_padded', 'stokes_pair'])
+def test_operators_share_one_launch_list(mesh_kind, ndim):
+  POINT = operators._GEO_POINT
+  lists, E = _launch_lists(mesh_kind, ndim, 'auto')
+  ref = lists['helmholtz']
+  modes = [q['geo_mode'] for q in ref]
+  assert len(modes) >= 2 and len(set(modes)) == len(modes), modes
+  # the kinds split the elements; curved rows are numbered in element order
+  every = torch.cat([q['elem_list'] for q in ref]).sort().values
+  assert torch.equal(every, torch.arange(E, dtype=torch.int32, device=DEV))
+  for q in ref:
+    if q['geo_mode'] == POINT:
+      rows = q['geo_index'][q['elem_list'].long()]
+      assert torch.equal(rows, torch.arange(
+          rows.numel(), dtype=torch.int32, device=DEV))
+  for name, parts in lists.items():
+    assert [q['geo_mode'] for q in parts] == modes, name
+    for q, r in zip(parts, ref):
+      curved = q['geo_mode'] == POINT
+      assert 'elem_list' in q and ('geo_index' in q) == curved, name
+      assert ('geo_elem' in q) == (not curved), name
+      assert (LAUNCH_DATA[name] in q) == curved, name
+      for key in ('elem_list', 'geo_index', 'geo_elem'):
+        assert (key in q) == (key in r), (name, key)
+        if key in q:
+          assert torch.equal(q[key], r[key]), (name, key)
+      if curved:
+        assert q[LAUNCH_DATA[name]].shape[0] == q['elem_list'].numel(), name
+  lists, E = _launch_lists(mesh_kind, ndim, 'stored')
+  for name, parts in lists.items():
+    assert [q['geo_mode'] for q in parts] == [POINT], name
+    assert not {'elem_list', 'geo_index', 'geo_elem'} & set(parts[0]), name
+    assert parts[0][LAUNCH_DATA[name]].shape[0] == E, name
