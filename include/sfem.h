@@ -639,6 +639,109 @@ typedef struct sfem_transport_vjp_args {
 int sfem_transport_rhs_vjp(const sfem_transport_vjp_args* args,
                            sfem_stream_t stream);
 
+/* ------------------------------------- fields at points: locate, eval, eval^T ---
+ * A field of order P1 - 1 on element e is u(xi) = sum_n u[elements[e, n]]
+ * l_n(xi) with l_n the tensor product of the 1D Lagrange polynomials on
+ * `nodes` (HOST, P1 doubles; `bary` = 1 / prod_{k != i} (nodes[i] - nodes[k]),
+ * HOST, P1 doubles), n lexicographic with axis 0 slowest.  The basis is formed
+ * in the product form l_i(x) = bary[i] prod_{k != i} (x - nodes[k]), which is
+ * finite at the nodes.
+ *
+ * sfem_point_locate finds, for each of `num_points` points (mesh dtype,
+ * (M, ndim)), an element and reference coordinates with x(xi) = point, where
+ * x(xi) is the same expansion of `node_coords`.  Candidates come from a
+ * uniform grid of ncell[0] x .. x ncell[ndim-1] cells over [grid_lo, grid_hi]
+ * (cell of x along axis a: floor((x_a - grid_lo[a]) * inv_cell[a]), clamped;
+ * cell index lexicographic with axis 0 slowest) as a CSR list `cell_offsets`
+ * / `cell_elems` of element ids, ascending per cell.  A point outside
+ * [grid_lo, grid_hi] is not found.  One lane per point walks its cell's
+ * candidates: reject by `boxes` (E, 2, ndim doubles: lower corner, upper
+ * corner), then at most `max_iter` Newton steps from xi = 0 in double
+ * arithmetic (Cramer's rule, xi clamped to [-1.5, 1.5] after each step) and,
+ * when that pass ends outside the reference cube, once more at most
+ * `max_iter` steps from the nearest point of the cube (the continued map of a
+ * curved element can fold back onto a point on a face), then accept when max |xi| <= 1 + tol_xi and max_a |x(xi) - point|_a <= tol_x *
+ * extent[e] (E doubles).  The first accepted candidate (the lowest element id)
+ * wins.  Outputs: `element` (M,) int32 (-1 when not found), `xi` (M, ndim) in
+ * the mesh dtype (0 when not found), `found` (M,) uint8.  No atomics, no
+ * barriers, every loop bounded by an argument.  Every entry of cell_elems
+ * must be a row of `elements` without -1 in [0, num_elements), every node id
+ * in [0, num_nodes); a node id outside that range reads coordinate 0.
+ * ndim outside 2..3 and P1 outside 2..12 return SFEM_EUNSUPPORTED; null
+ * pointers, max_iter outside 0..64, a negative tolerance or size, a
+ * non-positive ncell or a CSR too long for int32 element ids are SFEM_EINVAL.
+ * ABI version 10 (a pure addition).                                          */
+typedef struct sfem_point_locate_args {
+  const void* points;          /* (M, ndim)                                   */
+  const void* node_coords;     /* (N, ndim)                                   */
+  const int32_t* elements;     /* (E, P1^ndim)                                */
+  const int64_t* cell_offsets; /* (cells + 1,)                                */
+  const int32_t* cell_elems;   /* (cell_offsets[cells],)                      */
+  const double* boxes;         /* (E, 2, ndim)                                */
+  const double* extent;        /* (E,)                                        */
+  const double* nodes;         /* HOST (P1,)                                  */
+  const double* bary;          /* HOST (P1,)                                  */
+  int32_t* element;            /* out (M,)                                    */
+  void* xi;                    /* out (M, ndim)                               */
+  uint8_t* found;              /* out (M,)                                    */
+  double grid_lo[3];
+  double grid_hi[3];
+  double inv_cell[3];
+  double tol_xi, tol_x;
+  int64_t num_points, num_nodes, num_elements;
+  int32_t ncell[3];
+  int32_t max_iter, ndim, P1, dtype;
+} sfem_point_locate_args;
+int sfem_point_locate(const sfem_point_locate_args* args, sfem_stream_t stream);
+
+/* Evaluation at located points and its transpose, from a plan: the found
+ * points sorted stably by element (`perm[p]` = index of sorted point p among
+ * the M points, `xi` (F, ndim) in sorted order), cut into segments of one
+ * element each (`seg_elem` (S,), ascending; `seg_offsets` (S + 1,) into the
+ * sorted order) and, for the evaluation, into chunks of at most 64 points of
+ * one element (`chunk_elem`, `chunk_start`, `chunk_count` (K,)).
+ *
+ * sfem_point_eval:    values[perm[p], c] = sum_n u[elements[e_p, n], c]
+ *                                          l_n(xi_p)
+ *   One wave per chunk: the element's nodal values of one component go to
+ *   LDS through the index row (a -1 slot reads 0), each lane contracts its
+ *   point sum-factorised.  `field` is addressed as field[k * node_stride +
+ *   c * comp_stride] (sfem_exchange_classes); `values` is (M, ncomp)
+ *   row-major, rows of points outside the plan are not written.
+ * sfem_point_eval_t:  rows[s, n, c] = sum_{p in segment s} values[perm[p], c]
+ *                                     l_n(xi_p)
+ *   One workgroup per segment, its lanes own nodes and add the points in
+ *   sorted order: no atomics, bitwise reproducible.  `rows` is (S, P1^ndim,
+ *   ncomp); sfem_scatter_csr assembles it.  `field`, the strides and the
+ *   chunk arrays are not read.
+ * Every element id of the plan must be in [0, num_elements), every perm
+ * entry in [0, num_points): the caller validates them on the host.
+ * ndim outside 2..3 and P1 outside 2..12 return SFEM_EUNSUPPORTED; null
+ * pointers, negative sizes, ncomp < 1 and more than 2^31 - 1 chunks or
+ * segments are SFEM_EINVAL.  ABI version 10 (a pure addition).               */
+#define SFEM_POINT_CHUNK 64
+typedef struct sfem_point_args {
+  const void* field;           /* eval: nodal field (strided)                 */
+  void* values;                /* (M, ncomp): eval out, eval_t in             */
+  void* rows;                  /* eval_t out (S, P1^ndim, ncomp)              */
+  const int32_t* elements;     /* (E, P1^ndim)                                */
+  const void* xi;              /* (F, ndim), sorted order                     */
+  const int64_t* perm;         /* (F,)                                        */
+  const int32_t* chunk_elem;   /* (K,)                                        */
+  const int64_t* chunk_start;  /* (K,)                                        */
+  const int32_t* chunk_count;  /* (K,) 1..SFEM_POINT_CHUNK                    */
+  const int32_t* seg_elem;     /* (S,)                                        */
+  const int64_t* seg_offsets;  /* (S + 1,)                                    */
+  const double* nodes;         /* HOST (P1,)                                  */
+  const double* bary;          /* HOST (P1,)                                  */
+  int64_t num_points, num_found, num_chunks, num_segments;
+  int64_t num_elements, num_nodes;
+  int64_t node_stride, comp_stride;
+  int32_t ncomp, ndim, P1, dtype;
+} sfem_point_args;
+int sfem_point_eval(const sfem_point_args* args, sfem_stream_t stream);
+int sfem_point_eval_t(const sfem_point_args* args, sfem_stream_t stream);
+
 /* ------------------------------------------------------------ CG kernels ---
  * Preconditioned CG of linalg/cg.py:30-97 with device-resident scalars: no
  * host synchronisation inside an iteration (the reference keeps its loop on

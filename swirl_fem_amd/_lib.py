@@ -143,6 +143,39 @@ class TransportVjpArgs(ctypes.Structure):
   ]
 
 
+SFEM_POINT_CHUNK = 64
+
+
+class PointLocateArgs(ctypes.Structure):
+  """Mirror of `struct sfem_point_locate_args`."""
+  _fields_ = [
+      ('points', c_ptr), ('node_coords', c_ptr), ('elements', c_ptr),
+      ('cell_offsets', c_ptr), ('cell_elems', c_ptr), ('boxes', c_ptr),
+      ('extent', c_ptr), ('nodes', c_ptr), ('bary', c_ptr),
+      ('element', c_ptr), ('xi', c_ptr), ('found', c_ptr),
+      ('grid_lo', c_dbl * 3), ('grid_hi', c_dbl * 3), ('inv_cell', c_dbl * 3),
+      ('tol_xi', c_dbl), ('tol_x', c_dbl),
+      ('num_points', c_i64), ('num_nodes', c_i64), ('num_elements', c_i64),
+      ('ncell', c_i32 * 3),
+      ('max_iter', c_i32), ('ndim', c_i32), ('P1', c_i32), ('dtype', c_i32),
+  ]
+
+
+class PointArgs(ctypes.Structure):
+  """Mirror of `struct sfem_point_args`."""
+  _fields_ = [
+      ('field', c_ptr), ('values', c_ptr), ('rows', c_ptr),
+      ('elements', c_ptr), ('xi', c_ptr), ('perm', c_ptr),
+      ('chunk_elem', c_ptr), ('chunk_start', c_ptr), ('chunk_count', c_ptr),
+      ('seg_elem', c_ptr), ('seg_offsets', c_ptr), ('nodes', c_ptr),
+      ('bary', c_ptr),
+      ('num_points', c_i64), ('num_found', c_i64), ('num_chunks', c_i64),
+      ('num_segments', c_i64), ('num_elements', c_i64), ('num_nodes', c_i64),
+      ('node_stride', c_i64), ('comp_stride', c_i64),
+      ('ncomp', c_i32), ('ndim', c_i32), ('P1', c_i32), ('dtype', c_i32),
+  ]
+
+
 class DiagArgs(ctypes.Structure):
   """Mirror of `struct sfem_diag_args`."""
   _fields_ = [
@@ -268,6 +301,9 @@ SIGNATURES = {
     'sfem_stokes_convect_local': [c_ptr, c_ptr],
     'sfem_transport_rhs': [ctypes.POINTER(TransportArgs), c_ptr],
     'sfem_transport_rhs_vjp': [ctypes.POINTER(TransportVjpArgs), c_ptr],
+    'sfem_point_locate': [ctypes.POINTER(PointLocateArgs), c_ptr],
+    'sfem_point_eval': [ctypes.POINTER(PointArgs), c_ptr],
+    'sfem_point_eval_t': [ctypes.POINTER(PointArgs), c_ptr],
     'sfem_pmg_prolong': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64,
                          c_i32, c_i32, c_i32, c_i32, c_i32, c_ptr],
     'sfem_pmg_restrict': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64,

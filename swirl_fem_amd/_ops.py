@@ -1321,6 +1321,100 @@ def transport_rhs_vjp(cotangent, levels, parts, host, ndim, P, wdet, want):
   return out, dsource
 
 
+# ------------------------------------------------------------ fields at points
+def point_locate(points, node_coords, elements, grid, nodes, bary, max_iter,
+                 tol_xi, tol_x):
+  """`sfem_point_locate`: (element (M,) int32, xi (M, d), found (M,) bool) of
+  `points` (M, d) in the mesh (`node_coords`, `elements`).  `grid` holds the
+  candidate lists of `core.points.CandidateGrid` on the device; `nodes` and
+  `bary` are the host tables of the 1D basis."""
+  points = points.contiguous()
+  dev = _dev(points, node_coords, elements, grid.cell_offsets, grid.cell_elems,
+             grid.boxes, grid.extent)
+  M, ndim = points.shape
+  element = torch.empty(M, dtype=torch.int32, device=dev)
+  xi = torch.empty((M, ndim), dtype=points.dtype, device=dev)
+  found = torch.empty(M, dtype=torch.uint8, device=dev)
+  nodes = np.ascontiguousarray(nodes, dtype=np.float64)
+  bary = np.ascontiguousarray(bary, dtype=np.float64)
+  args = _lib.PointLocateArgs(
+      points=_dptr(points), node_coords=_dptr(node_coords),
+      elements=_dptr(elements), cell_offsets=_dptr(grid.cell_offsets),
+      cell_elems=_dptr(grid.cell_elems), boxes=_dptr(grid.boxes),
+      extent=_dptr(grid.extent), nodes=_hptr(nodes), bary=_hptr(bary),
+      element=_dptr(element), xi=_dptr(xi), found=_dptr(found),
+      tol_xi=float(tol_xi), tol_x=float(tol_x), num_points=M,
+      num_nodes=node_coords.shape[0], num_elements=elements.shape[0],
+      max_iter=int(max_iter), ndim=ndim, P1=len(nodes),
+      dtype=_dtype_code(points))
+  for a in range(ndim):
+    args.grid_lo[a], args.grid_hi[a] = float(grid.lo[a]), float(grid.hi[a])
+    args.inv_cell[a], args.ncell[a] = float(grid.inv_cell[a]), int(grid.ncell[a])
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_point_locate(ctypes.byref(args), _stream(dev)),
+               'sfem_point_locate')
+  return element, xi, found.bool()
+
+
+def _point_args(plan, values, ncomp):
+  return _lib.PointArgs(
+      values=_dptr(values), elements=_dptr(plan.elements), xi=_dptr(plan.xi),
+      perm=_dptr(plan.perm), chunk_elem=_dptr(plan.chunk_elem),
+      chunk_start=_dptr(plan.chunk_start), chunk_count=_dptr(plan.chunk_count),
+      seg_elem=_dptr(plan.seg_elem), seg_offsets=_dptr(plan.seg_offsets),
+      nodes=_hptr(plan.nodes), bary=_hptr(plan.bary),
+      num_points=plan.num_points, num_found=plan.num_found,
+      num_chunks=plan.chunk_elem.numel(), num_segments=plan.seg_elem.numel(),
+      num_elements=plan.elements.shape[0], num_nodes=plan.num_nodes,
+      ncomp=ncomp, ndim=plan.ndim, P1=len(plan.nodes),
+      dtype=_dtype_code(values))
+
+
+def point_eval(u, plan, fill):
+  """`sfem_point_eval`: a nodal field (N,), row-major (N, C) or
+  component-major (N, C) at the points of `plan` (`core.points.PointPlan`):
+  (M,) or (M, C), `fill` where a point was not found."""
+  ncomp, ns, cs = _node_view(u)
+  dev = _dev(u.movedim(-1, 0) if is_component_major(u) else u, plan.elements,
+             plan.xi, plan.perm, plan.chunk_elem)
+  if u.dtype != plan.xi.dtype:
+    raise ValueError(f'field dtype {u.dtype} differs from the mesh dtype '
+                     f'{plan.xi.dtype}')
+  shape = (plan.num_points,) if u.dim() == 1 else (plan.num_points, ncomp)
+  out = torch.full(shape, fill, dtype=u.dtype, device=dev)
+  args = _point_args(plan, out, ncomp)
+  args.field, args.node_stride, args.comp_stride = _dptr(u), ns, cs
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_point_eval(ctypes.byref(args), _stream(dev)),
+               'sfem_point_eval')
+  return out
+
+
+def point_eval_t(w, plan):
+  """`sfem_point_eval_t` and the deterministic assembly of its element-local
+  rows: point weights (M,) or (M, C) to nodal (N,) or (N, C)."""
+  w = w.contiguous()
+  dev = _dev(w, plan.elements, plan.xi, plan.perm, plan.seg_elem,
+             plan.seg_offsets)
+  if w.dtype != plan.xi.dtype:
+    raise ValueError(f'weight dtype {w.dtype} differs from the mesh dtype '
+                     f'{plan.xi.dtype}')
+  ncomp = 1 if w.dim() == 1 else w.shape[1]
+  S = plan.seg_elem.numel()
+  n = plan.elements.shape[1]
+  shape = (plan.num_nodes,) if w.dim() == 1 else (plan.num_nodes, ncomp)
+  if S == 0:
+    return torch.zeros(shape, dtype=w.dtype, device=dev)
+  rows = torch.empty((S, n, ncomp), dtype=w.dtype, device=dev)
+  args = _point_args(plan, w, ncomp)
+  args.rows = _dptr(rows)
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_point_eval_t(ctypes.byref(args), _stream(dev)),
+               'sfem_point_eval_t')
+  offsets, slots = plan.scatter_csr
+  return scatter_csr(rows, offsets, slots, plan.num_nodes, ncomp).reshape(shape)
+
+
 from swirl_fem_amd.core.layout import is_component_major  # noqa: E402
 
 

@@ -199,6 +199,13 @@ class Mesh:
         unique_indices=self.exchange_unique_indices,
         axis_name=self.axis_name, plan=self.neighbor_plan)
 
+  def point_evaluator(self, points: torch.Tensor, **locate_kwargs):
+    """A `core.points.PointEvaluator` for `points` (M, d): located once, then
+    `ev(u)` samples nodal fields there and `ev.transpose(w)` spreads point
+    weights to the nodes."""
+    from swirl_fem_amd.core.points import PointEvaluator
+    return PointEvaluator.create(self, points, **locate_kwargs)
+
   # ------------------------------------------------------- kernel-side plans
   def assembly_plan(self):
     """Slot classification + CSR inverse map used by the fused operators."""

@@ -96,6 +96,24 @@ def _detached(v):
   return v.detach() if isinstance(v, torch.Tensor) else v
 
 
+def _point_covector(mesh, point_sources, dtype, device):
+  """`sum_m s_m phi_i(x_m)` as an `(N,)` vector, periodic images summed."""
+  from swirl_fem_amd.core.points import PointEvaluator
+  if not (isinstance(point_sources, (tuple, list)) and
+          len(point_sources) == 2):
+    raise ValueError('point_sources is a pair (points, strengths)')
+  points, strengths = point_sources
+  points = torch.as_tensor(points, dtype=dtype, device=device)
+  strengths = torch.as_tensor(strengths, dtype=dtype, device=device)
+  if strengths.dim() != 1 or points.dim() != 2 or (
+      points.shape[0] != strengths.shape[0]):
+    raise ValueError('point_sources: expected points (M, d) and strengths '
+                     f'(M,), got {tuple(points.shape)} and '
+                     f'{tuple(strengths.shape)}')
+  ev = PointEvaluator.create(mesh, points)
+  return mesh.exchange(ev.transpose(strengths.detach()))
+
+
 class _HelmholtzSolve(torch.autograd.Function):
   """`_solve` as one autograd node: the adjoint solve and the coefficient
   sensitivities in `backward`."""
@@ -155,9 +173,18 @@ def solve_helmholtz(mesh: Mesh, forcing,
                     *, lambda0: float = 0.0, lambda1: float = 1.0,
                     rtol: float = 1e-5, atol: float = 0.,
                     return_info: bool = False, preconditioner=None,
-                    diffusivity=None, reaction=None, velocity=None):
+                    diffusivity=None, reaction=None, velocity=None,
+                    point_sources=None):
   """Solves `lambda0 c u + b . grad u - lambda1 div(k grad u) = forcing` with
   boundary data.
+
+  `point_sources`: None, or `(points (M, d), strengths (M,))`: the Dirac loads
+  `sum_m strengths[m] delta(x - points[m])` added to the forcing.  The points
+  are located once (`core.points.PointEvaluator`) and the covector
+  `ev.transpose(strengths)` joins the right-hand side with the Neumann
+  covectors (before lift and mask, summed over periodic images); a point
+  outside the mesh contributes nothing.  `strengths` that require grad raise
+  NotImplementedError.
 
   `velocity` b: None (no advective term: the symmetric solve by CG), a `(d,)`
   constant, an `(E, d)` tensor, an `(E, Q^d, d)` tensor at the quadrature
@@ -202,6 +229,11 @@ def solve_helmholtz(mesh: Mesh, forcing,
   """
   kwargs = dict(lambda0=lambda0, lambda1=lambda1, rtol=rtol, atol=atol,
                 preconditioner=preconditioner)
+  if point_sources is not None:
+    if _requires_grad(point_sources[1]):
+      raise NotImplementedError('gradients of solve_helmholtz with respect to '
+                                'point source strengths')
+    kwargs['point_sources'] = point_sources
   if not _requires_grad(forcing, diffusivity, reaction, velocity):
     return _solve(mesh, forcing, boundary_conditions, diffusivity=diffusivity,
                   reaction=reaction, velocity=velocity,
@@ -221,7 +253,8 @@ def _solve(mesh: Mesh, forcing,
            *, lambda0: float = 0.0, lambda1: float = 1.0,
            rtol: float = 1e-5, atol: float = 0.,
            return_info: bool = False, preconditioner=None,
-           diffusivity=None, reaction=None, velocity=None, _state=None):
+           diffusivity=None, reaction=None, velocity=None, _state=None,
+           point_sources=None):
   """The body of `solve_helmholtz`.  `_state`: a dict that receives what the
   adjoint solve needs (the operators, the mask, the preconditioner)."""
   if preconditioner not in (None, 'jacobi', 'pmg'):
@@ -403,6 +436,8 @@ def _solve(mesh: Mesh, forcing,
     rhs = rhs + lambda1 * fespace.boundary_covector(group, value)
   for group, _, g in robin:
     rhs = rhs + lambda1 * fespace.boundary_covector(group, g)
+  if point_sources is not None:
+    rhs = rhs + _point_covector(mesh, point_sources, dtype, device)
   b = rhs * keep
 
   A = K

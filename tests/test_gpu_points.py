@@ -1,0 +1,430 @@
+"""Fields at arbitrary points on the GPU: `sfem_point_locate`,
+`sfem_point_eval` and `sfem_point_eval_t` each alone against the NumPy
+reference (`tests/point_reference.py`), autograd, the end-to-end evaluator,
+point sources in `solve_helmholtz`, an inverse-problem gradient and the
+refusals."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from swirl_fem_amd.common.premesh_commons import unit_cube_mesh
+from swirl_fem_amd.core import layout
+from swirl_fem_amd.core import points as PT
+from swirl_fem_amd.core.interpolation import Nodes1D, NodeType
+from swirl_fem_amd.core.mesh_refiner import refine_premesh
+from swirl_fem_amd.examples.helmholtz import BCType, solve_helmholtz
+from tests import adjoint_reference as AJ
+from tests import geometry_cases as G
+from tests import point_reference as PR
+from tests import transport_reference as TR
+from tests.fp32util import F32Rng, f32r, tolerance
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+F64, F32 = torch.float64, torch.float32
+DTYPES = [F64, F32]
+
+
+def _dev(a, dtype=F64):
+  return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device=DEV)
+
+
+def _np(t):
+  return t.detach().double().cpu().numpy()
+
+
+def _rel(a, b):
+  return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
+
+
+def _case(name, ndim, P1):
+  if name == 'three_kinds':
+    return G.three_kinds(3, ndim, P1, pad=2)
+  return getattr(G, name)(3, ndim, P1)
+
+
+@functools.lru_cache(maxsize=4)
+def _mesh(name, ndim, P1, dtype):
+  """(mesh, node coordinates the mesh holds, element rows, 1D nodes)."""
+  mesh, _, rp = _case(name, ndim, P1).finalize(DEV, dtype)
+  return (mesh, np.asarray(rp.node_coords, np.float64),
+          mesh.elements.cpu().numpy(), rp.gridpoints_1d.node_values)
+
+
+# ------------------------------------------------------------------ 1. locate
+@pytest.mark.parametrize('dtype', DTYPES, ids=['f64', 'f32'])
+@pytest.mark.parametrize('name', ['three_kinds', 'curved_multilinear',
+                                  'periodic'])
+@pytest.mark.parametrize('P1', [2, 5, 8, 12])
+@pytest.mark.parametrize('ndim', [2, 3])
+def test_locate(ndim, P1, name, dtype):
+  """1000 inside points (a fifth on faces, edges and vertices) and 50 points
+  at least 0.05 outside the bounding box: every inside point is found, no
+  outside point is, max |xi| <= 1 + tol_xi, the reference's map at the
+  returned (element, xi) is within tolerance(dtype, P1) x extent of the
+  point, and a point with max |xi0| <= 0.9 gets exactly e0."""
+  mesh, X, el, nodes = _mesh(name, ndim, P1, dtype)
+  rng = np.random.default_rng([ndim, P1, len(name)])
+  e0, xi0, x = PR.make_points(rng, X, el, nodes, 1000)
+  out = PR.outside_points(rng, X, 50)
+  pts = np.concatenate([x, out])
+  if dtype == F32:
+    pts = f32r(pts)
+  loc = PT.locate_points(mesh, _dev(pts, dtype))
+  element = loc.element.cpu().numpy().astype(np.int64)
+  xi, found = _np(loc.xi), loc.found.cpu().numpy()
+  assert loc.element.dtype == torch.int32 and loc.xi.dtype == dtype
+  assert loc.found.dtype == torch.bool
+  missed = 1.0 - found[:1000].mean()
+  tol_xi = 1e-10 if dtype == F64 else 1e-5
+  back, _ = PR.nodal_map(X, el, nodes, np.maximum(element[:1000], 0),
+                         xi[:1000])
+  ext = PR.extents(X, el)[np.maximum(element[:1000], 0)]
+  res = (np.abs(back - pts[:1000]).max(axis=1) / ext)[found[:1000]]
+  inner = np.abs(xi0).max(axis=1) <= 0.9
+  print(f'{name} d={ndim} P1={P1} {dtype}: missed {missed:.4f}, outside found '
+        f'{found[1000:].sum()}, max|xi| - 1 = {np.abs(xi).max() - 1:.2e}, '
+        f'residual / extent {res.max():.2e}, wrong element '
+        f'{(element[:1000][inner] != e0[inner]).sum()} of {inner.sum()}')
+  assert missed == 0.0
+  assert not found[1000:].any()
+  assert (element[~found] == -1).all() and (xi[~found] == 0).all()
+  assert (element[found] >= 0).all()
+  assert np.abs(xi).max() <= 1 + tol_xi
+  assert res.max() <= tolerance(dtype, P1)
+  assert (element[:1000][inner] == e0[inner]).all()
+
+
+# -------------------------------------------------- 2. eval and its transpose
+@functools.lru_cache(maxsize=2)
+def _located(ndim, P1, dtype):
+  """A fixed location on three_kinds(3, d, P1, pad=2), not made by the
+  locator: one real element without points, one with 1, one with 70 (more
+  than a chunk), the others about 5 each, three points not found; xi from
+  F32Rng, unsorted, some components exactly +-1 or exactly an interior
+  node."""
+  mesh, X, el, nodes = _mesh('three_kinds', ndim, P1, dtype)
+  rng = F32Rng(100 * ndim + P1)
+  real = np.flatnonzero((el >= 0).all(axis=1))
+  none, one, many = real[1], real[2], real[4]
+  rest = np.array([e for e in real if e not in (none, one, many)])
+  element = np.concatenate([[one], np.full(70, many),
+                            rest[rng.integers(0, len(rest), 5 * len(rest))],
+                            [-1, -1, -1]])
+  element = element[rng.permutation(len(element))]
+  M = len(element)
+  xi = rng.uniform(-1.0, 1.0, (M, ndim))
+  node = f32r(nodes[1]) if dtype == F32 else nodes[1]
+  xi[rng.random((M, ndim)) < 0.1] = 1.0
+  xi[rng.random((M, ndim)) < 0.1] = -1.0
+  xi[rng.random((M, ndim)) < 0.1] = node
+  assert (xi == node).any() and (xi == 1.0).any() and (xi == -1.0).any()
+  ev = PT.PointEvaluator.from_location(mesh, _dev(element, torch.int32),
+                                       _dev(xi, dtype))
+  return mesh, el, nodes, element, xi, ev
+
+
+def _fields(rng, N, dtype):
+  """(name, device field, NumPy values): (N,), (N, 3) row-major and a
+  component-major view."""
+  u1, u3 = rng.standard_normal(N), rng.standard_normal((N, 3))
+  cm = layout.component_major(_dev(u3, dtype))
+  assert layout.is_component_major(cm)
+  return [('scalar', _dev(u1, dtype), u1), ('rows', _dev(u3, dtype), u3),
+          ('component-major', cm, u3)]
+
+
+@pytest.mark.parametrize('dtype', DTYPES, ids=['f64', 'f32'])
+@pytest.mark.parametrize('P1', range(2, 13))
+@pytest.mark.parametrize('ndim', [2, 3])
+def test_eval_every_size(ndim, P1, dtype):
+  """`sfem_point_eval` through `from_location` (the locator plays no part)
+  against the dense reference: the error relative to max |ref| is within
+  tolerance(dtype, P1).  Measured on the CPU: the same algorithm in float32
+  is 0.8e-7..5.6e-7 from float64 for P1 = 2..12."""
+  mesh, el, nodes, element, xi, ev = _located(ndim, P1, dtype)
+  rng = F32Rng(7 * P1 + ndim)
+  hit = element >= 0
+  assert (ev.found.cpu().numpy() == hit).all()
+  for name, u, u_np in _fields(rng, mesh.num_nodes, dtype):
+    ref = PR.evaluate(el, nodes, element, xi, u_np)
+    got = ev(u)
+    assert tuple(got.shape) == ref.shape and got.dtype == dtype
+    assert bool(torch.isnan(got[~ev.found]).all())
+    assert _np(ev(u, fill=-3.0))[~hit].min() == -3.0 == \
+        _np(ev(u, fill=-3.0))[~hit].max()
+    err = np.abs(_np(got)[hit] - ref[hit]).max() / np.abs(ref).max()
+    print(f'd={ndim} P1={P1} {dtype} {name}: rel err {err:.2e}')
+    assert err <= tolerance(dtype, P1), name
+
+
+@pytest.mark.parametrize('dtype', DTYPES, ids=['f64', 'f32'])
+@pytest.mark.parametrize('P1', [2, 4, 8, 12])
+@pytest.mark.parametrize('ndim', [2, 3])
+def test_transpose(ndim, P1, dtype):
+  """`sfem_point_eval_t` + `sfem_scatter_csr` against E^T w of the dense
+  reference; <E u, w> = <u, E^T w>; two calls are bitwise equal; a
+  duplicated point doubles its contribution; weights of not-found points
+  are ignored."""
+  mesh, el, nodes, element, xi, ev = _located(ndim, P1, dtype)
+  rng = F32Rng(11 * P1 + ndim)
+  M, N = len(element), mesh.num_nodes
+  hit = element >= 0
+  for shape in [(M,), (M, 3)]:
+    w = rng.standard_normal(shape)
+    ref = PR.evaluate_t(el, nodes, element, xi, w, N)
+    got = ev.transpose(_dev(w, dtype))
+    assert tuple(got.shape) == ref.shape and got.dtype == dtype
+    err = _rel(_np(got), ref)
+    print(f'd={ndim} P1={P1} {dtype} w{shape[1:]}: rel err {err:.2e}')
+    assert err <= tolerance(dtype, P1)
+    assert torch.equal(got, ev.transpose(_dev(w, dtype)))
+    # not-found points: any weight, the same result
+    w2 = w.copy()
+    w2[~hit] = 1e6
+    assert torch.equal(got, ev.transpose(_dev(w2, dtype)))
+    if dtype == F64:
+      u = rng.standard_normal((N,) + shape[1:])
+      eu = _np(ev(_dev(u), fill=0.0))
+      lhs, rhs = (eu * w).sum(), (u * _np(got)).sum()
+      assert abs(lhs - rhs) <= 1e-12 * np.abs(eu * w).sum()
+  # the first found point once more, at the end of the list
+  j = int(np.flatnonzero(hit)[0])
+  ev2 = PT.PointEvaluator.from_location(
+      mesh, _dev(np.append(element, element[j]), torch.int32),
+      _dev(np.concatenate([xi, xi[j:j + 1]]), dtype))
+  w = rng.standard_normal(M)
+  twice = w.copy()
+  twice[j] *= 2.0
+  got = _np(ev2.transpose(_dev(np.append(w, w[j]), dtype)))
+  want = _np(ev.transpose(_dev(twice, dtype)))
+  assert _rel(got, want) <= tolerance(dtype, P1)
+  assert _rel(got, PR.evaluate_t(el, nodes, element, xi, twice, N)) <= \
+      tolerance(dtype, P1)
+
+
+# ---------------------------------------------------------------- 3. autograd
+@pytest.mark.parametrize('ndim', [2, 3])
+def test_autograd(ndim):
+  """ev(u) is differentiable in u with the transpose as backward, and the
+  converse; both are linear.  Points that require grad are refused."""
+  mesh, el, nodes, element, xi, ev = _located(ndim, 4, F64)
+  rng = np.random.default_rng(ndim)
+  M, N = len(element), mesh.num_nodes
+  for tail in [(), (3,)]:
+    u = _dev(rng.standard_normal((N,) + tail)).requires_grad_(True)
+    w = _dev(rng.standard_normal((M,) + tail))
+    (ev(u, fill=0.0) * w).sum().backward()
+    assert torch.equal(u.grad, ev.transpose(w))
+    wl = w.clone().requires_grad_(True)
+    v = _dev(rng.standard_normal((N,) + tail))
+    (ev.transpose(wl) * v).sum().backward()
+    assert torch.equal(wl.grad, ev(v, fill=0.0))
+    assert not ev(u.detach()).requires_grad
+  mesh3, X, _, _ = _mesh('three_kinds', ndim, 4, F64)
+  pts = _dev(X[:5]).requires_grad_(True)
+  with pytest.raises(NotImplementedError):
+    PT.PointEvaluator.create(mesh3, pts)
+  with pytest.raises(NotImplementedError):
+    mesh3.point_evaluator(pts)
+
+
+# -------------------------------------------------------------- 4. end to end
+def _poly(y, ndim):
+  return (1.0 + y @ np.arange(1, ndim + 1)) ** 4 - 0.5 * y[:, 0] ** 4
+
+
+@pytest.mark.parametrize('ndim', [2, 3])
+def test_end_to_end_polynomial(ndim):
+  """Locate + evaluate on an affine mesh of order 4: a polynomial of total
+  degree 4 at 500 inside points, to 1e-11 of its maximum."""
+  case = G.affine(3, ndim, 5)
+  mesh, _, rp = case.finalize(DEV, F64)
+  nodes = rp.gridpoints_1d.node_values
+  rng = np.random.default_rng(ndim)
+  _, _, x = PR.make_points(rng, rp.node_coords, rp.elements, nodes, 500)
+  ev = mesh.point_evaluator(_dev(x))
+  assert bool(ev.found.all())
+  u = _poly(np.asarray(rp.node_coords, np.float64), ndim)
+  want = _poly(x, ndim)
+  err = np.abs(_np(ev(_dev(u))) - want).max() / np.abs(want).max()
+  print(f'd={ndim}: rel err {err:.2e}')
+  assert err <= 1e-11
+
+
+def test_end_to_end_newton_cotes():
+  """The same on equispaced (NEWTON_COTES) nodes: the basis tables come from
+  the mesh's own 1D nodes."""
+  ndim = 2
+  rng = np.random.default_rng(5)
+  pm = unit_cube_mesh(3, ndim=ndim)
+  A = np.eye(ndim) + 0.3 * rng.uniform(-1, 1, (ndim, ndim))
+  grid = Nodes1D.create(5, NodeType.NEWTON_COTES)
+  rp = refine_premesh(pm.replace(node_coords=pm.node_coords @ A.T + 0.1), grid)
+  mesh = rp.finalize(device=DEV)
+  assert mesh.gridpoints_1d.node_type == NodeType.NEWTON_COTES
+  _, _, x = PR.make_points(rng, rp.node_coords, rp.elements, grid.node_values,
+                           500)
+  ev = PT.PointEvaluator.create(mesh, _dev(x))
+  assert bool(ev.found.all())
+  want = _poly(x, ndim)
+  got = _np(ev(_dev(_poly(np.asarray(rp.node_coords, np.float64), ndim))))
+  assert np.abs(got - want).max() <= 1e-11 * np.abs(want).max()
+
+
+# ----------------------------------------------------------- 5. point sources
+L0, L1 = 0.5, 1.0
+
+
+@functools.lru_cache(maxsize=None)
+def _dirichlet_box(ndim, n=2):
+  """The box of `transport_reference.box_with_sides(n, d, 4)` with u = 0 on
+  every side, on the GPU next to its dense matrices."""
+  P1 = 4
+  rp = TR.box_with_sides(n, ndim, P1)
+  mesh = rp.finalize(device=DEV)
+  x = np.asarray(rp.node_coords, np.float64)
+  on_side = (np.abs(x) < 1e-9).any(axis=1) | (np.abs(x - 1) < 1e-9).any(axis=1)
+  prob = TR.Dense(rp, P1, dvals=np.where(on_side, 0.0, np.nan))
+  bcs = {g: (BCType.DIRICHLET, 0.0) for g in mesh.boundary_facets}
+  assert len(bcs) == 2 * ndim
+  return rp, mesh, prob, bcs
+
+
+def _dense_solve(prob, rhs):
+  K, g, expand = prob._reduce(L0 * prob.B + L1 * prob.A, rhs)
+  return expand(np.linalg.solve(K, g)), np.linalg.cond(K)
+
+
+@pytest.mark.parametrize('ndim', [2, 3])
+def test_point_sources_match_dense_solve(ndim):
+  """solve_helmholtz(point_sources=...) against the dense solve with E^T s
+  added to its right-hand side, within 100 cond 1e-12 (the solver rule of the
+  dense-solve tests, rtol = 1e-12); without sources the solve is the plain
+  one."""
+  rp, mesh, prob, bcs = _dirichlet_box(ndim)
+  nodes = rp.gridpoints_1d.node_values
+  rng = np.random.default_rng(20 + ndim)
+  N = mesh.num_nodes
+  e0, xi0, x = PR.make_points(rng, rp.node_coords, rp.elements, nodes, 6)
+  s = rng.standard_normal(6)
+  f = rng.standard_normal(N)
+  ets = PR.evaluate_t(rp.elements, nodes, e0, xi0, s, N)
+  want, cond = _dense_solve(prob, prob.B @ f + ets)
+  bound = 100.0 * cond * 1e-12
+  assert bound <= 1e-7
+  kw = dict(lambda0=L0, lambda1=L1, rtol=1e-12)
+  got = solve_helmholtz(mesh, _dev(f), bcs, point_sources=(_dev(x), _dev(s)),
+                        **kw)
+  err = _rel(_np(got), want)
+  plain, _ = _dense_solve(prob, prob.B @ f)
+  print(f'd={ndim}: cond {cond:.1f}, rel err {err:.2e}, sources change u by '
+        f'{_rel(want, plain):.2e}')
+  assert _rel(want, plain) > 1e-3
+  assert err <= bound
+  # (two solves are not bitwise equal: the 3D operator assembles atomically)
+  none = solve_helmholtz(mesh, _dev(f), bcs, point_sources=None, **kw)
+  assert _rel(_np(none), plain) <= bound
+  with pytest.raises(NotImplementedError):
+    solve_helmholtz(mesh, _dev(f), bcs,
+                    point_sources=(_dev(x), _dev(s).requires_grad_(True)), **kw)
+
+
+@pytest.mark.parametrize('ndim', [2, 3])
+def test_point_source_reciprocity(ndim):
+  """The symmetric operator: the solution for a unit source at x_a, read at
+  x_b, equals the solution for a unit source at x_b, read at x_a, to the
+  solver tolerance."""
+  rp, mesh, prob, bcs = _dirichlet_box(ndim)
+  nodes = rp.gridpoints_1d.node_values
+  rng = np.random.default_rng(30 + ndim)
+  _, _, x = PR.make_points(rng, rp.node_coords, rp.elements, nodes, 12)
+  x = x[5:7]                                    # two points of general position
+  cond = np.linalg.cond(prob._reduce(L0 * prob.B + L1 * prob.A,
+                                     np.zeros(mesh.num_nodes))[0])
+  bound = 100.0 * cond * 1e-12
+  ev = PT.PointEvaluator.create(mesh, _dev(x))
+  one = _dev(np.ones(1))
+  zero = torch.zeros(mesh.num_nodes, dtype=F64, device=DEV)
+  ua = solve_helmholtz(mesh, zero, bcs, lambda0=L0, lambda1=L1, rtol=1e-12,
+                       point_sources=(_dev(x[:1]), one))
+  ub = solve_helmholtz(mesh, zero, bcs, lambda0=L0, lambda1=L1, rtol=1e-12,
+                       point_sources=(_dev(x[1:]), one))
+  a_at_b, b_at_a = float(ev(ua)[1]), float(ev(ub)[0])
+  scale = max(float(ua.abs().max()), float(ub.abs().max()))
+  print(f'd={ndim}: {a_at_b:.12e} vs {b_at_a:.12e}, max |u| {scale:.3e}')
+  assert abs(a_at_b) > 1e-3 * scale
+  assert abs(a_at_b - b_at_a) <= bound * scale
+
+
+# ------------------------------------------------------- 6. inverse problem
+@pytest.mark.parametrize('ndim', [2, 3])
+def test_inverse_problem_gradient(ndim):
+  """loss = sum (ev(solve_helmholtz(diffusivity=k)) - data)^2 with k (E,)
+  requiring grad on 3^d elements, P1 = 4: k.grad against central differences
+  for three entries of k, with the step (1e-4) and the bound (1e-7, relative
+  to the largest gradient entry) of the coefficient gradients in
+  `tests/adjoint_reference.py`, the solves at rtol = 1e-15 as there."""
+  rp, mesh, _, bcs = _dirichlet_box(ndim, n=3)
+  nodes = rp.gridpoints_1d.node_values
+  rng = np.random.default_rng(40 + ndim)
+  E = mesh.num_elements
+  assert E == 3 ** ndim
+  _, _, x = PR.make_points(rng, rp.node_coords, rp.elements, nodes, 40)
+  ev = PT.PointEvaluator.create(mesh, _dev(x))
+  assert bool(ev.found.all())
+  f = _dev(1.0 + rng.random(mesh.num_nodes))
+  k0 = 1.0 + rng.random(E)
+  data = _dev(0.01 * rng.standard_normal(40))
+
+  def loss(k):
+    u = solve_helmholtz(mesh, f, bcs, lambda0=L0, lambda1=L1, rtol=1e-15,
+                        preconditioner='jacobi', diffusivity=k)
+    return ((ev(u) - data) ** 2).sum()
+
+  k = _dev(k0).requires_grad_(True)
+  loss(k).backward()
+  grad = _np(k.grad)
+  assert grad.shape == (E,) and np.abs(grad).max() > 0
+  h = AJ.CD_H
+  for i in (0, E // 2, E - 1):
+    dk = np.zeros(E)
+    dk[i] = h
+    with torch.no_grad():
+      cd = (float(loss(_dev(k0 + dk))) - float(loss(_dev(k0 - dk)))) / (2 * h)
+    err = abs(cd - grad[i]) / np.abs(grad).max()
+    print(f'd={ndim} entry {i}: grad {grad[i]:.6e}, central difference '
+          f'{cd:.6e}, discrepancy {err:.2e}')
+    assert err <= AJ.CD_BOUND
+
+
+# ------------------------------------------------------------------ 7. refusals
+def test_refusals():
+  mesh, X, _, _ = _mesh('three_kinds', 2, 4, F64)
+  pts = _dev(X[:4])
+  with pytest.raises(NotImplementedError):
+    PT.PointEvaluator.create(mesh.replace(axis_name='i'), pts)
+  with pytest.raises(NotImplementedError):
+    PT.PointEvaluator.create(mesh.replicate(2), pts)
+  for bad in (_dev(X[:4, :1]), _dev(X[0]), _dev(X[:4], F32), pts.cpu()):
+    with pytest.raises(ValueError):
+      PT.PointEvaluator.create(mesh, bad)
+  ev = PT.PointEvaluator.create(mesh, pts)
+  assert bool(ev.found.all())
+  N = mesh.num_nodes
+  for bad in (torch.zeros(N + 1, dtype=F64, device=DEV),
+              torch.zeros(N, dtype=F32, device=DEV),
+              torch.zeros(N, dtype=F64), torch.zeros((N, 2, 2), device=DEV)):
+    with pytest.raises(ValueError):
+      ev(bad)
+  for bad in (torch.zeros(5, dtype=F64, device=DEV),
+              torch.zeros(4, dtype=F32, device=DEV), torch.zeros(4, dtype=F64)):
+    with pytest.raises(ValueError):
+      ev.transpose(bad)
+  with pytest.raises(ValueError):
+    PT.PointEvaluator.from_location(mesh, ev.element.cpu(), ev.xi.cpu())
+  # a non-contiguous field is copied, not misread
+  u = torch.randn((N, 6), dtype=F64, device=DEV)[:, ::2]
+  assert torch.equal(ev(u), ev(u.contiguous()))
