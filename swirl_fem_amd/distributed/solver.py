@@ -26,6 +26,7 @@ from __future__ import annotations
 import torch
 
 from swirl_fem_amd.distributed import comm
+from swirl_fem_amd.linalg import _driver
 from swirl_fem_amd.linalg import cg as cg_lib
 
 
@@ -184,9 +185,5 @@ def cg(local_op, b_local, plan: comm.NeighborPlan, *, x0=None, tol=1e-5,
   run = make_runner(local_op, b_local, plan, x0=x0, tol=tol, atol=atol,
                     maxiter=maxiter, group=group, assembled_rhs=assembled_rhs,
                     M=M)
-  while run.issued < run.maxiter:
-    for _ in range(min(check_every, run.maxiter - run.issued)):
-      run.step()
-    if run.done():
-      break
+  _driver.drive(run, check_every)
   return run.x, run.info()

@@ -40,12 +40,11 @@ x is the last iterate.
 
 from __future__ import annotations
 
-import warnings
-
 import torch
 
 from swirl_fem_amd import _lib
 from swirl_fem_amd import _ops
+from swirl_fem_amd.linalg import _driver
 
 
 class _Scalars:
@@ -179,11 +178,7 @@ def bicgstab(A, b, x0=None, *, tol=1e-5, atol=0.0, maxiter=None, M=None,
     for _ in range(min(check_every, run.maxiter - run.issued)):
       run.step()
   info = run.info()
-  if info['status'].startswith('breakdown'):
-    warnings.warn(f"bicgstab stopped with status '{info['status']}' after "
-                  f"{info['num_iterations']} iterations: x is the last "
-                  'iterate, not a solution to the requested tolerance',
-                  RuntimeWarning, stacklevel=2)
+  _driver.warn_on_breakdown('bicgstab', info)
   return run.x, info
 
 

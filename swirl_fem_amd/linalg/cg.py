@@ -40,11 +40,37 @@ Per iteration (M = identity): A(p) with p.Ap fused into the operator's scatter
 stage when it offers `apply_with_dot`; r -= a Ap fused with r.r; then
 x += a p and p = r + b p in one kernel  ->  8 N-vector passes besides the
 apply (SURVEY 8d's fused model: 11; the reference's un-fused loop: 13).
+
+The modes of `CGRunner`.  Each is an attribute that holds the mode's state,
+or None / False / 0 when the mode is off; `__init__` selects them in the
+order of the table (a mode's test names only modes above it), `_step_eager`
+runs the four stages -- apply A and alpha, update r and gamma_new, update x
+and p, close the iteration -- and each stage asks the attributes.  `_ops`
+calls are named without their prefix.
+
+| mode | selected when | r update, gamma_new | x / p update | excludes |
+|---|---|---|---|---|
+| `fused_dot` | `dot_fn` is None, A has `apply_with_dot`, one tensor | (p.Ap from the apply's partial sums: `cg_scalars` phase 3, or 5 when `merged`) | | -- (`rr_stop` switches it off) |
+| `merged` | `fused_dot` and no `reduce_fn` | (one scalar launch per iteration: phase 5 gives alpha and closes the iteration before; `_flush` closes the last) | | |
+| `fuse_rr` (= 2) | M is None, `dot_fn` is None | `cg_update_r` sums r.r over 64 slots; otherwise z = M(r) and `dot` (or `M.apply_with_dot`, or `dot_fn`) | `cg_update_xp` | |
+| `fold_rr` | `fuse_rr` with `reduce_fn` or `interface` | + `cg_scalars` phase 7, `dot_indexed`, `reduce_fn` | | |
+| `rr_stop` | M has `stops_on_residual`, `dot_fn` is None, one 1-D tensor | `_step_residual_stop`: `cg_update_r` (`_layered`), z = M(r), `pmg_dot2`, `pmg_cg_scalars` | `cg_update_xp` | `fused_dot`, and every mode below |
+| `mean` | M has `mean_projection()`, no `dot_fn` / `reduce_fn` / `interface`, one tensor, `SFEM_FUSED_MEAN` | `cg_update_r_mean` | `cg_update_xp_mean` | `jacobi`, `layered`, `lazy` |
+| `jacobi` | M has `jacobi_diagonal()` of r's length, `dot_fn` is None, `interface` or no `reduce_fn`, a scalar or component-major field, `SFEM_FUSED_JACOBI` | `cg_update_r_jacobi` (with the layers and, with `det`, `cg_scalars_n` phase 8); with `reduce_fn`: phase 7, `dot_indexed` with `jacobi_interface`, `reduce_fn` | `cg_update_xp_jacobi` | `lazy` |
+| `layered` | `fused_dot`, a 1-D field, A has `apply_layered_with_dot` and a layer plan | `cg_update_r_layered` | | |
+| `det` | `layered`, no `reduce_fn` / `interface`, `SFEM_DETERMINISTIC` | `cg_scalars_n` phase 5 after the apply; `cg_update_r_layered_det`, `cg_scalars_n` phase 8 | | |
+| `lazy` | `SFEM_LAZY_X` >= 2, p one contiguous tensor of `SFEM_LAZY_X_MIN_MB` or more | | `cg_update_xp_lazy`; `cg_flush_x` when x is read | dropped by `capture` |
+
+Known limitation: `det` is also selected when a preconditioner M is given
+(`fuse_rr` = 0).  The r update is then `cg_update_r_layered` and r . M r a
+plain `dot`, which accumulates with atomics: such an iteration is NOT bitwise
+reproducible, only its p.Ap is summed in a fixed order.  (The fused Jacobi
+update does take the fixed-order sums.)
 """
 
 from __future__ import annotations
 
-import os
+from typing import NamedTuple
 
 import torch
 
@@ -52,6 +78,7 @@ from swirl_fem_amd import switches
 from swirl_fem_amd import _lib
 from swirl_fem_amd import _ops
 from swirl_fem_amd.core import layout
+from swirl_fem_amd.linalg import _driver
 
 
 def _leaves(t):
@@ -84,11 +111,33 @@ MAX_KEPT_RUNNERS = 6   # solver states a `workspace` of `cg` holds at most
 LAZY_X_MIN_BYTES = 1 << 28
 RR_PARTIALS = 1 << 16      # stored r.r sums: one per workgroup of the r update
 RESIDUAL_STOP_GROUPS = 512  # stored partial sums per inner product (r.r stop)
+# `fuse_rr` of the r updates: r.r spread over 64 slots, update_r then streams
+# with 128 workgroups per CU.  When something needs the complete sum in the
+# named slot right after the update (an all-reduce, the interface correction)
+# one tiny scalar launch folds the slots first (`fold_rr`).
+FUSE_RR_SPREAD = 2
 
 
 def _lazy_min_bytes():
   mb = switches.get('SFEM_LAZY_X_MIN_MB')
   return LAZY_X_MIN_BYTES if mb is None else int(float(mb) * (1 << 20))
+
+
+# The states of the modes (`CGRunner.rr_stop`, `.mean`, `.jacobi`, `.det`,
+# `.lazy`).  rr_stop: stored partial sums of the inner products; `layered`:
+# the operator's layer plan (its apply then stores per-wave p.Ap sums in
+# `waves`) or None.  det: one double per wave of the apply, one per workgroup
+# of the r update.  lazy: the (m, n padded) ring of directions.
+_ResidualStop = NamedTuple('_ResidualStop', [
+    ('groups', int), ('layered', object), ('parts', torch.Tensor),
+    ('waves', torch.Tensor), ('num_waves', int)])
+_Mean = NamedTuple('_Mean', [('w', torch.Tensor), ('total', float),
+                             ('sums', torch.Tensor)])
+_Jacobi = NamedTuple('_Jacobi', [('dinv', torch.Tensor), ('ncomp', int)])
+_Det = NamedTuple('_Det', [('wave_sums', torch.Tensor),
+                           ('rr_sums', torch.Tensor)])
+_Lazy = NamedTuple('_Lazy', [('ring', torch.Tensor), ('n', int),
+                             ('state', torch.Tensor)])
 
 
 class _Scalars:
@@ -113,11 +162,22 @@ class _Scalars:
     for x, y in zip(_leaves(a), _leaves(b)):
       _ops.dot_indexed(x, layout.like(y, x), idx, w, self.t, slot, -1.0)
 
-  def dot_into(self, slot, a, b, dot_fn, reduce_fn, interface=None):
-    """scalars[slot] = <a, b> summed over the leaves of the pytrees."""
+  def complete(self, slot, a, b, reduce_fn, interface):
+    """What turns the local sum of a . b in `slot` into the inner product:
+    the interface correction, then the reduction over the partitions."""
+    if interface is not None:
+      self.interface_correction(slot, a, b, interface)
+    if reduce_fn is not None:
+      reduce_fn(self.t[slot:slot + 1])
+
+  def dot_into(self, slot, a, b, dot_fn, reduce_fn, interface=None,
+               cleared=False):
+    """scalars[slot] = <a, b> summed over the leaves of the pytrees.
+    `cleared`: the slot is zero already (a scalar phase cleared it), so the
+    device dot of the first leaf accumulates as well."""
     la, lb = _leaves(a), _leaves(b)
     if dot_fn is None:
-      first = True
+      first = not cleared
       for x, y in zip(la, lb):
         _ops.dot(layout.flat(x), layout.flat(layout.like(y, x)), self.t, slot,
                  accumulate=not first)
@@ -126,17 +186,14 @@ class _Scalars:
       total = sum(dot_fn(x, y) for x, y in zip(la, lb))
       self.t[slot] = torch.as_tensor(total, dtype=torch.float64,
                                      device=self.t.device)
-    if interface is not None:
-      self.interface_correction(slot, a, b, interface)
-    if reduce_fn is not None:
-      reduce_fn(self.t[slot:slot + 1])
+    self.complete(slot, a, b, reduce_fn, interface)
 
 
 class CGRunner:
   """State of one CG solve; `step()` enqueues exactly one iteration.
 
   `cg()` drives it until the device flag reports convergence; `bench.py`
-  steps it a fixed number of times.
+  steps it a fixed number of times.  The module docstring lists the modes.
   """
 
   def __init__(self, A, b, x0=None, *, tol=1e-5, atol=0.0, maxiter=None,
@@ -157,135 +214,57 @@ class CGRunner:
     if maxiter is None:
       maxiter = 10 * sum(l.numel() for l in b_leaves)
     self.maxiter = maxiter
-    device = b_leaves[0].device
     dense = lambda t: t if (t.is_contiguous() or
                             layout.is_component_major(t)) else t.contiguous()
     b = _map(dense, b)
     self._x = (_map(torch.zeros_like, b) if x0 is None
                else _map(lambda t, bb: layout.like(t, bb).clone(), x0, b))
-    self.lazy = None
-    self.s = s = _Scalars(device)
-    S = _Scalars
+    self.s = _Scalars(b_leaves[0].device)
     self.identity_m = M is None
-    s.dot_into(S.BB, b, b, dot_fn, reduce_fn, interface)
-    self.r = _map(lambda bb, ax: bb - layout.like(ax, bb), b, A(self._x))
-    z = self.r if self.identity_m else M(self.r)
-    self._p = _map(lambda t, rr: layout.like(t, rr).clone(), z, self.r)
-    s.dot_into(S.GAMMA, self.r, z, dot_fn, reduce_fn, interface)
+    self.issued = 0
+    self._graph = None
+    self._capture_failed = False
+    z = self._start_vectors(b, allocate=True)
     # operators exposing `apply_with_dot` hand back p.Ap with the apply
     self.fused_dot = (dot_fn is None and hasattr(A, 'apply_with_dot') and
                       isinstance(self._p, torch.Tensor))
-    self.parts = s.partials if self.fused_dot else None
-    _ops.cg_scalars(s.t, 2, maxiter, tol, atol, self.parts)
-    self.fuse_rr = self.identity_m and dot_fn is None
-    # stop on r.r with fixed-order sums: the preconditioner asks for it
-    self.rr_stop = None
-    if (getattr(M, 'stops_on_residual', False) and dot_fn is None and
-        isinstance(self.r, torch.Tensor) and self.r.dim() == 1):
-      self._residual_stop_setup(A, b, z)
-    # r.r spread over 64 slots: update_r then streams with 128 workgroups per
-    # CU.  When something needs the complete sum in the named slot right after
-    # the update (an all-reduce, the interface correction) one tiny scalar
-    # launch folds the slots first.
-    if self.fuse_rr:
-      self.fuse_rr = 2
-    self.fold_rr = self.fuse_rr == 2 and (reduce_fn is not None or
-                                          interface is not None)
-    # M r = r - (w . r / total) 1 folded into the two vector updates
-    self.mean = None
-    probe = getattr(M, 'mean_projection', None)
-    if (probe is not None and self.rr_stop is None and dot_fn is None and reduce_fn is None and
-        interface is None and isinstance(self.r, torch.Tensor) and
-        switches.get('SFEM_FUSED_MEAN') != '0'):
-      found = probe()
-      if found is not None:
-        w, total = found
-        self.mean = (layout.flat(layout.like(w.to(self.r.dtype), self.r)),
-                     float(total),
-                     torch.zeros(_lib.SFEM_CG_MEAN_SUMS, dtype=torch.float64,
-                                 device=device))
-    # M r = dinv (.) r folded into the two vector updates: (dinv, components)
-    # of a scalar or component-major field (one dinv for all components)
-    self.jacobi = None
-    probe = getattr(M, 'jacobi_diagonal', None)
-    if (probe is not None and self.mean is None and self.rr_stop is None and
-        dot_fn is None and
-        (interface is not None or reduce_fn is None) and
-        isinstance(self.r, torch.Tensor) and
-        switches.get('SFEM_FUSED_JACOBI') != '0'):
-      dinv = probe()
-      dinv = None if dinv is None else dinv.to(self.r.dtype).contiguous()
-      n = -1 if dinv is None else dinv.numel()
-      vn = 16 // self.r.element_size()
-      if self.r.dim() == 1 or (self.r.dim() == 2 and self.r.shape[1] == 1 and
-                               self.r.is_contiguous()):
-        ncomp = 1
-      elif (self.r.dim() == 2 and layout.is_component_major(self.r) and
-            self._p.stride() == self.r.stride() and n % vn == 0):
-        ncomp = self.r.shape[1]
-      else:
-        ncomp = None       # (row-major fields: M is called as a function)
-      if ncomp is not None and self.r.shape[0] == n:
-        self.jacobi = (dinv, ncomp)
+    self.fuse_rr = FUSE_RR_SPREAD if self.identity_m and dot_fn is None else 0
+    self.fold_rr = bool(self.fuse_rr) and (reduce_fn is not None or
+                                           interface is not None)
+    self.parts = self.s.partials if self.fused_dot else None
+    self._start_scalars(z)
+    self.rr_stop = self._select_residual_stop()
+    if self.rr_stop is not None:
+      self.fused_dot, self.parts = False, None
+    self._args = (self.maxiter, self.tol, self.atol, self.parts)
+    # Without an all-reduce between the sum of the partials and alpha the
+    # iteration needs ONE scalar launch: phase 5 also closes the previous
+    # iteration (beta, gamma, counter, convergence flag) -- see `_flush`.
+    self.merged = self.fused_dot and reduce_fn is None
+    self.mean = self._select_mean()
+    self.jacobi = self._select_jacobi()
     # r . (dinv r) of consistent vectors: its interface correction is the
     # r . r one with the weights w dinv (dinv is the same on every holder)
     self.jacobi_interface = None
     if self.jacobi is not None and interface is not None:
       idx, w = interface
       self.jacobi_interface = (
-          idx, (w * self.jacobi[0][idx].double()).contiguous())
-    # Layered assembly: the operator leaves the contributions of shared nodes
-    # in layers of an extended Ap (plain stores: no atomics, no cleared range)
-    # and `r -= alpha Ap` adds them up where it streams Ap anyway, in a fixed
-    # order -- same sums, bitwise reproducible.  One partition, scalar field.
-    # On partitions (`reduce_fn`, `interface`) the operator hands back the
-    # layered result with its interface nodes already whole and exchanged.
-    self.layered = None
-    if (self.fused_dot and self.mean is None and self.rr_stop is None and
-        self._p.dim() == 1 and
-        hasattr(A, 'apply_layered_with_dot')):
-      self.layered = A.layer_plan()
-    # ... and with the two inner products of the iteration summed from STORED
-    # partial sums in a fixed order (one double per wave of the apply, one per
-    # workgroup of the r update) the whole iteration is bitwise reproducible
-    # from run to run; costs one more scalar launch per iteration
-    self.det = None
-    if (self.layered is not None and reduce_fn is None and interface is None
-        and switches.get('SFEM_DETERMINISTIC') != '0'):
-      # (+ SFEM_FOLD_GROUPS: scratch of the two-stage sums behind the slots)
-      pad = _lib.SFEM_FOLD_GROUPS
-      self.det = (torch.zeros(A.layered_dot_slots() + pad, dtype=torch.float64,
-                              device=device),
-                  torch.zeros(RR_PARTIALS + pad, dtype=torch.float64,
-                              device=device))
-      self._reproducible_start(b, z)
-    # Lazy solution update (`sfem_cg_update_xp_lazy`): x is touched every m-th
-    # iteration only, the directions in between wait in a ring -- bitwise the
-    # same x, 4.25 instead of 5 vector passes in the x / p update at m = 4.
-    # Worth m - 1 more vectors only where the iteration streams from HBM.
-    # (With the fused Jacobi updates x is updated every iteration.)
-    m = int(switches.get('SFEM_LAZY_X'))
-    if (m >= 2 and self.mean is None and self.jacobi is None and
-        self.rr_stop is None and
-        isinstance(self._p, torch.Tensor) and
-        self._p.is_contiguous() and
-        self._p.numel() * self._p.element_size() >= _lazy_min_bytes()):
-      m = min(m, _lib.SFEM_CG_LAZY_MAX)
-      n = self._p.numel()
-      ring = torch.empty((m, (n + 3) // 4 * 4), dtype=self._p.dtype,
-                         device=device)
-      ring[0, :n] = self._p.reshape(-1)
-      self._p = None
-      self.lazy = (ring, n, torch.zeros(1 + _lib.SFEM_CG_LAZY_MAX,
-                                        dtype=torch.float64, device=device))
-      self._shape = tuple(self.r.shape)
-    self.issued = 0
-    self._graph = None
-    self._capture_failed = False
+          idx, (w * self.jacobi.dinv[idx].double()).contiguous())
+    self.layered = self._select_layered()
+    self.det = self._select_det()
+    self.lazy = self._select_lazy()
+    self._start_fixed_order_sums(b, z)
 
-  def _residual_stop_setup(self, A, b, z):
-    """State of the r.r-stopping path: stored partial sums of the inner
-    products, and the layered apply (per-wave p.Ap sums) when A has one."""
+  # --------------------------------------------------------- mode selection
+  def _select_residual_stop(self):
+    """Stop on r.r with fixed-order sums: the preconditioner asks for it.
+    State: stored partial sums of the inner products, and the layered apply
+    (per-wave p.Ap sums) when A has one."""
+    A = self.A
+    if not (getattr(self.M, 'stops_on_residual', False) and
+            self.dot_fn is None and isinstance(self.r, torch.Tensor) and
+            self.r.dim() == 1):
+      return None
     dev = self.r.device
     G = RESIDUAL_STOP_GROUPS
     layered = None
@@ -293,31 +272,153 @@ class CGRunner:
         self.reduce_fn is None and self.interface is None):
       layered = A.layer_plan()
     waves = A.layered_dot_slots() if layered is not None else 0
-    self.rr_stop = dict(
+    return _ResidualStop(
         groups=G, layered=layered,
         parts=torch.zeros(2 * G, dtype=torch.float64, device=dev),
         waves=torch.zeros(waves + _lib.SFEM_FOLD_GROUPS, dtype=torch.float64,
                           device=dev), num_waves=waves)
-    self.fused_dot = False
-    self.parts = None
-    self._residual_stop_start(b, z)
+
+  def _select_mean(self):
+    """M r = r - (w . r / total) 1 folded into the two vector updates."""
+    probe = getattr(self.M, 'mean_projection', None)
+    if not (probe is not None and self.rr_stop is None and
+            self.dot_fn is None and self.reduce_fn is None and
+            self.interface is None and isinstance(self.r, torch.Tensor) and
+            switches.get('SFEM_FUSED_MEAN') != '0'):
+      return None
+    found = probe()
+    if found is None:
+      return None
+    w, total = found
+    return _Mean(layout.flat(layout.like(w.to(self.r.dtype), self.r)),
+                 float(total),
+                 torch.zeros(_lib.SFEM_CG_MEAN_SUMS, dtype=torch.float64,
+                             device=self.r.device))
+
+  def _select_jacobi(self):
+    """M r = dinv (.) r folded into the two vector updates: (dinv, components)
+    of a scalar or component-major field (one dinv for all components)."""
+    probe = getattr(self.M, 'jacobi_diagonal', None)
+    r = self.r
+    if not (probe is not None and self.mean is None and
+            self.rr_stop is None and self.dot_fn is None and
+            (self.interface is not None or self.reduce_fn is None) and
+            isinstance(r, torch.Tensor) and
+            switches.get('SFEM_FUSED_JACOBI') != '0'):
+      return None
+    dinv = probe()
+    dinv = None if dinv is None else dinv.to(r.dtype).contiguous()
+    n = -1 if dinv is None else dinv.numel()
+    vn = 16 // r.element_size()
+    if r.dim() == 1 or (r.dim() == 2 and r.shape[1] == 1 and
+                        r.is_contiguous()):
+      ncomp = 1
+    elif (r.dim() == 2 and layout.is_component_major(r) and
+          self._p.stride() == r.stride() and n % vn == 0):
+      ncomp = r.shape[1]
+    else:
+      return None          # (row-major fields: M is called as a function)
+    return _Jacobi(dinv, ncomp) if r.shape[0] == n else None
+
+  def _select_layered(self):
+    """Layered assembly: the operator leaves the contributions of shared nodes
+    in layers of an extended Ap (plain stores: no atomics, no cleared range)
+    and `r -= alpha Ap` adds them up where it streams Ap anyway, in a fixed
+    order -- same sums, bitwise reproducible.  One partition, scalar field.
+    On partitions (`reduce_fn`, `interface`) the operator hands back the
+    layered result with its interface nodes already whole and exchanged."""
+    if (self.fused_dot and self.mean is None and self.rr_stop is None and
+        self._p.dim() == 1 and hasattr(self.A, 'apply_layered_with_dot')):
+      return self.A.layer_plan()
+    return None
+
+  def _select_det(self):
+    """... and with the two inner products of the iteration summed from STORED
+    partial sums in a fixed order (one double per wave of the apply, one per
+    workgroup of the r update) the whole iteration is bitwise reproducible
+    from run to run; costs one more scalar launch per iteration."""
+    if not (self.layered is not None and self.reduce_fn is None and
+            self.interface is None and
+            switches.get('SFEM_DETERMINISTIC') != '0'):
+      return None
+    # (+ SFEM_FOLD_GROUPS: scratch of the two-stage sums behind the slots)
+    pad = _lib.SFEM_FOLD_GROUPS
+    dev = self.r.device
+    return _Det(torch.zeros(self.A.layered_dot_slots() + pad,
+                            dtype=torch.float64, device=dev),
+                torch.zeros(RR_PARTIALS + pad, dtype=torch.float64,
+                            device=dev))
+
+  def _select_lazy(self):
+    """Lazy solution update (`sfem_cg_update_xp_lazy`): x is touched every
+    m-th iteration only, the directions in between wait in a ring -- bitwise
+    the same x, 4.25 instead of 5 vector passes in the x / p update at m = 4.
+    Worth m - 1 more vectors only where the iteration streams from HBM.
+    (With the fused Jacobi updates x is updated every iteration.)  The ring
+    takes the place of `_p`."""
+    m = int(switches.get('SFEM_LAZY_X'))
+    p = self._p
+    if not (m >= 2 and self.mean is None and self.jacobi is None and
+            self.rr_stop is None and isinstance(p, torch.Tensor) and
+            p.is_contiguous() and
+            p.numel() * p.element_size() >= _lazy_min_bytes()):
+      return None
+    m = min(m, _lib.SFEM_CG_LAZY_MAX)
+    n = p.numel()
+    ring = torch.empty((m, (n + 3) // 4 * 4), dtype=p.dtype, device=p.device)
+    ring[0, :n] = p.reshape(-1)
+    self._p = None
+    self._shape = tuple(self.r.shape)
+    return _Lazy(ring, n, torch.zeros(1 + _lib.SFEM_CG_LAZY_MAX,
+                                      dtype=torch.float64, device=p.device))
+
+  # ------------------------------------------------------------------ start
+  def _start_vectors(self, b, allocate=False):
+    """b.b, r = b - A x, z = M r and p = z for the x in place; returns z.
+    `__init__` allocates r and p here, `restart` rewrites them in place."""
+    s, S = self.s, _Scalars
+    s.dot_into(S.BB, b, b, self.dot_fn, self.reduce_fn, self.interface)
+    Ax = self.A(self._x)
+    if allocate:
+      self.r = _map(lambda bb, ax: bb - layout.like(ax, bb), b, Ax)
+    else:
+      _map(lambda rr, bb, ax: rr.copy_(layout.like(bb, rr) -
+                                       layout.like(ax, rr)), self.r, b, Ax)
+    z = self.r if self.identity_m else self.M(self.r)
+    if allocate:
+      self._p = _map(lambda t, rr: layout.like(t, rr).clone(), z, self.r)
+    else:
+      _map(lambda pp, zz: pp.copy_(layout.like(zz, pp)), self.p, z)
+    return z
+
+  def _start_scalars(self, z):
+    """gamma_0 = r.z and the stopping rule (phase 2)."""
+    s = self.s
+    s.dot_into(_Scalars.GAMMA, self.r, z, self.dot_fn, self.reduce_fn,
+               self.interface)
+    _ops.cg_scalars(s.t, 2, self.maxiter, self.tol, self.atol, self.parts)
+
+  def _start_fixed_order_sums(self, b, z):
+    """The modes that sum in a fixed order take b.b and gamma_0 again."""
+    if self.det is not None:
+      self._reproducible_start(b, z)
+    if self.rr_stop is not None:
+      self._residual_stop_start(b, z)
 
   def _residual_stop_start(self, b, z):
     """b.b, r.r and gamma_0 = r.z as fixed-order sums; the stop rule on r.r."""
     st = self.rr_stop
-    G, parts = st['groups'], st['parts']
     args = (self.maxiter, self.tol, self.atol)
     self._dot2(b, b, None)
-    _ops.pmg_cg_scalars(self.s.t, 3, parts, G, *args)
+    _ops.pmg_cg_scalars(self.s.t, 3, st.parts, st.groups, *args)
     self._dot2(self.r, self.r, layout.like(z, self.r).contiguous())
-    _ops.pmg_cg_scalars(self.s.t, 2, parts, G, *args)
+    _ops.pmg_cg_scalars(self.s.t, 2, st.parts, st.groups, *args)
 
   def _dot2(self, a, b, c):
     """Stored partial sums of a.b (and a.c) for `sfem_pmg_cg_scalars`; on
     partitions the interface correction goes into the first partial of each
     and the partials are all-reduced, so every rank adds the same numbers."""
-    st = self.rr_stop
-    G, parts = st['groups'], st['parts']
+    G, parts = self.rr_stop.groups, self.rr_stop.parts
     _ops.pmg_dot2(a, b, c, parts, G)
     if self.interface is not None:
       idx, w = self.interface
@@ -327,28 +428,6 @@ class CGRunner:
           _ops.dot_indexed(a, c, idx, w, parts, G, -1.0)
     if self.reduce_fn is not None:
       self.reduce_fn(parts[:G if c is None else 2 * G])
-
-  def _step_residual_stop(self):
-    """One PCG iteration that stops on r.r (see the module docstring)."""
-    s, st = self.s, self.rr_stop
-    G, parts = st['groups'], st['parts']
-    args = (self.maxiter, self.tol, self.atol)
-    if st['layered'] is not None:
-      Ap = self.A.apply_layered_with_dot(self.p, st['waves'], per_wave=True)
-      _ops.pmg_cg_scalars(s.t, 0, st['waves'], st['num_waves'], *args)
-      _ops.cg_update_r_layered(self.r, Ap, st['layered'].layers, s.t, 0,
-                               masks=st['layered'].masks)
-    else:
-      Ap = layout.like(self.A(self.p), self.r).contiguous()
-      self._dot2(self.p, Ap, None)
-      _ops.pmg_cg_scalars(s.t, 0, parts, G, *args)
-      _ops.cg_update_r(self.r, Ap, s.t, 0)
-    z = layout.like(self.M(self.r), self.r).contiguous()
-    self._dot2(self.r, self.r, z)
-    _ops.pmg_cg_scalars(s.t, 4, parts, G, *args)
-    _ops.cg_update_xp(self._x, self.p, z, s.t)
-    _ops.pmg_cg_scalars(s.t, 1, parts, G, *args)
-    self.issued += 1
 
   def _reproducible_start(self, b, z):
     """b.b and gamma_0 = r.z again, as tree reductions without atomics (the
@@ -370,7 +449,7 @@ class CGRunner:
       return 10
     if self.lazy is None:
       return 8
-    m = self.lazy[0].shape[0]
+    m = self.lazy.ring.shape[0]
     return 3 + (4 * m + 1) / m
 
   @property
@@ -387,8 +466,8 @@ class CGRunner:
     after adding the terms that were still held back)."""
     if self.lazy is not None:
       self._flush()
-      ring, n, state = self.lazy
-      _ops.cg_flush_x(layout.flat(self._x), ring, self.s.t, state)
+      _ops.cg_flush_x(layout.flat(self._x), self.lazy.ring, self.s.t,
+                      self.lazy.state)
     return self._x
 
   def matches(self, b, tol, atol, maxiter) -> bool:
@@ -415,32 +494,20 @@ class CGRunner:
     HIP graph stays valid -- a time stepper that solves with the same
     operators every step then records each of them once (recording costs
     about 1 ms per solve, a third of a Kolmogorov-generator step)."""
-    s, S = self.s, _Scalars
     if x0 is None:
       _map(lambda xx: xx.zero_(), self._x)
     else:
       _map(lambda xx, t: xx.copy_(layout.like(t, xx)), self._x, x0)
     self.issued = 0
     if self.lazy is not None:
-      self.lazy[2].zero_()
-    s.dot_into(S.BB, b, b, self.dot_fn, self.reduce_fn, self.interface)
-    _map(lambda rr, bb, ax: rr.copy_(layout.like(bb, rr) - layout.like(ax, rr)),
-         self.r, b, self.A(self._x))
-    z = self.r if self.identity_m else self.M(self.r)
-    if z is not self.r:
-      _map(lambda pp, zz: pp.copy_(layout.like(zz, pp)), self.p, z)
-    else:
-      _map(lambda pp, rr: pp.copy_(rr), self.p, self.r)
-    s.dot_into(S.GAMMA, self.r, z, self.dot_fn, self.reduce_fn, self.interface)
-    _ops.cg_scalars(s.t, 2, self.maxiter, self.tol, self.atol, self.parts)
-    if self.det is not None:
-      self._reproducible_start(b, z)
-    if self.rr_stop is not None:
-      self._residual_stop_start(b, z)
+      self.lazy.state.zero_()
+    z = self._start_vectors(b)
+    self._start_scalars(z)
+    self._start_fixed_order_sums(b, z)
     if self.mean is not None:
-      self.mean[2].zero_()
-    self.issued = 0
+      self.mean.sums.zero_()
 
+  # -------------------------------------------------------------- iteration
   def step(self):
     """One iteration of cg.py:75-86, all on the device."""
     if self._graph is not None:
@@ -453,143 +520,153 @@ class CGRunner:
     if self.rr_stop is not None:
       self._step_residual_stop()
       return
-    s, S = self.s, _Scalars
-    A, M, dot_fn, reduce_fn = self.A, self.M, self.dot_fn, self.reduce_fn
-    args = (self.maxiter, self.tol, self.atol, self.parts)
-    merged = self.fused_dot and reduce_fn is None
-    if self.fused_dot and self.det is not None:
-      Ap = A.apply_layered_with_dot(self.p, self.det[0], per_wave=True)
-      _ops.cg_scalars_n(s.t, 5, self.maxiter, self.tol, self.atol,
-                        self.det[0],
-                        self.det[0].numel() - _lib.SFEM_FOLD_GROUPS)
-    elif self.fused_dot:
+    Ap = self._apply_and_alpha()
+    z = self._update_r(Ap)
+    self._update_xp(z)
+    self._close()
+
+  def _apply_and_alpha(self):
+    """Ap = A p, p.Ap and alpha = gamma / p.Ap (scalar phase 0, or 5)."""
+    s, S, A = self.s, _Scalars, self.A
+    if self.det is not None:
+      sums = self.det.wave_sums
+      Ap = A.apply_layered_with_dot(self.p, sums, per_wave=True)
+      _ops.cg_scalars_n(s.t, 5, self.maxiter, self.tol, self.atol, sums,
+                        sums.numel() - _lib.SFEM_FOLD_GROUPS)
+      return Ap
+    if self.fused_dot:
       Ap = (A.apply_layered_with_dot(self.p, s.partials)
             if self.layered is not None
             else A.apply_with_dot(self.p, s.partials))
-      # Without an all-reduce between the sum of the partials and alpha the
-      # iteration needs ONE scalar launch: phase 5 also closes the previous
-      # iteration (beta, gamma, counter, convergence flag) -- see `_flush`.
-      _ops.cg_scalars(s.t, 5 if merged else 3, *args)
-      if reduce_fn is not None:
-        reduce_fn(s.t[S.PAP:S.PAP + 1])
+      _ops.cg_scalars(s.t, 5 if self.merged else 3, *self._args)
+      if self.reduce_fn is not None:
+        # (p . unassembled Ap: nothing to correct on the interface)
+        self.reduce_fn(s.t[S.PAP:S.PAP + 1])
     else:
       Ap = A(self.p)
-    if self.fused_dot:
-      pass
-    elif dot_fn is None:
       # slot PAP is zero here: cleared by phase 2 / phase 1
-      for xx, yy in zip(_leaves(self.p), _leaves(Ap)):
-        _ops.dot(layout.flat(xx), layout.flat(layout.like(yy, xx)), s.t,
-                 S.PAP, accumulate=True)
-      if self.interface is not None:
-        s.interface_correction(S.PAP, self.p, Ap, self.interface)
-      if reduce_fn is not None:
-        reduce_fn(s.t[S.PAP:S.PAP + 1])
-    else:
-      s.dot_into(S.PAP, self.p, Ap, dot_fn, reduce_fn)
-    if not merged:
-      _ops.cg_scalars(s.t, 0, *args)
+      s.dot_into(S.PAP, self.p, Ap, self.dot_fn, self.reduce_fn,
+                 self.interface, cleared=True)
+    if not self.merged:
+      _ops.cg_scalars(s.t, 0, *self._args)
+    return Ap
+
+  def _update_r(self, Ap):
+    """r -= alpha Ap and gamma_new = r . M r; returns z = M r, or None when
+    M is folded into the vector updates (`mean`, `jacobi`)."""
+    s, S, M = self.s, _Scalars, self.M
     if self.mean is not None:
-      w, total, sums = self.mean
       _ops.cg_update_r_mean(layout.flat(self.r),
-                            layout.flat(layout.like(Ap, self.r)), w, s.t, sums)
-      _ops.cg_update_xp_mean(layout.flat(self._x), layout.flat(self.p),
-                             layout.flat(self.r), s.t, sums, total)
-      if not merged:
-        _ops.cg_scalars(s.t, 1, *args)
-      self.issued += 1
-      return
+                            layout.flat(layout.like(Ap, self.r)), self.mean.w,
+                            s.t, self.mean.sums)
+      return None
     if self.jacobi is not None:
-      self._jacobi_updates(Ap, merged, args)
-      return
-    if self.layered is not None and self.det is not None and self.fuse_rr:
+      self._update_r_jacobi(Ap)
+      return None
+    plan = self.layered
+    if plan is not None and self.det is not None and self.fuse_rr:
       n = _ops.cg_update_r_layered_det(
-          self.r, Ap, self.layered.layers, s.t,
-          self.det[1][:RR_PARTIALS], masks=self.layered.masks)
+          self.r, Ap, plan.layers, s.t, self.det.rr_sums[:RR_PARTIALS],
+          masks=plan.masks)
       _ops.cg_scalars_n(s.t, 8, self.maxiter, self.tol, self.atol,
-                        self.det[1], n)
-    elif self.layered is not None:
-      _ops.cg_update_r_layered(self.r, Ap, self.layered.layers, s.t,
-                               self.fuse_rr, masks=self.layered.masks)
+                        self.det.rr_sums, n)
+    elif plan is not None:
+      _ops.cg_update_r_layered(self.r, Ap, plan.layers, s.t, self.fuse_rr,
+                               masks=plan.masks)
     else:
       for rr, aa in zip(_leaves(self.r), _leaves(Ap)):
         _ops.cg_update_r(layout.flat(rr), layout.flat(layout.like(aa, rr)),
                          s.t, self.fuse_rr)
     if self.fuse_rr:
-      z = self.r
-      if self.fold_rr:
-        _ops.cg_scalars(s.t, 7, *args)
-      if self.interface is not None:
-        s.interface_correction(S.GAMMA_NEW, self.r, self.r, self.interface)
-      if reduce_fn is not None:
-        reduce_fn(s.t[S.GAMMA_NEW:S.GAMMA_NEW + 1])
+      if self.fold_rr:             # (an all-reduce or a correction follows)
+        _ops.cg_scalars(s.t, 7, *self._args)
+        s.complete(S.GAMMA_NEW, self.r, self.r, self.reduce_fn,
+                   self.interface)
+      return self.r
+    if (self.dot_fn is None and hasattr(M, 'apply_with_dot') and
+        isinstance(self.r, torch.Tensor)):
+      # the preconditioner accumulates r . M r itself (slot is zero here)
+      z = M.apply_with_dot(self.r, s.t, S.GAMMA_NEW)
+      s.complete(S.GAMMA_NEW, self.r, z, self.reduce_fn, self.interface)
     else:
-      if (dot_fn is None and hasattr(M, 'apply_with_dot') and
-          isinstance(self.r, torch.Tensor)):
-        # the preconditioner accumulates r . M r itself (slot is zero here)
-        z = M.apply_with_dot(self.r, s.t, S.GAMMA_NEW)
-        if self.interface is not None:
-          s.interface_correction(S.GAMMA_NEW, self.r, z, self.interface)
-        if reduce_fn is not None:
-          reduce_fn(s.t[S.GAMMA_NEW:S.GAMMA_NEW + 1])
-      elif dot_fn is None:
-        z = self.r if self.identity_m else M(self.r)
-        for xx, yy in zip(_leaves(self.r), _leaves(z)):
-          _ops.dot(layout.flat(xx), layout.flat(layout.like(yy, xx)), s.t,
-                   S.GAMMA_NEW, accumulate=True)
-        if self.interface is not None:
-          s.interface_correction(S.GAMMA_NEW, self.r, z, self.interface)
-        if reduce_fn is not None:
-          reduce_fn(s.t[S.GAMMA_NEW:S.GAMMA_NEW + 1])
-      else:
-        # after convergence the done flag guards every consumer of this slot
-        z = self.r if self.identity_m else M(self.r)
-        s.dot_into(S.GAMMA_NEW, self.r, z, dot_fn, reduce_fn)
-    # x += alpha p rides with the p update (p is in registers there): 8 vector
-    # passes per iteration instead of 9, same arithmetic
-    if self.lazy is not None:
-      ring, n, state = self.lazy
-      _ops.cg_update_xp_lazy(layout.flat(self._x), ring,
-                             layout.flat(layout.like(z, self.r)), s.t, state)
+      # (slot zero here too; with a `dot_fn`: after convergence the done flag
+      # guards every consumer of this slot)
+      z = self.r if self.identity_m else M(self.r)
+      s.dot_into(S.GAMMA_NEW, self.r, z, self.dot_fn, self.reduce_fn,
+                 self.interface, cleared=True)
+    return z
+
+  def _update_r_jacobi(self, Ap):
+    """r -= alpha Ap with r . (dinv r) (`sfem_cg_update_r_jacobi`)."""
+    s, plan = self.s, self.layered
+    dinv, ncomp = self.jacobi
+    if plan is None:
+      r, Ap = layout.flat(self.r), layout.flat(layout.like(Ap, self.r))
+      layers, masks = (), None
+    else:                          # (a 1-D field: ncomp = 1)
+      r, layers, masks = self.r, plan.layers, plan.masks
+    sums = (self.det.rr_sums[:RR_PARTIALS]
+            if plan is not None and self.det is not None else None)
+    n = _ops.cg_update_r_jacobi(r, Ap, dinv, s.t, ncomp, layers, masks, sums)
+    if sums is not None:
+      _ops.cg_scalars_n(s.t, 8, self.maxiter, self.tol, self.atol,
+                        self.det.rr_sums, n)
+    if self.reduce_fn is not None:
+      # the striped r . (dinv r) into [2], corrected on the interface nodes,
+      # summed over the partitions
+      _ops.cg_scalars(s.t, 7, *self._args)
+      s.complete(_Scalars.GAMMA_NEW, self.r, self.r, self.reduce_fn,
+                 self.jacobi_interface)
+
+  def _update_xp(self, z):
+    """x += alpha p and p = z + beta p in one kernel: x += alpha p rides with
+    the p update (p is in registers there), 8 vector passes per iteration
+    instead of 9, same arithmetic."""
+    s = self.s
+    if self.mean is not None:
+      _ops.cg_update_xp_mean(layout.flat(self._x), layout.flat(self.p),
+                             layout.flat(self.r), s.t, self.mean.sums,
+                             self.mean.total)
+    elif self.jacobi is not None:
+      dinv, ncomp = self.jacobi
+      _ops.cg_update_xp_jacobi(layout.flat(self._x), layout.flat(self.p),
+                               layout.flat(self.r), dinv, s.t, ncomp)
+    elif self.lazy is not None:
+      _ops.cg_update_xp_lazy(layout.flat(self._x), self.lazy.ring,
+                             layout.flat(layout.like(z, self.r)), s.t,
+                             self.lazy.state)
     else:
       for xx, pp, zz in zip(_leaves(self._x), _leaves(self.p), _leaves(z)):
         _ops.cg_update_xp(layout.flat(xx), layout.flat(pp),
                           layout.flat(layout.like(zz, pp)), s.t)
-    if not merged:
-      _ops.cg_scalars(s.t, 1, *args)
+
+  def _close(self):
+    """beta, gamma, the counter and the convergence flag (phase 1) -- unless
+    the next iteration's phase 5 does it (`merged`)."""
+    if not self.merged:
+      _ops.cg_scalars(self.s.t, 1, *self._args)
     self.issued += 1
 
-  def _jacobi_updates(self, Ap, merged, args):
-    """r -= alpha Ap with r . (dinv r), then x += alpha p, p = dinv r + beta p
-    (`sfem_cg_update_r_jacobi` / `sfem_cg_update_xp_jacobi`)."""
-    s = self.s
-    dinv, ncomp = self.jacobi
-    if self.layered is not None:
-      plan = self.layered
-      if self.det is not None:
-        n = _ops.cg_update_r_jacobi(self.r, Ap, dinv, s.t, 1, plan.layers,
-                                    plan.masks, self.det[1][:RR_PARTIALS])
-        _ops.cg_scalars_n(s.t, 8, self.maxiter, self.tol, self.atol,
-                          self.det[1], n)
-      else:
-        _ops.cg_update_r_jacobi(self.r, Ap, dinv, s.t, 1, plan.layers,
-                                plan.masks)
+  def _step_residual_stop(self):
+    """One PCG iteration that stops on r.r (see the module docstring)."""
+    s, st = self.s, self.rr_stop
+    G, parts = st.groups, st.parts
+    args = (self.maxiter, self.tol, self.atol)
+    if st.layered is not None:
+      Ap = self.A.apply_layered_with_dot(self.p, st.waves, per_wave=True)
+      _ops.pmg_cg_scalars(s.t, 0, st.waves, st.num_waves, *args)
+      _ops.cg_update_r_layered(self.r, Ap, st.layered.layers, s.t, 0,
+                               masks=st.layered.masks)
     else:
-      _ops.cg_update_r_jacobi(layout.flat(self.r),
-                              layout.flat(layout.like(Ap, self.r)), dinv, s.t,
-                              ncomp)
-    if self.reduce_fn is not None:
-      # the striped r . (dinv r) into [2], corrected on the interface nodes,
-      # summed over the partitions
-      _ops.cg_scalars(s.t, 7, *args)
-      if self.jacobi_interface is not None:
-        s.interface_correction(_Scalars.GAMMA_NEW, self.r, self.r,
-                               self.jacobi_interface)
-      self.reduce_fn(s.t[_Scalars.GAMMA_NEW:_Scalars.GAMMA_NEW + 1])
-    _ops.cg_update_xp_jacobi(layout.flat(self._x), layout.flat(self.p),
-                             layout.flat(self.r), dinv, s.t, ncomp)
-    if not merged:
-      _ops.cg_scalars(s.t, 1, *args)
+      Ap = layout.like(self.A(self.p), self.r).contiguous()
+      self._dot2(self.p, Ap, None)
+      _ops.pmg_cg_scalars(s.t, 0, parts, G, *args)
+      _ops.cg_update_r(self.r, Ap, s.t, 0)
+    z = layout.like(self.M(self.r), self.r).contiguous()
+    self._dot2(self.r, self.r, z)
+    _ops.pmg_cg_scalars(s.t, 4, parts, G, *args)
+    _ops.cg_update_xp(self._x, self.p, z, s.t)
+    _ops.pmg_cg_scalars(s.t, 1, parts, G, *args)
     self.issued += 1
 
   def capture(self) -> bool:
@@ -616,36 +693,17 @@ class CGRunner:
       self.lazy = None
     self.step()                    # warm caches / lazy setup eagerly
     torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
     issued = self.issued
-    # The cyclic collector must not run while the stream is capturing: an
-    # older solver state that sits in a reference cycle (stepper -> cache ->
-    # runner -> operator -> stepper) owns a graph and its memory pool, and
-    # freeing those in the middle of a capture aborts the process.  Collect
-    # first, then keep the collector off until the capture has ended.
-    import gc
-    gc.collect()
-    was_enabled = gc.isenabled()
-    gc.disable()
-    try:
-      with torch.cuda.graph(graph):
-        self._step_eager()
-    except Exception:              # pylint: disable=broad-except
-      torch.cuda.synchronize()
-      self.issued = issued
-      self._capture_failed = True  # (a kept runner does not try again)
-      return False
-    finally:
-      if was_enabled:
-        gc.enable()
+    self._graph = _driver.capture_graph(self._step_eager)
     self.issued = issued           # capture records, it does not execute
-    self._graph = graph
-    return True
+    if self._graph is None:
+      self._capture_failed = True  # (a kept runner does not try again)
+    return self._graph is not None
 
   def _flush(self):
     """Closes the iteration that the single-scalar-launch scheme leaves open
     (no-op otherwise), so that the scalars describe the last `step()`."""
-    if self.fused_dot and self.reduce_fn is None:
+    if self.merged:
       _ops.cg_scalars(self.s.t, 6, self.maxiter, self.tol, self.atol, None)
 
   def done(self) -> bool:
@@ -710,37 +768,20 @@ def cg(A, b, x0=None, *, tol=1e-5, atol=0.0, maxiter=None, M=None,
     return b, {'residual': 0.0, 'num_iterations': 0, 'status': 'converged'}
   reuse = (graph and workspace is not None and key is not None and
            dot_fn is None and reduce_fn is None and interface is None)
-  run = workspace.get(key) if reuse else None
-  if run is not None and run.matches(b, tol, atol, maxiter):
-    workspace[key] = workspace.pop(key)      # most recently used goes last
+  run, kept = _driver.kept_runner(
+      workspace if reuse else None, key, MAX_KEPT_RUNNERS,
+      lambda run: run.matches(b, tol, atol, maxiter),
+      lambda: CGRunner(A, b, x0, tol=tol, atol=atol, maxiter=maxiter, M=M,
+                       dot_fn=dot_fn, reduce_fn=reduce_fn,
+                       interface=interface))
+  if kept:
     run.restart(b, x0)
-  else:
-    run = CGRunner(A, b, x0, tol=tol, atol=atol, maxiter=maxiter, M=M,
-                   dot_fn=dot_fn, reduce_fn=reduce_fn, interface=interface)
-    if reuse:
-      workspace.pop(key, None)
-      workspace[key] = run
-      # (a stepper whose coefficients change every step must not collect
-      # solver states without bound: the oldest ones go)
-      while len(workspace) > MAX_KEPT_RUNNERS:
-        workspace.pop(next(iter(workspace)))
   if (graph and dot_fn is None and run.maxiter > 2 and run._graph is None and
       not run._capture_failed and not run.done()):
     run.capture()
-  while run.issued < run.maxiter:
-    for _ in range(min(check_every, run.maxiter - run.issued)):
-      run.step()
-    if run.done():
-      break
+  _driver.drive(run, check_every)
   info = run.info()
-  if info['status'].startswith('breakdown'):
-    # the reference would have returned this as a converged solve; callers
-    # that ignore `info` (the Stokes solves) at least get told
-    import warnings
-    warnings.warn(f"cg stopped with status '{info['status']}' after "
-                  f"{info['num_iterations']} iterations: x is the last "
-                  'iterate, not a solution to the requested tolerance',
-                  RuntimeWarning, stacklevel=2)
+  _driver.warn_on_breakdown('cg', info)
   # (a kept runner overwrites its x in the next solve)
   return (_map(lambda t: t.clone(), run.x) if reuse else run.x), info
 

@@ -20,11 +20,10 @@ sums added in a fixed order -- no atomics, nothing to clear).
 
 from __future__ import annotations
 
-import gc
-
 import torch
 
 from swirl_fem_amd import _lib, _ops, switches
+from swirl_fem_amd.linalg import _driver
 
 MAX_KEPT_RUNNERS = 8
 
@@ -135,25 +134,12 @@ class EnsembleCGRunner:
       return True
     self._iterate()                # warm caches eagerly
     torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
     issued = self.issued
-    gc.collect()
-    was_enabled = gc.isenabled()
-    gc.disable()
-    try:
-      with torch.cuda.graph(graph):
-        self._iterate()
-    except Exception:              # pylint: disable=broad-except
-      torch.cuda.synchronize()
-      self.issued = issued
+    self._graph = _driver.capture_graph(self._iterate)
+    self.issued = issued           # capture records, it does not execute
+    if self._graph is None:
       self._capture_failed = True
-      return False
-    finally:
-      if was_enabled:
-        gc.enable()
-    self.issued = issued
-    self._graph = graph
-    return True
+    return self._graph is not None
 
   def done(self) -> bool:
     """Synchronising poll: have all members stopped?"""
@@ -187,33 +173,19 @@ def cg_ensemble(A, b, members, x0=None, *, tol=1e-5, atol=0.0, maxiter=None,
     info['residual'] is the (B,) tensor of final r.M r.
   """
   reuse = graph and workspace is not None and key is not None
-  run = workspace.get(key) if reuse else None
-  if run is not None and run.matches(b, members, tol, atol, maxiter):
-    workspace[key] = workspace.pop(key)
+  run, kept = _driver.kept_runner(
+      workspace if reuse else None, key, MAX_KEPT_RUNNERS,
+      lambda run: run.matches(b, members, tol, atol, maxiter),
+      lambda: EnsembleCGRunner(A, b, members, x0, tol=tol, atol=atol,
+                               maxiter=maxiter, M=M))
+  if kept:
     run.restart(b, x0)
-  else:
-    run = EnsembleCGRunner(A, b, members, x0, tol=tol, atol=atol,
-                           maxiter=maxiter, M=M)
-    if reuse:
-      workspace.pop(key, None)
-      workspace[key] = run
-      while len(workspace) > MAX_KEPT_RUNNERS:
-        workspace.pop(next(iter(workspace)))
   if (graph and run.maxiter > 2 and run._graph is None and
       not run._capture_failed and not run.done()):
     run.capture()
-  while run.issued < run.maxiter:
-    for _ in range(min(check_every, run.maxiter - run.issued)):
-      run.step()
-    if run.done():
-      break
+  _driver.drive(run, check_every)
   info = run.info()
-  if info['status'].startswith('breakdown'):
-    import warnings
-    warnings.warn(f"cg_ensemble: a member stopped with status "
-                  f"'{info['status']}': its x is the last iterate, not a "
-                  'solution to the requested tolerance', RuntimeWarning,
-                  stacklevel=2)
+  _driver.warn_on_breakdown('cg_ensemble', info)
   return (run.x.clone() if reuse else run.x), info
 
 

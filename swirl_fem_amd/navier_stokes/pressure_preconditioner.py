@@ -41,6 +41,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from swirl_fem_amd.linalg import _driver
 from swirl_fem_amd.navier_stokes import navier_stokes as ns
 
 
@@ -433,21 +434,11 @@ class SchwarzPressurePreconditioner:
       for _ in range(2):                         # warm-up outside the capture
         self._coarse_iterate(self._coarse_in)
       torch.cuda.synchronize()
-      graph = torch.cuda.CUDAGraph()
-      import gc                  # (no collection inside a capture: cg.capture)
-      gc.collect()
-      was_enabled = gc.isenabled()
-      gc.disable()
-      try:
-        with torch.cuda.graph(graph):
-          self._coarse_out = self._coarse_iterate(self._coarse_in)
-        self._coarse_graph = graph
-      except Exception:                  # pylint: disable=broad-except
-        torch.cuda.synchronize()
-        self._coarse_graph = False
-      finally:
-        if was_enabled:
-          gc.enable()
+
+      def record():
+        self._coarse_out = self._coarse_iterate(self._coarse_in)
+      # (False: the capture failed, the solve stays eager)
+      self._coarse_graph = _driver.capture_graph(record) or False
     if self._coarse_graph is False:
       return self._coarse_iterate(b)
     self._coarse_in.copy_(b)

@@ -344,7 +344,7 @@ def test_reproducible_and_graph_captured():
   assert i3['num_iterations'] == i1['num_iterations']
   assert torch.equal(x1, x3)
   run = CGRunner(A, b, tol=1e-10, M=M)
-  assert run.rr_stop is not None and run.rr_stop['layered'] is not None
+  assert run.rr_stop is not None and run.rr_stop.layered is not None
 
 
 def test_refusals():
