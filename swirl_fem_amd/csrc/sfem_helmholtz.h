@@ -35,7 +35,7 @@
 //     and the kernel is HBM-bound at ~20 % VALU occupancy, so the contractions
 //     stay on the vector ALU.
 #pragma once
-#include "sfem_common.h"
+#include "sfem_launch.h"
 
 #ifndef SFEM_DMAT_MEM
 #define SFEM_DMAT_MEM 1
@@ -390,8 +390,6 @@ __device__ __forceinline__ void line_apply_pk(const DMat<float, P>& dm,
 //                    constant times the tensor quadrature weight
 // A mesh that mixes the three kinds is processed by up to three launches, each
 // over its own element list (`elem_list`), so every kernel stays specialised.
-enum GeoMode { GEO_POINT = 0, GEO_AFFINE = 1, GEO_MULTILINEAR = 3 };
-
 // w / d for the per-point geometric factors: hardware reciprocal estimate + two
 // Newton steps (5 instructions) instead of the IEEE division sequence (~14 for
 // fp64: v_div_scale x2, v_rcp, 6 fma, v_div_fmas, v_div_fixup).  Relative error
@@ -884,6 +882,49 @@ __device__ __forceinline__ void scatter_shared_sorted(
   }
 }
 
+// Where a lane of an element kernel stands (every kernel on HelmholtzTile):
+// lane t = (i, j) of element `el` of the workgroup owns the nodes (*, i, j);
+// `e` is the element's id and s0 / s1 its pair of LDS tensors.  Expects TPE,
+// EPB, W and `lds` in scope; PRM_ has num_elements and elem_list.  A macro and
+// not a struct: the register allocation of the kernels must not move.
+#define SFEM_LANE_PROLOGUE(PRM_)                                              \
+  const int tid = threadIdx.x;                                                \
+  const int el = tid / TPE;       /* element within the workgroup */          \
+  const int t = tid - el * TPE;   /* lane within the element */               \
+  const int i = DIM == 3 ? t / P : 0;                                         \
+  const int j = DIM == 3 ? t - i * P : t;                                     \
+  const bool lane_ok = el < EPB;  /* tail lanes of a padded block */          \
+  const int64_t work = (int64_t)blockIdx.x * EPB + (lane_ok ? el : 0);        \
+  const bool active = lane_ok && work < (PRM_).num_elements;                  \
+  /* element id: wave-uniform when an element fills whole waves */            \
+  const int64_t e = (PRM_).elem_list                                          \
+                        ? (active ? (int64_t)(PRM_).elem_list[work] : 0)      \
+                        : work;                                               \
+  T* s0 = lds + (lane_ok ? el : 0) * 2 * W;  /* becomes the axis-1 result */  \
+  T* s1 = s0 + W;                            /* becomes the axis-2 result */  \
+  (void)s1
+
+// y = D x (TR: D^T x) inside a kernel whose first argument is a PRM_ and whose
+// second is the DMat `dmat`.  fp32, P >= 9: matrix entries from the kernarg
+// segment (line_apply_mem; measured p = 11 fp32 1.02 -> 0.99 ms at 48^3,
+// p = 9 fp64 0.83 -> 0.85 ms); sizeof(PRM_) is the matrix's offset there.
+#if SFEM_DMAT_MEM
+#define SFEM_LINE_APPLY(PRM_, TR, X, Y)                                       \
+  do {                                                                        \
+    if constexpr (P >= 9 && sizeof(T) == 4)                                   \
+      line_apply_mem<T, P, TR>(                                               \
+          (const SFEM_CONSTANT_AS DMat<T, P>*)((                              \
+              const SFEM_CONSTANT_AS char*)                                   \
+                  __builtin_amdgcn_kernarg_segment_ptr() +                    \
+              sizeof(PRM_)),                                                  \
+          X, Y);                                                              \
+    else                                                                      \
+      line_apply<T, P, TR>(dmat, X, Y);                                       \
+  } while (0)
+#else
+#define SFEM_LINE_APPLY(PRM_, TR, X, Y) line_apply<T, P, TR>(dmat, X, Y)
+#endif
+
 // SORTED: the sorted shared scatter below, its own instantiation (compiled
 // together with the slot-order scatter it cost registers in both).
 // MASS: lambda0 != 0 (decided at launch).  The pure stiffness kernels carry no
@@ -912,39 +953,8 @@ helmholtz_kernel(typename HelmholtzPrm<T, COEF>::type prm, DMat<T, P> dm) {
   constexpr int N = DIM == 3 ? P * P * P : P * P;        // nodes per element
   __shared__ T lds[2 * EPB * W];
 
-  const int tid = threadIdx.x;
-  const int el = tid / TPE;                 // element within the workgroup
-  const int t = tid - el * TPE;             // lane within the element
-  const int i = DIM == 3 ? t / P : 0;
-  const int j = DIM == 3 ? t - i * P : t;
-  const bool lane_ok = el < EPB;            // tail lanes of a padded block
-  const int64_t work = (int64_t)blockIdx.x * EPB + (lane_ok ? el : 0);
-  const bool active = lane_ok && work < prm.num_elements;
-  // element id: wave-uniform when an element fills whole waves
-  const int64_t e =
-      prm.elem_list ? (active ? (int64_t)prm.elem_list[work] : 0) : work;
-
-  T* s0 = lds + (lane_ok ? el : 0) * 2 * W;    // becomes the axis-1 result
-  T* s1 = s0 + W;                              // becomes the axis-2 result
+  SFEM_LANE_PROLOGUE(prm);
   const DMat<T, P>& dmat = dm;
-  // fp32, P >= 9: matrix entries from the kernarg segment (line_apply_mem;
-  // measured p = 11 fp32 1.02 -> 0.99 ms at 48^3, p = 9 fp64 0.83 -> 0.85 ms)
-#if SFEM_DMAT_MEM
-#define SFEM_LINE_APPLY(TR, X, Y)                                             \
-  do {                                                                        \
-    if constexpr (P >= 9 && sizeof(T) == 4)                                   \
-      line_apply_mem<T, P, TR>(                                               \
-          (const SFEM_CONSTANT_AS DMat<T, P>*)((                              \
-              const SFEM_CONSTANT_AS char*)                                   \
-                  __builtin_amdgcn_kernarg_segment_ptr() +                    \
-              sizeof(PRM)),                                                   \
-          X, Y);                                                              \
-    else                                                                      \
-      line_apply<T, P, TR>(dmat, X, Y);                                       \
-  } while (0)
-#else
-#define SFEM_LINE_APPLY(TR, X, Y) line_apply<T, P, TR>(dmat, X, Y)
-#endif
   // SCALAR: one component known at compile time (no component loop, so the
   // compiler has nothing to hoist out of it and spill)
   const int nc = SCALAR ? 1 : prm.ncomp;
@@ -1037,7 +1047,7 @@ helmholtz_kernel(typename HelmholtzPrm<T, COEF>::type prm, DMat<T, P> dm) {
     }
     if (has_stiff) {
       T d0[P];   // derivative along axis 0 at (a, i, j)
-      SFEM_LINE_APPLY(false, ua, d0);
+      SFEM_LINE_APPLY(PRM, false, ua, d0);
       if (lane_ok) {
 #pragma unroll
         for (int a = 0; a < P; ++a) {
@@ -1051,7 +1061,7 @@ helmholtz_kernel(typename HelmholtzPrm<T, COEF>::type prm, DMat<T, P> dm) {
         T x[P], y[P];
 #pragma unroll
         for (int m = 0; m < P; ++m) x[m] = line[m];
-        SFEM_LINE_APPLY(false, x, y);
+        SFEM_LINE_APPLY(PRM, false, x, y);
 #pragma unroll
         for (int m = 0; m < P; ++m) line[m] = y[m];
       }
@@ -1060,7 +1070,7 @@ helmholtz_kernel(typename HelmholtzPrm<T, COEF>::type prm, DMat<T, P> dm) {
         T x[P], y[P];
 #pragma unroll
         for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-        SFEM_LINE_APPLY(false, x, y);
+        SFEM_LINE_APPLY(PRM, false, x, y);
 #pragma unroll
         for (int m = 0; m < P; ++m) line[m * SB] = y[m];
       }
@@ -1115,7 +1125,7 @@ helmholtz_kernel(typename HelmholtzPrm<T, COEF>::type prm, DMat<T, P> dm) {
         T x[P], y[P];
 #pragma unroll
         for (int m = 0; m < P; ++m) x[m] = line[m];
-        SFEM_LINE_APPLY(true, x, y);
+        SFEM_LINE_APPLY(PRM, true, x, y);
 #pragma unroll
         for (int m = 0; m < P; ++m) line[m] = y[m];
       }
@@ -1124,12 +1134,12 @@ helmholtz_kernel(typename HelmholtzPrm<T, COEF>::type prm, DMat<T, P> dm) {
         T x[P], y[P];
 #pragma unroll
         for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-        SFEM_LINE_APPLY(true, x, y);
+        SFEM_LINE_APPLY(PRM, true, x, y);
 #pragma unroll
         for (int m = 0; m < P; ++m) line[m * SB] = y[m];
       }
       T dt0[P];
-      SFEM_LINE_APPLY(true, w0, dt0);
+      SFEM_LINE_APPLY(PRM, true, w0, dt0);
       __syncthreads();
       if (lane_ok) {
 #pragma unroll
@@ -1243,38 +1253,26 @@ helmholtz_kernel(typename HelmholtzPrm<T, COEF>::type prm, DMat<T, P> dm) {
   }
 }
 
+// The coefficient kernels: affine or else multilinear elements, coefficients
+// per element or else per point.
 template <typename T, int P, int DIM, bool GS>
 int launch_helmholtz_coef(const HelmholtzCoefParams<T>& prm,
                           hipStream_t stream) {
-  using Tile = HelmholtzTile<T, P, DIM>;
-  const int64_t groups = (prm.num_elements + Tile::EPB - 1) / Tile::EPB;
-  if (groups > 0x7fffffff) {
-    set_error("helmholtz: too many workgroups (%lld)", (long long)groups);
-    return SFEM_EINVAL;
-  }
-  const DMat<T, P> dm =
-      make_dmat<T, P>(prm.dmat_host, prm.weights_host, prm.nodes_host);
-  const dim3 grid((unsigned)groups), block(Tile::BLOCK);
-  const bool mass = prm.lambda0 != T(0);
-#define SFEM_LAUNCH_COEF(GMV, MASSV, CM)                                      \
-  hipLaunchKernelGGL(                                                         \
-      (helmholtz_kernel<T, P, DIM, GS, true, GMV, false, MASSV, CM>), grid,   \
-      block, 0, stream, prm, dm)
-#define SFEM_LAUNCH_COEF_GM(GMV, CM)                                          \
-  do {                                                                        \
-    if (mass) SFEM_LAUNCH_COEF(GMV, true, CM);                                \
-    else SFEM_LAUNCH_COEF(GMV, false, CM);                                    \
-  } while (0)
-  if (prm.geo_mode == GEO_AFFINE) {
-    if (prm.coef_mode == COEF_ELEM) SFEM_LAUNCH_COEF_GM(GEO_AFFINE, COEF_ELEM);
-    else SFEM_LAUNCH_COEF_GM(GEO_AFFINE, COEF_POINT);
-  } else {
-    if (prm.coef_mode == COEF_ELEM)
-      SFEM_LAUNCH_COEF_GM(GEO_MULTILINEAR, COEF_ELEM);
-    else SFEM_LAUNCH_COEF_GM(GEO_MULTILINEAR, COEF_POINT);
-  }
-#undef SFEM_LAUNCH_COEF_GM
-#undef SFEM_LAUNCH_COEF
+  ElementLaunch<T, P> L;
+  if (int rc = element_launch<HelmholtzTile<T, P, DIM>>("helmholtz", prm, &L))
+    return rc;
+  with_flag(prm.geo_mode == GEO_AFFINE, [&](auto affine) {
+    with_flag(prm.coef_mode == COEF_ELEM, [&](auto per_elem) {
+      with_flag(prm.lambda0 != T(0), [&](auto mass) {
+        constexpr int GM =
+            decltype(affine)::value ? GEO_AFFINE : GEO_MULTILINEAR;
+        constexpr int CM = decltype(per_elem)::value ? COEF_ELEM : COEF_POINT;
+        hipLaunchKernelGGL((helmholtz_kernel<T, P, DIM, GS, true, GM, false,
+                                             decltype(mass)::value, CM>),
+                           L.grid, L.block, 0, stream, prm, L.dm);
+      });
+    });
+  });
   SFEM_LAUNCH_CHECK();
   return SFEM_OK;
 }
@@ -1282,54 +1280,34 @@ int launch_helmholtz_coef(const HelmholtzCoefParams<T>& prm,
 template <typename T, int P, int DIM, bool GS>
 int launch_helmholtz(const HelmholtzParams<T>& prm, hipStream_t stream) {
   using Tile = HelmholtzTile<T, P, DIM>;
-  const int64_t groups = (prm.num_elements + Tile::EPB - 1) / Tile::EPB;
-  if (groups > 0x7fffffff) {
-    set_error("helmholtz: too many workgroups (%lld)", (long long)groups);
-    return SFEM_EINVAL;
-  }
-  const DMat<T, P> dm =
-      make_dmat<T, P>(prm.dmat_host, prm.weights_host, prm.nodes_host);
-  const dim3 grid((unsigned)groups), block(Tile::BLOCK);
+  ElementLaunch<T, P> L;
+  if (int rc = element_launch<Tile>("helmholtz", prm, &L)) return rc;
   // One-wave elements in 3D can issue their atomics in node order.  Not the
   // multilinear kernels WITH a mass term: they sit at the 128-VGPR budget of
   // 4 waves per SIMD and the sorted path spills (1.09 vs 1.04 ms; 1.13 ms
   // with 3 waves).
   constexpr bool CAN_SORT = GS && DIM == 3 && Tile::TPE <= 64;
   const bool sorted = CAN_SORT && prm.shared_order && !prm.colored;
-  const bool mass = prm.lambda0 != T(0);
-#define SFEM_LAUNCH_SM(SC, GMV, PRM, MASSV)                                   \
-  do {                                                                        \
-    constexpr bool SORT_GM =                                                  \
-        CAN_SORT && (GMV != GEO_MULTILINEAR || !(MASSV));                     \
-    if (sorted && SORT_GM)                                                    \
-      hipLaunchKernelGGL(                                                     \
-          (helmholtz_kernel<T, P, DIM, GS, SC, GMV, SORT_GM, MASSV>), grid,   \
-          block, 0, stream, PRM, dm);                                         \
-    else                                                                      \
-      hipLaunchKernelGGL(                                                     \
-          (helmholtz_kernel<T, P, DIM, GS, SC, GMV, false, MASSV>), grid,     \
-          block, 0, stream, PRM, dm);                                         \
-  } while (0)
-#define SFEM_LAUNCH_GM(SC, GMV, PRM)                                          \
-  do {                                                                        \
-    if (mass) SFEM_LAUNCH_SM(SC, GMV, PRM, true);                             \
-    else SFEM_LAUNCH_SM(SC, GMV, PRM, false);                                 \
-  } while (0)
-  if (prm.ncomp == 1) {
-    switch (prm.geo_mode) {
-      case GEO_POINT: SFEM_LAUNCH_GM(true, GEO_POINT, prm); break;
-      case GEO_AFFINE: SFEM_LAUNCH_GM(true, GEO_AFFINE, prm); break;
-      default: SFEM_LAUNCH_GM(true, GEO_MULTILINEAR, prm); break;
-    }
-  } else if (prm.geo_mode == GEO_POINT) {
-    SFEM_LAUNCH_GM(false, GEO_POINT, prm);     // factors read once per element
-  } else if (prm.geo_mode == GEO_AFFINE) {
-    SFEM_LAUNCH_GM(false, GEO_AFFINE, prm);
-  } else {
-    SFEM_LAUNCH_GM(false, GEO_MULTILINEAR, prm);
-  }
-#undef SFEM_LAUNCH_GM
-#undef SFEM_LAUNCH_SM
+  // (vector fields: the factors are read once per element)
+  with_flag(prm.ncomp == 1, [&](auto scalar) {
+    with_geo_mode(prm.geo_mode, [&](auto gm) {
+      with_flag(prm.lambda0 != T(0), [&](auto mass) {
+        constexpr bool SC = decltype(scalar)::value;
+        constexpr bool MASSV = decltype(mass)::value;
+        constexpr int GMV = decltype(gm)::value;
+        constexpr bool SORT_GM =
+            CAN_SORT && (GMV != GEO_MULTILINEAR || !(MASSV));
+        if (sorted && SORT_GM)
+          hipLaunchKernelGGL(
+              (helmholtz_kernel<T, P, DIM, GS, SC, GMV, SORT_GM, MASSV>),
+              L.grid, L.block, 0, stream, prm, L.dm);
+        else
+          hipLaunchKernelGGL(
+              (helmholtz_kernel<T, P, DIM, GS, SC, GMV, false, MASSV>),
+              L.grid, L.block, 0, stream, prm, L.dm);
+      });
+    });
+  });
   SFEM_LAUNCH_CHECK();
   return SFEM_OK;
 }
@@ -1344,51 +1322,29 @@ template <typename T, int DIM>
 int dispatch_helmholtz_coef(const HelmholtzCoefParams<T>& prm, int P, bool gs,
                             hipStream_t stream);
 
-#define SFEM_HELMHOLTZ_COEF_CASE(PP)                                        \
-  case PP:                                                                  \
-    return gs ? launch_helmholtz_coef<T, PP, DIM, true>(prm, stream)        \
-              : launch_helmholtz_coef<T, PP, DIM, false>(prm, stream);
-
 #define SFEM_DEFINE_HELMHOLTZ_COEF_DISPATCH(TYPE, DIMV)                     \
   template <>                                                               \
   int dispatch_helmholtz_coef<TYPE, DIMV>(                                  \
       const HelmholtzCoefParams<TYPE>& prm, int P, bool gs,                 \
       hipStream_t stream) {                                                 \
-    using T = TYPE;                                                         \
-    constexpr int DIM = DIMV;                                               \
-    switch (P) {                                                            \
-      SFEM_HELMHOLTZ_COEF_CASE(2) SFEM_HELMHOLTZ_COEF_CASE(3)               \
-      SFEM_HELMHOLTZ_COEF_CASE(4) SFEM_HELMHOLTZ_COEF_CASE(5)               \
-      SFEM_HELMHOLTZ_COEF_CASE(6) SFEM_HELMHOLTZ_COEF_CASE(7)               \
-      SFEM_HELMHOLTZ_COEF_CASE(8) SFEM_HELMHOLTZ_COEF_CASE(9)               \
-      SFEM_HELMHOLTZ_COEF_CASE(10) SFEM_HELMHOLTZ_COEF_CASE(11)             \
-      SFEM_HELMHOLTZ_COEF_CASE(12)                                          \
-      default:                                                              \
-        set_error("helmholtz: P=%d outside the compiled range 2..12", P);   \
-        return SFEM_EUNSUPPORTED;                                           \
-    }                                                                       \
+    return with_order<2, 12>("helmholtz", P, [&](auto p) {                  \
+      return with_flag(gs, [&](auto g) {                                    \
+        return launch_helmholtz_coef<TYPE, decltype(p)::value, DIMV,        \
+                                     decltype(g)::value>(prm, stream);      \
+      });                                                                   \
+    });                                                                     \
   }
-
-#define SFEM_HELMHOLTZ_CASE(PP)                                             \
-  case PP:                                                                  \
-    return gs ? launch_helmholtz<T, PP, DIM, true>(prm, stream)             \
-              : launch_helmholtz<T, PP, DIM, false>(prm, stream);
 
 #define SFEM_DEFINE_HELMHOLTZ_DISPATCH(TYPE, DIMV)                          \
   template <>                                                               \
   int dispatch_helmholtz<TYPE, DIMV>(const HelmholtzParams<TYPE>& prm,      \
                                      int P, bool gs, hipStream_t stream) {  \
-    using T = TYPE;                                                         \
-    constexpr int DIM = DIMV;                                               \
-    switch (P) {                                                            \
-      SFEM_HELMHOLTZ_CASE(2) SFEM_HELMHOLTZ_CASE(3) SFEM_HELMHOLTZ_CASE(4)  \
-      SFEM_HELMHOLTZ_CASE(5) SFEM_HELMHOLTZ_CASE(6) SFEM_HELMHOLTZ_CASE(7)  \
-      SFEM_HELMHOLTZ_CASE(8) SFEM_HELMHOLTZ_CASE(9) SFEM_HELMHOLTZ_CASE(10) \
-      SFEM_HELMHOLTZ_CASE(11) SFEM_HELMHOLTZ_CASE(12)                       \
-      default:                                                              \
-        set_error("helmholtz: P=%d outside the compiled range 2..12", P);   \
-        return SFEM_EUNSUPPORTED;                                           \
-    }                                                                       \
+    return with_order<2, 12>("helmholtz", P, [&](auto p) {                  \
+      return with_flag(gs, [&](auto g) {                                    \
+        return launch_helmholtz<TYPE, decltype(p)::value, DIMV,             \
+                                decltype(g)::value>(prm, stream);           \
+      });                                                                   \
+    });                                                                     \
   }
 
 }  // namespace sfem

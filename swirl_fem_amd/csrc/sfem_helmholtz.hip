@@ -281,9 +281,10 @@ static int run_helmholtz(const HelmholtzCall& c, hipStream_t stream) {
     ap.sigma = (const T*)c.sigma;
     ap.beta = (const T*)c.beta;
     const bool tr = c.adv_transpose != 0;
-    if (c.ndim == 3)
-      return dispatch_helmholtz_adv<T, 3>(ap, c.P, c.gs, tr, stream);
-    return dispatch_helmholtz_adv<T, 2>(ap, c.P, c.gs, tr, stream);
+    return with_dim(c.ndim, [&](auto d) {
+      return dispatch_helmholtz_adv<T, decltype(d)::value>(ap, c.P, c.gs, tr,
+                                                           stream);
+    });
   }
   if (c.coef_mode != COEF_NONE) {
     HelmholtzCoefParams<T> cp{};
@@ -291,8 +292,10 @@ static int run_helmholtz(const HelmholtzCall& c, hipStream_t stream) {
     cp.kappa = (const T*)c.kappa;
     cp.sigma = (const T*)c.sigma;
     cp.coef_mode = c.coef_mode;
-    if (c.ndim == 3) return dispatch_helmholtz_coef<T, 3>(cp, c.P, c.gs, stream);
-    return dispatch_helmholtz_coef<T, 2>(cp, c.P, c.gs, stream);
+    return with_dim(c.ndim, [&](auto d) {
+      return dispatch_helmholtz_coef<T, decltype(d)::value>(cp, c.P, c.gs,
+                                                            stream);
+    });
   }
   if (c.cluster_elems) {
     ClusterParams<T> cl{c.cluster_elems, c.cluster_offsets, c.cluster_nodes,
@@ -397,23 +400,6 @@ static int check_advection(const char* who, const sfem_helmholtz_args* a) {
   if (why) {
     set_error("%s: the advective term (beta) does not take %s", who, why);
     return SFEM_EUNSUPPORTED;
-  }
-  return SFEM_OK;
-}
-
-static int check_geometry(const char* who, int geo_mode, const void* geo,
-                          const void* geo_elem, const void* weights,
-                          const void* nodes) {
-  if (geo_mode == SFEM_GEO_POINT) {
-    SFEM_REQUIRE(geo, "%s: per-point geometry needs `geo`", who);
-  } else if (geo_mode == SFEM_GEO_AFFINE || geo_mode == SFEM_GEO_MULTILINEAR ||
-             geo_mode == SFEM_GEO_BOX) {
-    SFEM_REQUIRE(geo_elem && weights && nodes,
-                 "%s: on-the-fly geometry needs geo_elem, weights and nodes",
-                 who);
-  } else {
-    set_error("%s: unknown geo_mode %d", who, geo_mode);
-    return SFEM_EINVAL;
   }
   return SFEM_OK;
 }
@@ -531,16 +517,17 @@ int sfem_helmholtz_apply(const sfem_helmholtz_args* a, sfem_stream_t stream) {
                "sfem_helmholtz_apply: null pointer");
   SFEM_REQUIRE(a->geo_mode != SFEM_GEO_BOX || a->facet_table,
                "sfem_helmholtz_apply: SFEM_GEO_BOX needs a facet table");
-  int rc = check_geometry("sfem_helmholtz_apply", a->geo_mode, a->geo,
+  int rc = check_geometry("sfem_helmholtz_apply", a->geo_mode, a->geo, "geo",
                           a->geo_elem, a->weights, a->nodes);
   if (rc) return rc;
   rc = check_advection("sfem_helmholtz_apply", a);
   if (rc) return rc;
   rc = check_coefficients("sfem_helmholtz_apply", a);
   if (rc) return rc;
-  const int64_t work = a->elem_list ? a->num_listed : a->num_elements;
-  SFEM_REQUIRE(work >= 0 && work <= a->num_elements,
-               "sfem_helmholtz_apply: bad element list length");
+  int64_t work;
+  rc = check_elem_list("sfem_helmholtz_apply", a->elem_list, a->num_listed,
+                       a->num_elements, &work);
+  if (rc) return rc;
   if (work == 0) return SFEM_OK;
   HelmholtzCall c{a->u, a->out, a->enc, a->geo, a->geo_elem, a->geo_index,
                   a->elem_list, a->dmat, a->weights, a->nodes, work, a->ndim,
@@ -611,8 +598,9 @@ int sfem_helmholtz_apply(const sfem_helmholtz_args* a, sfem_stream_t stream) {
   }
   SFEM_REQUIRE(!a->layered_extent || a->facet_table,
                "sfem_helmholtz_apply: layered assembly needs a facet table");
-  if (a->dtype == SFEM_F64) return run_helmholtz<double>(c, as_stream(stream));
-  return run_helmholtz<float>(c, as_stream(stream));
+  return with_real(a->dtype, [&](auto zero) {
+    return run_helmholtz<decltype(zero)>(c, as_stream(stream));
+  });
 }
 
 int sfem_kernarg_selftest(int32_t* bad, sfem_stream_t stream) {
@@ -720,16 +708,17 @@ int sfem_helmholtz_local(const sfem_helmholtz_args* a, sfem_stream_t stream) {
                "sfem_helmholtz_local: unknown dtype %d", a->dtype);
   if (a->num_elements == 0) return SFEM_OK;
   SFEM_REQUIRE(a->u && a->out && a->dmat, "sfem_helmholtz_local: null pointer");
-  int rc = check_geometry("sfem_helmholtz_local", a->geo_mode, a->geo,
+  int rc = check_geometry("sfem_helmholtz_local", a->geo_mode, a->geo, "geo",
                           a->geo_elem, a->weights, a->nodes);
   if (rc) return rc;
   rc = check_advection("sfem_helmholtz_local", a);
   if (rc) return rc;
   rc = check_coefficients("sfem_helmholtz_local", a);
   if (rc) return rc;
-  const int64_t work = a->elem_list ? a->num_listed : a->num_elements;
-  SFEM_REQUIRE(work >= 0 && work <= a->num_elements,
-               "sfem_helmholtz_local: bad element list length");
+  int64_t work;
+  rc = check_elem_list("sfem_helmholtz_local", a->elem_list, a->num_listed,
+                       a->num_elements, &work);
+  if (rc) return rc;
   if (work == 0) return SFEM_OK;
   HelmholtzCall c{a->u, a->out, nullptr, a->geo, a->geo_elem, a->geo_index,
                   a->elem_list, a->dmat, a->weights, a->nodes, work, a->ndim,
@@ -740,8 +729,9 @@ int sfem_helmholtz_local(const sfem_helmholtz_args* a, sfem_stream_t stream) {
   c.coef_mode = a->coef_mode;
   c.beta = a->beta;
   c.adv_transpose = a->adv_transpose;
-  if (a->dtype == SFEM_F64) return run_helmholtz<double>(c, as_stream(stream));
-  return run_helmholtz<float>(c, as_stream(stream));
+  return with_real(a->dtype, [&](auto zero) {
+    return run_helmholtz<decltype(zero)>(c, as_stream(stream));
+  });
 }
 
 int sfem_helmholtz_sens(const sfem_helmholtz_sens_args* a,
@@ -749,39 +739,31 @@ int sfem_helmholtz_sens(const sfem_helmholtz_sens_args* a,
   SFEM_REQUIRE(a, "sfem_helmholtz_sens: null args");
   SFEM_REQUIRE(a->num_elements >= 0 && a->ncomp >= 1,
                "sfem_helmholtz_sens: bad sizes");
-  SFEM_REQUIRE(a->dtype == SFEM_F32 || a->dtype == SFEM_F64,
-               "sfem_helmholtz_sens: unknown dtype %d", a->dtype);
+  int rc = check_shape("sfem_helmholtz_sens", a->dtype, a->ndim, "P", a->P, 2,
+                       12);
+  if (rc) return rc;
   if (a->ncomp != 1) {
     set_error("sfem_helmholtz_sens: takes scalar fields (ncomp = %d)",
               a->ncomp);
-    return SFEM_EUNSUPPORTED;
-  }
-  if (a->ndim != 2 && a->ndim != 3) {
-    set_error("sfem_helmholtz_sens: ndim=%d (the kernel supports 2 and 3)",
-              a->ndim);
-    return SFEM_EUNSUPPORTED;
-  }
-  if (a->P < 2 || a->P > 12) {
-    set_error("sfem_helmholtz_sens: P=%d outside the compiled range 2..12",
-              a->P);
     return SFEM_EUNSUPPORTED;
   }
   if (a->num_elements == 0) return SFEM_OK;
   SFEM_REQUIRE(a->u && a->lam && a->dmat,
                "sfem_helmholtz_sens: null pointer");
   if (!a->dkappa && !a->dsigma && !a->dbeta) return SFEM_OK;
-  int rc = check_geometry("sfem_helmholtz_sens", a->geo_mode, a->geo,
+  rc = check_geometry("sfem_helmholtz_sens", a->geo_mode, a->geo, "geo",
                           a->geo_elem, a->weights, a->nodes);
   if (rc) return rc;
   if (a->geo_mode == SFEM_GEO_BOX) {
     set_error("sfem_helmholtz_sens: does not take SFEM_GEO_BOX");
     return SFEM_EUNSUPPORTED;
   }
-  const int64_t work = a->elem_list ? a->num_listed : a->num_elements;
-  SFEM_REQUIRE(work >= 0 && work <= a->num_elements,
-               "sfem_helmholtz_sens: bad element list length");
+  int64_t work;
+  rc = check_elem_list("sfem_helmholtz_sens", a->elem_list, a->num_listed,
+                       a->num_elements, &work);
+  if (rc) return rc;
   if (work == 0) return SFEM_OK;
-  auto run = [&](auto zero) -> int {
+  return with_real(a->dtype, [&](auto zero) {
     using T = decltype(zero);
     HelmholtzSensParams<T> prm{};
     prm.u = (const T*)a->u; prm.lam = (const T*)a->lam;
@@ -794,12 +776,11 @@ int sfem_helmholtz_sens(const sfem_helmholtz_sens_args* a,
     prm.elem_list = a->elem_list; prm.ncomp = 1; prm.node_stride = 1;
     prm.comp_stride = 1; prm.lambda0 = (T)a->lambda0;
     prm.lambda1 = (T)a->lambda1;
-    if (a->ndim == 3)
-      return dispatch_helmholtz_sens<T, 3>(prm, a->P, as_stream(stream));
-    return dispatch_helmholtz_sens<T, 2>(prm, a->P, as_stream(stream));
-  };
-  if (a->dtype == SFEM_F64) return run(double(0));
-  return run(float(0));
+    return with_dim(a->ndim, [&](auto d) {
+      return dispatch_helmholtz_sens<T, decltype(d)::value>(prm, a->P,
+                                                            as_stream(stream));
+    });
+  });
 }
 
 }  // extern "C"

@@ -56,37 +56,8 @@ helmholtz_adv_kernel(HelmholtzAdvParams<T> prm, DMat<T, P> dm) {
   constexpr int N = DIM == 3 ? P * P * P : P * P;        // nodes per element
   __shared__ T lds[2 * EPB * W];
 
-  const int tid = threadIdx.x;
-  const int el = tid / TPE;                 // element within the workgroup
-  const int t = tid - el * TPE;             // lane within the element
-  const int i = DIM == 3 ? t / P : 0;
-  const int j = DIM == 3 ? t - i * P : t;
-  const bool lane_ok = el < EPB;            // tail lanes of a padded block
-  const int64_t work = (int64_t)blockIdx.x * EPB + (lane_ok ? el : 0);
-  const bool active = lane_ok && work < prm.num_elements;
-  const int64_t e =
-      prm.elem_list ? (active ? (int64_t)prm.elem_list[work] : 0) : work;
-
-  T* s0 = lds + (lane_ok ? el : 0) * 2 * W;    // becomes the axis-1 result
-  T* s1 = s0 + W;                              // becomes the axis-2 result
+  SFEM_LANE_PROLOGUE(prm);
   const DMat<T, P>& dmat = dm;
-  // fp32, P >= 9: matrix entries from the kernarg segment, as the parent does
-#if SFEM_DMAT_MEM
-#define SFEM_ADV_LINE_APPLY(TR, X, Y)                                         \
-  do {                                                                        \
-    if constexpr (P >= 9 && sizeof(T) == 4)                                   \
-      line_apply_mem<T, P, TR>(                                               \
-          (const SFEM_CONSTANT_AS DMat<T, P>*)((                              \
-              const SFEM_CONSTANT_AS char*)                                   \
-                  __builtin_amdgcn_kernarg_segment_ptr() +                    \
-              sizeof(PRM)),                                                   \
-          X, Y);                                                              \
-    else                                                                      \
-      line_apply<T, P, TR>(dmat, X, Y);                                       \
-  } while (0)
-#else
-#define SFEM_ADV_LINE_APPLY(TR, X, Y) line_apply<T, P, TR>(dmat, X, Y)
-#endif
   const int64_t ns = prm.node_stride;
   const bool has_mass = prm.lambda0 != T(0);
 
@@ -132,7 +103,7 @@ helmholtz_adv_kernel(HelmholtzAdvParams<T> prm, DMat<T, P> dm) {
     }
   }
   T d0[P];   // derivative along axis 0 at (a, i, j)
-  SFEM_ADV_LINE_APPLY(false, ua, d0);
+  SFEM_LINE_APPLY(PRM, false, ua, d0);
   if (lane_ok) {
 #pragma unroll
     for (int a = 0; a < P; ++a) {
@@ -146,7 +117,7 @@ helmholtz_adv_kernel(HelmholtzAdvParams<T> prm, DMat<T, P> dm) {
     T x[P], y[P];
 #pragma unroll
     for (int m = 0; m < P; ++m) x[m] = line[m];
-    SFEM_ADV_LINE_APPLY(false, x, y);
+    SFEM_LINE_APPLY(PRM, false, x, y);
 #pragma unroll
     for (int m = 0; m < P; ++m) line[m] = y[m];
   }
@@ -155,7 +126,7 @@ helmholtz_adv_kernel(HelmholtzAdvParams<T> prm, DMat<T, P> dm) {
     T x[P], y[P];
 #pragma unroll
     for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-    SFEM_ADV_LINE_APPLY(false, x, y);
+    SFEM_LINE_APPLY(PRM, false, x, y);
 #pragma unroll
     for (int m = 0; m < P; ++m) line[m * SB] = y[m];
   }
@@ -214,7 +185,7 @@ helmholtz_adv_kernel(HelmholtzAdvParams<T> prm, DMat<T, P> dm) {
     T x[P], y[P];
 #pragma unroll
     for (int m = 0; m < P; ++m) x[m] = line[m];
-    SFEM_ADV_LINE_APPLY(true, x, y);
+    SFEM_LINE_APPLY(PRM, true, x, y);
 #pragma unroll
     for (int m = 0; m < P; ++m) line[m] = y[m];
   }
@@ -223,12 +194,12 @@ helmholtz_adv_kernel(HelmholtzAdvParams<T> prm, DMat<T, P> dm) {
     T x[P], y[P];
 #pragma unroll
     for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-    SFEM_ADV_LINE_APPLY(true, x, y);
+    SFEM_LINE_APPLY(PRM, true, x, y);
 #pragma unroll
     for (int m = 0; m < P; ++m) line[m * SB] = y[m];
   }
   T dt0[P];
-  SFEM_ADV_LINE_APPLY(true, w0, dt0);
+  SFEM_LINE_APPLY(PRM, true, w0, dt0);
   __syncthreads();
   if (lane_ok) {
 #pragma unroll
@@ -261,29 +232,18 @@ helmholtz_adv_kernel(HelmholtzAdvParams<T> prm, DMat<T, P> dm) {
       ol0[(int64_t)(slot_off + a * TPE) * ns] = acc[a];
     }
   }
-#undef SFEM_ADV_LINE_APPLY
 }
 
 template <typename T, int P, int DIM, bool GS, bool TR>
 int launch_helmholtz_adv(const HelmholtzAdvParams<T>& prm, hipStream_t stream) {
-  using Tile = HelmholtzTile<T, P, DIM>;
-  const int64_t groups = (prm.num_elements + Tile::EPB - 1) / Tile::EPB;
-  if (groups > 0x7fffffff) {
-    set_error("helmholtz: too many workgroups (%lld)", (long long)groups);
-    return SFEM_EINVAL;
-  }
-  const DMat<T, P> dm =
-      make_dmat<T, P>(prm.dmat_host, prm.weights_host, prm.nodes_host);
-  const dim3 grid((unsigned)groups), block(Tile::BLOCK);
-#define SFEM_LAUNCH_ADV(GMV)                                                  \
-  hipLaunchKernelGGL((helmholtz_adv_kernel<T, P, DIM, GS, GMV, TR>), grid,    \
-                     block, 0, stream, prm, dm)
-  switch (prm.geo_mode) {
-    case GEO_POINT: SFEM_LAUNCH_ADV(GEO_POINT); break;
-    case GEO_AFFINE: SFEM_LAUNCH_ADV(GEO_AFFINE); break;
-    default: SFEM_LAUNCH_ADV(GEO_MULTILINEAR); break;
-  }
-#undef SFEM_LAUNCH_ADV
+  ElementLaunch<T, P> L;
+  if (int rc = element_launch<HelmholtzTile<T, P, DIM>>("helmholtz", prm, &L))
+    return rc;
+  with_geo_mode(prm.geo_mode, [&](auto gm) {
+    hipLaunchKernelGGL(
+        (helmholtz_adv_kernel<T, P, DIM, GS, decltype(gm)::value, TR>), L.grid,
+        L.block, 0, stream, prm, L.dm);
+  });
   SFEM_LAUNCH_CHECK();
   return SFEM_OK;
 }
@@ -293,33 +253,20 @@ template <typename T, int DIM>
 int dispatch_helmholtz_adv(const HelmholtzAdvParams<T>& prm, int P, bool gs,
                            bool transpose, hipStream_t stream);
 
-#define SFEM_HELMHOLTZ_ADV_CASE(PP)                                         \
-  case PP:                                                                  \
-    if (transpose)                                                          \
-      return gs ? launch_helmholtz_adv<T, PP, DIM, true, true>(prm, stream) \
-                : launch_helmholtz_adv<T, PP, DIM, false, true>(prm,        \
-                                                                stream);    \
-    return gs ? launch_helmholtz_adv<T, PP, DIM, true, false>(prm, stream)  \
-              : launch_helmholtz_adv<T, PP, DIM, false, false>(prm, stream);
-
 #define SFEM_DEFINE_HELMHOLTZ_ADV_DISPATCH(TYPE, DIMV)                      \
   template <>                                                               \
   int dispatch_helmholtz_adv<TYPE, DIMV>(                                   \
       const HelmholtzAdvParams<TYPE>& prm, int P, bool gs, bool transpose,  \
       hipStream_t stream) {                                                 \
-    using T = TYPE;                                                         \
-    constexpr int DIM = DIMV;                                               \
-    switch (P) {                                                            \
-      SFEM_HELMHOLTZ_ADV_CASE(2) SFEM_HELMHOLTZ_ADV_CASE(3)                 \
-      SFEM_HELMHOLTZ_ADV_CASE(4) SFEM_HELMHOLTZ_ADV_CASE(5)                 \
-      SFEM_HELMHOLTZ_ADV_CASE(6) SFEM_HELMHOLTZ_ADV_CASE(7)                 \
-      SFEM_HELMHOLTZ_ADV_CASE(8) SFEM_HELMHOLTZ_ADV_CASE(9)                 \
-      SFEM_HELMHOLTZ_ADV_CASE(10) SFEM_HELMHOLTZ_ADV_CASE(11)               \
-      SFEM_HELMHOLTZ_ADV_CASE(12)                                           \
-      default:                                                              \
-        set_error("helmholtz: P=%d outside the compiled range 2..12", P);   \
-        return SFEM_EUNSUPPORTED;                                           \
-    }                                                                       \
+    return with_order<2, 12>("helmholtz", P, [&](auto p) {                  \
+      return with_flag(gs, [&](auto g) {                                    \
+        return with_flag(transpose, [&](auto tr) {                          \
+          return launch_helmholtz_adv<TYPE, decltype(p)::value, DIMV,       \
+                                      decltype(g)::value,                   \
+                                      decltype(tr)::value>(prm, stream);    \
+        });                                                                 \
+      });                                                                   \
+    });                                                                     \
   }
 
 }  // namespace sfem

@@ -254,42 +254,31 @@ helmholtz_cluster_kernel(DMat<T, P> dm, HelmholtzParams<T> prm,
   }
 }
 
+// One workgroup per cluster; scalar fields, component-major vector fields
+// (node_stride == 1) and row-major ones have kernels of their own.
 template <typename T, int P>
 int launch_helmholtz_cluster(const HelmholtzParams<T>& prm,
                              const ClusterParams<T>& cl, hipStream_t stream) {
-  using Tile = ClusterTile<T, P>;
-  if (cl.num_clusters > 0x7fffffff) {
-    set_error("helmholtz: too many clusters (%lld)", (long long)cl.num_clusters);
-    return SFEM_EINVAL;
-  }
-  const DMat<T, P> dm =
-      make_dmat<T, P>(prm.dmat_host, prm.weights_host, prm.nodes_host);
-  const dim3 grid((unsigned)cl.num_clusters), block(Tile::BLOCK);
-  const bool mass = prm.lambda0 != T(0);
-#define SFEM_LAUNCH_CL(SC, N1, GMV)                                          \
-  do {                                                                        \
-    if (mass)                                                                 \
-      hipLaunchKernelGGL(                                                     \
-          (helmholtz_cluster_kernel<T, P, SC, N1, GMV, true>), grid, block,   \
-          0, stream, dm, prm, cl);                                            \
-    else                                                                      \
-      hipLaunchKernelGGL(                                                     \
-          (helmholtz_cluster_kernel<T, P, SC, N1, GMV, false>), grid, block,  \
-          0, stream, dm, prm, cl);                                            \
-  } while (0)
-#define SFEM_LAUNCH_CL_GM(SC, N1)                                             \
-  do {                                                                        \
-    switch (prm.geo_mode) {                                                   \
-      case GEO_POINT: SFEM_LAUNCH_CL(SC, N1, GEO_POINT); break;               \
-      case GEO_AFFINE: SFEM_LAUNCH_CL(SC, N1, GEO_AFFINE); break;             \
-      default: SFEM_LAUNCH_CL(SC, N1, GEO_MULTILINEAR); break;                \
-    }                                                                         \
-  } while (0)
-  if (prm.ncomp == 1) SFEM_LAUNCH_CL_GM(true, true);
-  else if (prm.node_stride == 1) SFEM_LAUNCH_CL_GM(false, true);
-  else SFEM_LAUNCH_CL_GM(false, false);
-#undef SFEM_LAUNCH_CL_GM
-#undef SFEM_LAUNCH_CL
+  ElementLaunch<T, P> L;
+  if (int rc = element_launch("helmholtz (clusters)", cl.num_clusters,
+                              ClusterTile<T, P>::BLOCK, prm.dmat_host,
+                              prm.weights_host, prm.nodes_host, &L))
+    return rc;
+  auto launch = [&](auto scalar, auto unit_stride) {
+    with_geo_mode(prm.geo_mode, [&](auto gm) {
+      with_flag(prm.lambda0 != T(0), [&](auto mass) {
+        hipLaunchKernelGGL(
+            (helmholtz_cluster_kernel<T, P, decltype(scalar)::value,
+                                      decltype(unit_stride)::value,
+                                      decltype(gm)::value,
+                                      decltype(mass)::value>),
+            L.grid, L.block, 0, stream, L.dm, prm, cl);
+      });
+    });
+  };
+  if (prm.ncomp == 1) launch(std::true_type(), std::true_type());
+  else if (prm.node_stride == 1) launch(std::false_type(), std::true_type());
+  else launch(std::false_type(), std::false_type());
   SFEM_LAUNCH_CHECK();
   return SFEM_OK;
 }
@@ -297,18 +286,11 @@ int launch_helmholtz_cluster(const HelmholtzParams<T>& prm,
 // Limits the host side needs to build clusters (sfem_helmholtz_cluster_limits).
 template <typename T>
 inline int cluster_limits(int P, int* cluster_size, int* max_shared) {
-  switch (P) {
-#define SFEM_CL_LIMIT(PP)                              \
-  case PP:                                             \
-    *cluster_size = ClusterTile<T, PP>::CL;            \
-    *max_shared = ClusterTile<T, PP>::KMAX;            \
-    return SFEM_OK;
-    SFEM_CL_LIMIT(4) SFEM_CL_LIMIT(5) SFEM_CL_LIMIT(6) SFEM_CL_LIMIT(7)
-    SFEM_CL_LIMIT(8)
-#undef SFEM_CL_LIMIT
-    default:
-      return SFEM_EUNSUPPORTED;
-  }
+  return with_order<4, 8>("helmholtz (clusters)", P, [&](auto p) {
+    *cluster_size = ClusterTile<T, decltype(p)::value>::CL;
+    *max_shared = ClusterTile<T, decltype(p)::value>::KMAX;
+    return (int)SFEM_OK;
+  });
 }
 
 template <typename T>
@@ -321,16 +303,10 @@ int dispatch_helmholtz_cluster(const HelmholtzParams<T>& prm,
   int dispatch_helmholtz_cluster<TYPE>(const HelmholtzParams<TYPE>& prm,      \
                                        const ClusterParams<TYPE>& cl, int P,  \
                                        hipStream_t stream) {                  \
-    switch (P) {                                                              \
-      case 4: return launch_helmholtz_cluster<TYPE, 4>(prm, cl, stream);      \
-      case 5: return launch_helmholtz_cluster<TYPE, 5>(prm, cl, stream);      \
-      case 6: return launch_helmholtz_cluster<TYPE, 6>(prm, cl, stream);      \
-      case 7: return launch_helmholtz_cluster<TYPE, 7>(prm, cl, stream);      \
-      case 8: return launch_helmholtz_cluster<TYPE, 8>(prm, cl, stream);      \
-      default:                                                                \
-        set_error("helmholtz (clusters): P=%d outside 4..8", P);              \
-        return SFEM_EUNSUPPORTED;                                             \
-    }                                                                         \
+    return with_order<4, 8>("helmholtz (clusters)", P, [&](auto p) {          \
+      return launch_helmholtz_cluster<TYPE, decltype(p)::value>(prm, cl,      \
+                                                                stream);      \
+    });                                                                       \
   }
 
 }  // namespace sfem

@@ -47,7 +47,6 @@
 
 namespace sfem {
 
-constexpr int GEO_BOX = 5;
 constexpr int FACET_ROW = 27 * 4;   // int32 words per element table
 
 template <typename T>
@@ -1061,68 +1060,51 @@ helmholtz_chain_kernel(FacetParams<T> prm, typename ELEM::Mat dm) {
 }
 
 // ----------------------------------------------------------------- launch ---
+// fields of 4 GiB and more take the 64-bit addressing instantiations
+// (SFEM_FACET_OFF64=1 forces them: tests)
+template <typename T>
+inline bool facet_off32(int64_t field_reals) {
+  const char* force64 = getenv("SFEM_FACET_OFF64");
+  return (uint64_t)field_reals * sizeof(T) < ((uint64_t)1 << 32) &&
+         !(force64 && force64[0] == '1');
+}
+
 template <typename T, int P, typename ELEM>
 int launch_facet_elem(const FacetParams<T>& prm, const typename ELEM::Mat& mat,
                       unsigned groups, bool off32, hipStream_t stream) {
   const dim3 grid(groups), block(FacetLayout<P>::BLOCK);
-  if (prm.layered) {
-    if (prm.ncomp != 1) {
-      set_error("helmholtz (facet): layered assembly takes scalar fields");
-      return SFEM_EINVAL;
-    }
+  if (prm.layered && prm.ncomp != 1) {
+    set_error("helmholtz (facet): layered assembly takes scalar fields");
+    return SFEM_EINVAL;
+  }
+  if (prm.chain_off && !ELEM::CHAINS) {
+    // (nothing was launched: the caller must not read `out`)
+    set_error("helmholtz (facet): no chain kernel for this geometry at P=%d",
+              P);
+    return SFEM_EUNSUPPORTED;
+  }
+  with_flag(off32, [&](auto o32) {
+    constexpr bool O32 = decltype(o32)::value;
     if (prm.chain_off) {
       if constexpr (ELEM::CHAINS) {
-        if (off32)
-          hipLaunchKernelGGL((helmholtz_chain_kernel<T, P, ELEM, true, true>),
+        if (prm.layered)
+          hipLaunchKernelGGL((helmholtz_chain_kernel<T, P, ELEM, O32, true>),
                              grid, block, 0, stream, prm, mat);
         else
-          hipLaunchKernelGGL((helmholtz_chain_kernel<T, P, ELEM, false, true>),
-                             grid, block, 0, stream, prm, mat);
-      } else {
-        set_error("helmholtz (facet): no chain kernel for this geometry at "
-                  "P=%d", P);
-        return SFEM_EUNSUPPORTED;
+          hipLaunchKernelGGL((helmholtz_chain_kernel<T, P, ELEM, O32>), grid,
+                             block, 0, stream, prm, mat);
       }
-    } else if (off32) {
-      hipLaunchKernelGGL(
-          (helmholtz_facet_kernel<T, P, ELEM, true, true, true>), grid, block,
-          0, stream, prm, mat);
+    } else if (prm.layered) {
+      hipLaunchKernelGGL((helmholtz_facet_kernel<T, P, ELEM, true, O32, true>),
+                         grid, block, 0, stream, prm, mat);
+    } else if (prm.ncomp == 1) {
+      hipLaunchKernelGGL((helmholtz_facet_kernel<T, P, ELEM, true, O32>), grid,
+                         block, 0, stream, prm, mat);
     } else {
-      hipLaunchKernelGGL(
-          (helmholtz_facet_kernel<T, P, ELEM, true, false, true>), grid, block,
-          0, stream, prm, mat);
+      hipLaunchKernelGGL((helmholtz_facet_kernel<T, P, ELEM, false, O32>),
+                         grid, block, 0, stream, prm, mat);
     }
-    return SFEM_OK;
-  }
-  if (prm.chain_off) {
-    if constexpr (ELEM::CHAINS) {
-      if (off32)
-        hipLaunchKernelGGL((helmholtz_chain_kernel<T, P, ELEM, true>), grid,
-                           block, 0, stream, prm, mat);
-      else
-        hipLaunchKernelGGL((helmholtz_chain_kernel<T, P, ELEM, false>), grid,
-                           block, 0, stream, prm, mat);
-    } else {
-      // (nothing was launched: the caller must not read `out`)
-      set_error("helmholtz (facet): no chain kernel for this geometry at P=%d",
-                P);
-      return SFEM_EUNSUPPORTED;
-    }
-  } else if (prm.ncomp == 1) {
-    if (off32)
-      hipLaunchKernelGGL((helmholtz_facet_kernel<T, P, ELEM, true, true>),
-                         grid, block, 0, stream, prm, mat);
-    else
-      hipLaunchKernelGGL((helmholtz_facet_kernel<T, P, ELEM, true, false>),
-                         grid, block, 0, stream, prm, mat);
-  } else {
-    if (off32)
-      hipLaunchKernelGGL((helmholtz_facet_kernel<T, P, ELEM, false, true>),
-                         grid, block, 0, stream, prm, mat);
-    else
-      hipLaunchKernelGGL((helmholtz_facet_kernel<T, P, ELEM, false, false>),
-                         grid, block, 0, stream, prm, mat);
-  }
+  });
   return SFEM_OK;
 }
 
@@ -1133,11 +1115,7 @@ int launch_helmholtz_facet(const FacetParams<T>& prm, int geo_mode,
                            int64_t groups, int64_t field_reals,
                            const T* dmat, const T* weights, const T* nodes,
                            hipStream_t stream) {
-  if (groups > 0x7fffffff) {
-    set_error("helmholtz (facet): too many workgroups (%lld)",
-              (long long)groups);
-    return SFEM_EINVAL;
-  }
+  if (int rc = check_groups("helmholtz (facet)", groups)) return rc;
   if (prm.chain_off && prm.ncomp != 1) {
     set_error("helmholtz (facet): chain launches take scalar fields");
     return SFEM_EINVAL;
@@ -1150,33 +1128,23 @@ int launch_helmholtz_facet(const FacetParams<T>& prm, int geo_mode,
               (long long)prm.dot_slots);
     return SFEM_EINVAL;
   }
-  const bool mass = prm.lambda0 != T(0);
-  // fields of 4 GiB and more take the 64-bit addressing instantiations
-  // (SFEM_FACET_OFF64=1 forces them: tests)
-  const char* force64 = getenv("SFEM_FACET_OFF64");
-  const bool off32 = (uint64_t)field_reals * sizeof(T) < ((uint64_t)1 << 32) &&
-                     !(force64 && force64[0] == '1');
+  const bool off32 = facet_off32<T>(field_reals);
   int rc = SFEM_OK;
-  if (geo_mode == GEO_BOX) {
-    const SMat<T, P> sm = make_smat<T, P>(dmat, weights);
-    if (mass) rc = launch_facet_elem<T, P, BoxElem<T, P, true>>(prm, sm, g,
-                                                                off32, stream);
-    else rc = launch_facet_elem<T, P, BoxElem<T, P, false>>(prm, sm, g, off32,
-                                                            stream);
-  } else {
-    const DMat<T, P> dm = make_dmat<T, P>(dmat, weights, nodes);
-#define SFEM_FACET_GM(GMV)                                                    \
-  do {                                                                        \
-    if (mass) rc = launch_facet_elem<T, P, FacetElem<T, P, GMV, true>>(       \
-        prm, dm, g, off32, stream);                                           \
-    else rc = launch_facet_elem<T, P, FacetElem<T, P, GMV, false>>(           \
-        prm, dm, g, off32, stream);                                           \
-  } while (0)
-    if (geo_mode == GEO_AFFINE) SFEM_FACET_GM(GEO_AFFINE);
-    else if (geo_mode == GEO_MULTILINEAR) SFEM_FACET_GM(GEO_MULTILINEAR);
-    else SFEM_FACET_GM(GEO_POINT);
-#undef SFEM_FACET_GM
-  }
+  with_flag(prm.lambda0 != T(0), [&](auto mass) {
+    constexpr bool MASS = decltype(mass)::value;
+    if (geo_mode == GEO_BOX) {
+      const SMat<T, P> sm = make_smat<T, P>(dmat, weights);
+      rc = launch_facet_elem<T, P, BoxElem<T, P, MASS>>(prm, sm, g, off32,
+                                                        stream);
+    } else {
+      const DMat<T, P> dm = make_dmat<T, P>(dmat, weights, nodes);
+      with_geo_mode(geo_mode, [&](auto gm) {
+        rc = launch_facet_elem<T, P,
+                               FacetElem<T, P, decltype(gm)::value, MASS>>(
+            prm, dm, g, off32, stream);
+      });
+    }
+  });
   if (rc != SFEM_OK) return rc;
   SFEM_LAUNCH_CHECK();
   return SFEM_OK;
@@ -1213,40 +1181,21 @@ int dispatch_helmholtz_facet(const FacetParams<T>& prm, int P, int geo_mode,
 
 inline bool facet_supported_p(int P) { return P >= 6 && P <= 12; }
 
-#define SFEM_FACET_CASE(PP)                                                   \
-  case PP:                                                                    \
-    return launch_helmholtz_facet<T, PP>(prm, geo_mode, groups, field_reals,  \
-                                         dmat, weights, nodes, stream);
-
-#define SFEM_DEFINE_FACET_DISPATCH_LOW(TYPE)                                  \
+// HALF: low (P = 6..8) or high (P = 9..12)
+#define SFEM_DEFINE_FACET_DISPATCH(HALF, LO, HI, TYPE)                        \
   template <>                                                                 \
-  int dispatch_helmholtz_facet_low<TYPE>(                                     \
+  int dispatch_helmholtz_facet_##HALF<TYPE>(                                  \
       const FacetParams<TYPE>& prm, int P, int geo_mode, int64_t groups,      \
       int64_t field_reals, const TYPE* dmat, const TYPE* weights,             \
       const TYPE* nodes, hipStream_t stream) {                                \
-    using T = TYPE;                                                           \
-    switch (P) {                                                              \
-      SFEM_FACET_CASE(6) SFEM_FACET_CASE(7) SFEM_FACET_CASE(8)                \
-      default:                                                                \
-        set_error("helmholtz (facet): P=%d outside 6..8", P);                 \
-        return SFEM_EUNSUPPORTED;                                             \
-    }                                                                         \
+    return with_order<LO, HI>("helmholtz (facet)", P, [&](auto p) {           \
+      return launch_helmholtz_facet<TYPE, decltype(p)::value>(                \
+          prm, geo_mode, groups, field_reals, dmat, weights, nodes, stream);  \
+    });                                                                       \
   }
-
-#define SFEM_DEFINE_FACET_DISPATCH_HIGH(TYPE)                                 \
-  template <>                                                                 \
-  int dispatch_helmholtz_facet_high<TYPE>(                                    \
-      const FacetParams<TYPE>& prm, int P, int geo_mode, int64_t groups,      \
-      int64_t field_reals, const TYPE* dmat, const TYPE* weights,             \
-      const TYPE* nodes, hipStream_t stream) {                                \
-    using T = TYPE;                                                           \
-    switch (P) {                                                              \
-      SFEM_FACET_CASE(9) SFEM_FACET_CASE(10) SFEM_FACET_CASE(11)              \
-      SFEM_FACET_CASE(12)                                                     \
-      default:                                                                \
-        set_error("helmholtz (facet): P=%d outside 9..12", P);                \
-        return SFEM_EUNSUPPORTED;                                             \
-    }                                                                         \
-  }
+#define SFEM_DEFINE_FACET_DISPATCH_LOW(TYPE) \
+  SFEM_DEFINE_FACET_DISPATCH(low, 6, 8, TYPE)
+#define SFEM_DEFINE_FACET_DISPATCH_HIGH(TYPE) \
+  SFEM_DEFINE_FACET_DISPATCH(high, 9, 12, TYPE)
 
 }  // namespace sfem

@@ -53,37 +53,8 @@ helmholtz_sens_kernel(HelmholtzSensParams<T> prm, DMat<T, P> dm) {
   constexpr int N = DIM == 3 ? P * P * P : P * P;        // points per element
   __shared__ T lds[2 * EPB * W];
 
-  const int tid = threadIdx.x;
-  const int el = tid / TPE;                 // element within the workgroup
-  const int t = tid - el * TPE;             // lane within the element
-  const int i = DIM == 3 ? t / P : 0;
-  const int j = DIM == 3 ? t - i * P : t;
-  const bool lane_ok = el < EPB;            // tail lanes of a padded block
-  const int64_t work = (int64_t)blockIdx.x * EPB + (lane_ok ? el : 0);
-  const bool active = lane_ok && work < prm.num_elements;
-  const int64_t e =
-      prm.elem_list ? (active ? (int64_t)prm.elem_list[work] : 0) : work;
-
-  T* s0 = lds + (lane_ok ? el : 0) * 2 * W;    // becomes the axis-1 result
-  T* s1 = s0 + W;                              // becomes the axis-2 result
+  SFEM_LANE_PROLOGUE(prm);
   const DMat<T, P>& dmat = dm;
-  // fp32, P >= 9: matrix entries from the kernarg segment, as the parent does
-#if SFEM_DMAT_MEM
-#define SFEM_SENS_LINE_APPLY(X, Y)                                            \
-  do {                                                                        \
-    if constexpr (P >= 9 && sizeof(T) == 4)                                   \
-      line_apply_mem<T, P, false>(                                            \
-          (const SFEM_CONSTANT_AS DMat<T, P>*)((                              \
-              const SFEM_CONSTANT_AS char*)                                   \
-                  __builtin_amdgcn_kernarg_segment_ptr() +                    \
-              sizeof(PRM)),                                                   \
-          X, Y);                                                              \
-    else                                                                      \
-      line_apply<T, P, false>(dmat, X, Y);                                    \
-  } while (0)
-#else
-#define SFEM_SENS_LINE_APPLY(X, Y) line_apply<T, P, false>(dmat, X, Y)
-#endif
   const bool want_k = prm.dkappa != nullptr;
   const bool want_c = prm.dsigma != nullptr;
   const bool want_b = prm.dbeta != nullptr;
@@ -104,7 +75,7 @@ helmholtz_sens_kernel(HelmholtzSensParams<T> prm, DMat<T, P> dm) {
   // dx0[a] = its axis-0 derivative out; the axis-1 / axis-2 derivatives at
   // (a, i, j) are left in s0 / s1
   auto derivatives = [&](const T (&x)[P], T (&dx0)[P]) {
-    SFEM_SENS_LINE_APPLY(x, dx0);
+    SFEM_LINE_APPLY(PRM, false, x, dx0);
     if (lane_ok) {
 #pragma unroll
       for (int a = 0; a < P; ++a) {
@@ -118,7 +89,7 @@ helmholtz_sens_kernel(HelmholtzSensParams<T> prm, DMat<T, P> dm) {
       T xx[P], yy[P];
 #pragma unroll
       for (int m = 0; m < P; ++m) xx[m] = line[m];
-      SFEM_SENS_LINE_APPLY(xx, yy);
+      SFEM_LINE_APPLY(PRM, false, xx, yy);
 #pragma unroll
       for (int m = 0; m < P; ++m) line[m] = yy[m];
     }
@@ -127,7 +98,7 @@ helmholtz_sens_kernel(HelmholtzSensParams<T> prm, DMat<T, P> dm) {
       T xx[P], yy[P];
 #pragma unroll
       for (int m = 0; m < P; ++m) xx[m] = line[m * SB];
-      SFEM_SENS_LINE_APPLY(xx, yy);
+      SFEM_LINE_APPLY(PRM, false, xx, yy);
 #pragma unroll
       for (int m = 0; m < P; ++m) line[m * SB] = yy[m];
     }
@@ -199,30 +170,19 @@ helmholtz_sens_kernel(HelmholtzSensParams<T> prm, DMat<T, P> dm) {
       if (want_c) sout[q] = prm.lambda0 * Wm * la[a] * ua[a];
     }
   }
-#undef SFEM_SENS_LINE_APPLY
 }
 
 template <typename T, int P, int DIM>
 int launch_helmholtz_sens(const HelmholtzSensParams<T>& prm,
                           hipStream_t stream) {
-  using Tile = HelmholtzTile<T, P, DIM>;
-  const int64_t groups = (prm.num_elements + Tile::EPB - 1) / Tile::EPB;
-  if (groups > 0x7fffffff) {
-    set_error("helmholtz_sens: too many workgroups (%lld)", (long long)groups);
-    return SFEM_EINVAL;
-  }
-  const DMat<T, P> dm =
-      make_dmat<T, P>(prm.dmat_host, prm.weights_host, prm.nodes_host);
-  const dim3 grid((unsigned)groups), block(Tile::BLOCK);
-#define SFEM_LAUNCH_SENS(GMV)                                                 \
-  hipLaunchKernelGGL((helmholtz_sens_kernel<T, P, DIM, GMV>), grid, block, 0, \
-                     stream, prm, dm)
-  switch (prm.geo_mode) {
-    case GEO_POINT: SFEM_LAUNCH_SENS(GEO_POINT); break;
-    case GEO_AFFINE: SFEM_LAUNCH_SENS(GEO_AFFINE); break;
-    default: SFEM_LAUNCH_SENS(GEO_MULTILINEAR); break;
-  }
-#undef SFEM_LAUNCH_SENS
+  ElementLaunch<T, P> L;
+  if (int rc =
+          element_launch<HelmholtzTile<T, P, DIM>>("helmholtz_sens", prm, &L))
+    return rc;
+  with_geo_mode(prm.geo_mode, [&](auto gm) {
+    hipLaunchKernelGGL((helmholtz_sens_kernel<T, P, DIM, decltype(gm)::value>),
+                       L.grid, L.block, 0, stream, prm, L.dm);
+  });
   SFEM_LAUNCH_CHECK();
   return SFEM_OK;
 }
@@ -232,27 +192,14 @@ template <typename T, int DIM>
 int dispatch_helmholtz_sens(const HelmholtzSensParams<T>& prm, int P,
                             hipStream_t stream);
 
-#define SFEM_HELMHOLTZ_SENS_CASE(PP) \
-  case PP: return launch_helmholtz_sens<T, PP, DIM>(prm, stream);
-
 #define SFEM_DEFINE_HELMHOLTZ_SENS_DISPATCH(TYPE, DIMV)                     \
   template <>                                                               \
   int dispatch_helmholtz_sens<TYPE, DIMV>(                                  \
       const HelmholtzSensParams<TYPE>& prm, int P, hipStream_t stream) {    \
-    using T = TYPE;                                                         \
-    constexpr int DIM = DIMV;                                               \
-    switch (P) {                                                            \
-      SFEM_HELMHOLTZ_SENS_CASE(2) SFEM_HELMHOLTZ_SENS_CASE(3)               \
-      SFEM_HELMHOLTZ_SENS_CASE(4) SFEM_HELMHOLTZ_SENS_CASE(5)               \
-      SFEM_HELMHOLTZ_SENS_CASE(6) SFEM_HELMHOLTZ_SENS_CASE(7)               \
-      SFEM_HELMHOLTZ_SENS_CASE(8) SFEM_HELMHOLTZ_SENS_CASE(9)               \
-      SFEM_HELMHOLTZ_SENS_CASE(10) SFEM_HELMHOLTZ_SENS_CASE(11)             \
-      SFEM_HELMHOLTZ_SENS_CASE(12)                                          \
-      default:                                                              \
-        set_error("helmholtz_sens: P=%d outside the compiled range 2..12",  \
-                  P);                                                       \
-        return SFEM_EUNSUPPORTED;                                           \
-    }                                                                       \
+    return with_order<2, 12>("helmholtz_sens", P, [&](auto p) {             \
+      return launch_helmholtz_sens<TYPE, decltype(p)::value, DIMV>(prm,     \
+                                                                   stream); \
+    });                                                                     \
   }
 
 }  // namespace sfem

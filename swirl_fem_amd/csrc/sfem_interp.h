@@ -23,7 +23,7 @@
 // summation order, so the results are the same to the last bit.
 #ifndef SFEM_INTERP_H_
 #define SFEM_INTERP_H_
-#include "sfem_common.h"
+#include "sfem_launch.h"
 
 namespace sfem {
 
@@ -132,55 +132,39 @@ int launch_tensor_interp_one(const T* in, const T* mat, const T* weight, T* out,
   return SFEM_OK;
 }
 
-// NO - NI in [-2, 2], both in [2, 14]; anything else: SFEM_EUNSUPPORTED
+// NO - NI in [-2, 2], both in [2, 14]; anything else: SFEM_EUNSUPPORTED,
+// without a message (the caller then runs the generic kernel)
 template <typename T, int D, int NI>
 int launch_tensor_interp_ni(int no, const T* in, const T* mat, const T* weight,
                             T* out, int64_t E, int nc, bool trans,
                             hipStream_t st) {
-#define SFEM_INTERP_CASE(DELTA)                                               \
-  if constexpr (NI + (DELTA) >= 2 && NI + (DELTA) <= 14) {                    \
-    if (no == NI + (DELTA))                                                   \
-      return launch_tensor_interp_one<T, D, NI, NI + (DELTA)>(                \
-          in, mat, weight, out, E, nc, trans, st);                            \
-  }
-  SFEM_INTERP_CASE(-2) SFEM_INTERP_CASE(-1) SFEM_INTERP_CASE(0)
-  SFEM_INTERP_CASE(1) SFEM_INTERP_CASE(2)
-#undef SFEM_INTERP_CASE
-  return SFEM_EUNSUPPORTED;
+  constexpr int LO = NI - 2 < 2 ? 2 : NI - 2, HI = NI + 2 > 14 ? 14 : NI + 2;
+  return with_order<LO, HI>(nullptr, no, [&](auto n) {
+    return launch_tensor_interp_one<T, D, NI, decltype(n)::value>(
+        in, mat, weight, out, E, nc, trans, st);
+  });
 }
 
 template <typename T, int D>
 int launch_tensor_interp_d(int ni, int no, const T* in, const T* mat,
                            const T* weight, T* out, int64_t E, int nc,
                            bool trans, hipStream_t st) {
-#define SFEM_INTERP_NI(V)                                                     \
-  case V:                                                                     \
-    return launch_tensor_interp_ni<T, D, V>(no, in, mat, weight, out, E, nc,  \
-                                            trans, st);
-  switch (ni) {
-    SFEM_INTERP_NI(2) SFEM_INTERP_NI(3) SFEM_INTERP_NI(4) SFEM_INTERP_NI(5)
-    SFEM_INTERP_NI(6) SFEM_INTERP_NI(7) SFEM_INTERP_NI(8) SFEM_INTERP_NI(9)
-    SFEM_INTERP_NI(10) SFEM_INTERP_NI(11) SFEM_INTERP_NI(12)
-    SFEM_INTERP_NI(13) SFEM_INTERP_NI(14)
-  }
-#undef SFEM_INTERP_NI
-  return SFEM_EUNSUPPORTED;
+  return with_order<2, 14>(nullptr, ni, [&](auto n) {
+    return launch_tensor_interp_ni<T, D, decltype(n)::value>(
+        no, in, mat, weight, out, E, nc, trans, st);
+  });
 }
 
 template <typename T>
 int launch_tensor_interp_t(int ndim, int ni, int no, const void* in,
                            const void* mat, const void* weight, void* out,
                            int64_t E, int nc, bool trans, hipStream_t st) {
-  if (E > 0x7fffffff) return SFEM_EUNSUPPORTED;
-  if (ndim == 3)
-    return launch_tensor_interp_d<T, 3>(ni, no, (const T*)in, (const T*)mat,
-                                        (const T*)weight, (T*)out, E, nc, trans,
-                                        st);
-  if (ndim == 2)
-    return launch_tensor_interp_d<T, 2>(ni, no, (const T*)in, (const T*)mat,
-                                        (const T*)weight, (T*)out, E, nc, trans,
-                                        st);
-  return SFEM_EUNSUPPORTED;
+  if (E > 0x7fffffff || (ndim != 2 && ndim != 3)) return SFEM_EUNSUPPORTED;
+  return with_dim(ndim, [&](auto d) {
+    return launch_tensor_interp_d<T, decltype(d)::value>(
+        ni, no, (const T*)in, (const T*)mat, (const T*)weight, (T*)out, E, nc,
+        trans, st);
+  });
 }
 
 // defined in sfem_interp_f64.hip / sfem_interp_f32.hip; SFEM_EUNSUPPORTED when

@@ -22,7 +22,7 @@
 //                        bitwise reproducible.
 // Barriers sit in loops whose trip counts are uniform over the workgroup.
 #pragma once
-#include "sfem_common.h"
+#include "sfem_launch.h"
 
 namespace sfem {
 
@@ -243,27 +243,15 @@ int dispatch_point_eval(const PointParams<T>& pp, int P1, const double* nodes,
                         const double* bary, bool transpose,
                         hipStream_t stream);
 
-#define SFEM_POINT_CASE(PP_)                                              \
-  case PP_:                                                               \
-    return launch_point_eval<T, DIM, PP_>(pp, nodes, bary, transpose,     \
-                                          stream);
-
 #define SFEM_DEFINE_POINT_DISPATCH(TYPE, DIMV)                               \
   template <>                                                                \
   int dispatch_point_eval<TYPE, DIMV>(                                       \
       const PointParams<TYPE>& pp, int P1, const double* nodes,              \
       const double* bary, bool transpose, hipStream_t stream) {              \
-    using T = TYPE;                                                          \
-    constexpr int DIM = DIMV;                                                \
-    switch (P1) {                                                            \
-      SFEM_POINT_CASE(2) SFEM_POINT_CASE(3) SFEM_POINT_CASE(4)               \
-      SFEM_POINT_CASE(5) SFEM_POINT_CASE(6) SFEM_POINT_CASE(7)               \
-      SFEM_POINT_CASE(8) SFEM_POINT_CASE(9) SFEM_POINT_CASE(10)              \
-      SFEM_POINT_CASE(11) SFEM_POINT_CASE(12)                                \
-      default:                                                               \
-        set_error("point_eval: P1=%d outside the compiled range 2..12", P1); \
-        return SFEM_EUNSUPPORTED;                                            \
-    }                                                                        \
+    return with_order<2, 12>("point_eval", P1, [&](auto p) {                 \
+      return launch_point_eval<TYPE, DIMV, decltype(p)::value>(              \
+          pp, nodes, bary, transpose, stream);                               \
+    });                                                                      \
   }
 
 }  // namespace sfem

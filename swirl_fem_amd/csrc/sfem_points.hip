@@ -242,20 +242,12 @@ int check_point_args(const sfem_point_args* a, const char* who,
   SFEM_REQUIRE(a->num_found <= a->num_points,
                "%s: more found points than points", who);
   SFEM_REQUIRE(a->ncomp >= 1, "%s: ncomp=%d", who, a->ncomp);
-  SFEM_REQUIRE(a->dtype == SFEM_F32 || a->dtype == SFEM_F64,
-               "%s: unknown dtype %d", who, a->dtype);
-  if (a->ndim != 2 && a->ndim != 3) {
-    sfem::set_error("%s: ndim=%d (the kernels support 2 and 3)", who, a->ndim);
-    return SFEM_EUNSUPPORTED;
-  }
-  if (a->P1 < 2 || a->P1 > 12) {
-    sfem::set_error("%s: P1=%d outside the compiled range 2..12", who, a->P1);
-    return SFEM_EUNSUPPORTED;
-  }
+  int rc = check_shape(who, a->dtype, a->ndim, "P1", a->P1, 2, 12);
+  if (rc) return rc;
   SFEM_REQUIRE(a->nodes && a->bary, "%s: null basis table", who);
   const int64_t launches = transpose ? a->num_segments : a->num_chunks;
-  SFEM_REQUIRE(launches <= 0x7fffffff, "%s: too many workgroups (%lld)", who,
-               (long long)launches);
+  rc = check_groups(who, launches);
+  if (rc) return rc;
   if (a->num_found == 0 || launches == 0) return SFEM_OK;
   SFEM_REQUIRE(a->values && a->elements && a->xi && a->perm,
                "%s: null pointer", who);
@@ -270,7 +262,7 @@ int check_point_args(const sfem_point_args* a, const char* who,
 
 int run_point_eval(const sfem_point_args* a, bool transpose,
                    sfem_stream_t stream) {
-  auto run = [&](auto zero) -> int {
+  return with_real(a->dtype, [&](auto zero) {
     using T = decltype(zero);
     PointParams<T> pp{};
     pp.field = (const T*)a->field;
@@ -289,14 +281,11 @@ int run_point_eval(const sfem_point_args* a, bool transpose,
     pp.node_stride = a->node_stride;
     pp.comp_stride = a->comp_stride;
     pp.ncomp = a->ncomp;
-    if (a->ndim == 3)
-      return dispatch_point_eval<T, 3>(pp, a->P1, a->nodes, a->bary, transpose,
-                                       as_stream(stream));
-    return dispatch_point_eval<T, 2>(pp, a->P1, a->nodes, a->bary, transpose,
-                                     as_stream(stream));
-  };
-  if (a->dtype == SFEM_F64) return run(double(0));
-  return run(float(0));
+    return with_dim(a->ndim, [&](auto d) {
+      return dispatch_point_eval<T, decltype(d)::value>(
+          pp, a->P1, a->nodes, a->bary, transpose, as_stream(stream));
+    });
+  });
 }
 
 }  // namespace
@@ -308,16 +297,8 @@ int sfem_point_locate(const sfem_point_locate_args* a, sfem_stream_t stream) {
   SFEM_REQUIRE(a, "%s: null args", who);
   SFEM_REQUIRE(a->num_points >= 0 && a->num_nodes >= 0 && a->num_elements >= 0,
                "%s: negative size", who);
-  SFEM_REQUIRE(a->dtype == SFEM_F32 || a->dtype == SFEM_F64,
-               "%s: unknown dtype %d", who, a->dtype);
-  if (a->ndim != 2 && a->ndim != 3) {
-    set_error("%s: ndim=%d (the kernel supports 2 and 3)", who, a->ndim);
-    return SFEM_EUNSUPPORTED;
-  }
-  if (a->P1 < 2 || a->P1 > LOCATE_MAX_P) {
-    set_error("%s: P1=%d outside the range 2..%d", who, a->P1, LOCATE_MAX_P);
-    return SFEM_EUNSUPPORTED;
-  }
+  int rc = check_shape(who, a->dtype, a->ndim, "P1", a->P1, 2, LOCATE_MAX_P);
+  if (rc) return rc;
   SFEM_REQUIRE(a->max_iter >= 0 && a->max_iter <= 64,
                "%s: max_iter=%d outside 0..64", who, a->max_iter);
   SFEM_REQUIRE(a->tol_xi >= 0.0 && a->tol_x >= 0.0,
@@ -335,8 +316,8 @@ int sfem_point_locate(const sfem_point_locate_args* a, sfem_stream_t stream) {
                    a->cell_elems && a->boxes && a->extent,
                "%s: null pointer (mesh or candidates)", who);
   const int64_t groups = (a->num_points + LOCATE_BLOCK - 1) / LOCATE_BLOCK;
-  SFEM_REQUIRE(groups <= 0x7fffffff, "%s: too many workgroups (%lld)", who,
-               (long long)groups);
+  rc = check_groups(who, groups);
+  if (rc) return rc;
   LocateParams lp{};
   lp.points = a->points;
   lp.node_coords = a->node_coords;
@@ -368,21 +349,14 @@ int sfem_point_locate(const sfem_point_locate_args* a, sfem_stream_t stream) {
   lp.P1 = a->P1;
   const dim3 grid((unsigned)groups), block(LOCATE_BLOCK);
   hipStream_t s = as_stream(stream);
-  if (a->dtype == SFEM_F64) {
-    if (a->ndim == 3)
-      hipLaunchKernelGGL((point_locate_kernel<double, 3>), grid, block, 0, s,
-                         lp);
-    else
-      hipLaunchKernelGGL((point_locate_kernel<double, 2>), grid, block, 0, s,
-                         lp);
-  } else {
-    if (a->ndim == 3)
-      hipLaunchKernelGGL((point_locate_kernel<float, 3>), grid, block, 0, s,
-                         lp);
-    else
-      hipLaunchKernelGGL((point_locate_kernel<float, 2>), grid, block, 0, s,
-                         lp);
-  }
+  with_real(a->dtype, [&](auto zero) {
+    return with_dim(a->ndim, [&](auto d) {
+      hipLaunchKernelGGL(
+          (point_locate_kernel<decltype(zero), decltype(d)::value>), grid,
+          block, 0, s, lp);
+      return (int)SFEM_OK;
+    });
+  });
   SFEM_LAUNCH_CHECK();
   return SFEM_OK;
 }

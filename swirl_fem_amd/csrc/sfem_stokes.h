@@ -305,18 +305,7 @@ __device__ __forceinline__ void cof_fence(ElemCof<T, P, DIM, GM>& g) {
   constexpr int N = DIM == 3 ? P * P * P : P * P;                             \
   constexpr int NP = DIM == 3 ? PP * PP * PP : PP * PP;                       \
   __shared__ T lds[2 * EPB * W];                                              \
-  const int tid = threadIdx.x;                                                \
-  const int el = tid / TPE;                                                   \
-  const int t = tid - el * TPE;                                               \
-  const int i = DIM == 3 ? t / P : 0;                                         \
-  const int j = DIM == 3 ? t - i * P : t;                                     \
-  const bool lane_ok = el < EPB;                                              \
-  const int64_t work = (int64_t)blockIdx.x * EPB + (lane_ok ? el : 0);        \
-  const bool active = lane_ok && work < prm.num_elements;                     \
-  const int64_t e =                                                           \
-      prm.elem_list ? (active ? (int64_t)prm.elem_list[work] : 0) : work;     \
-  T* s0 = lds + (lane_ok ? el : 0) * 2 * W;                                   \
-  T* s1 = s0 + W;                                                             \
+  SFEM_LANE_PROLOGUE(prm);                                                    \
   const int64_t ns = prm.node_stride, ks = prm.comp_stride;                   \
   ElemCof<T, P, DIM, GM> geom;                                                \
   geom.init(prm, dm, e, active, i, j, t);                                     \
@@ -328,7 +317,7 @@ __device__ __forceinline__ void cof_fence(ElemCof<T, P, DIM, GM>& g) {
   }                                                                           \
   const int32_t* penc0 = prm.penc ? prm.penc + e * NP : nullptr;              \
   const int64_t pbase = e * NP;                                               \
-  (void)s1; (void)N; (void)penc0; (void)pbase
+  (void)N; (void)penc0; (void)pbase
 
 // SECOND: the second half of the split E = D Q D^T (see stokes_e_first_kernel):
 // only the SHARED slots are gathered (the others were consumed in registers by
@@ -877,19 +866,7 @@ stokes_convect_kernel(StokesParams<T> prm, DMat<T, P> dm) {
   constexpr int EPB = Tile::EPB, W = Tile::ELEM_WORDS;
   constexpr int N = DIM == 3 ? P * P * P : P * P;
   __shared__ T lds[2 * EPB * W];
-  const int tid = threadIdx.x;
-  const int el = tid / TPE;
-  const int t = tid - el * TPE;
-  const int i = DIM == 3 ? t / P : 0;
-  const int j = DIM == 3 ? t - i * P : t;
-  const bool lane_ok = el < EPB;
-  const int64_t work = (int64_t)blockIdx.x * EPB + (lane_ok ? el : 0);
-  const bool active = lane_ok && work < prm.num_elements;
-  const int64_t e =
-      prm.elem_list ? (active ? (int64_t)prm.elem_list[work] : 0) : work;
-  T* s0 = lds + (lane_ok ? el : 0) * 2 * W;
-  T* s1 = s0 + W;
-  (void)s1;
+  SFEM_LANE_PROLOGUE(prm);
   ElemCof<T, P, DIM, GM> geom;
   geom.init(prm, dm, e, active, i, j, t);
   const T* ue = prm.u + e * N * DIM;
@@ -961,48 +938,39 @@ int launch_stokes(const StokesParams<T>& prm, int mode, hipStream_t stream) {
   const bool grad_t = mode == 1;
   constexpr int PP = P - 2;
   using Tile = HelmholtzTile<T, P, DIM>;
-  const int64_t groups = (prm.num_elements + Tile::EPB - 1) / Tile::EPB;
-  if (groups > 0x7fffffff) {
-    set_error("stokes: too many workgroups (%lld)", (long long)groups);
-    return SFEM_EINVAL;
-  }
-  const DMat<T, P> dm =
-      make_dmat<T, P>(prm.dmat_host, prm.weights_host, prm.nodes_host);
+  ElementLaunch<T, P> L;
+  if (int rc = element_launch<Tile>("stokes", prm, &L)) return rc;
   IMat<T, P, PP> im;
   for (int q = 0; q < P * PP; ++q)
     im.m[q] = prm.interp_host ? prm.interp_host[q] : T(0);
-  const dim3 grid((unsigned)groups), block(Tile::BLOCK);
   // sorted shared scatter: own instantiations, one-wave elements in 3D
   constexpr bool CAN_SORT = DIM == 3 && Tile::TPE <= 64;
   const bool sorted = CAN_SORT && prm.shared_order != nullptr;
-#define SFEM_LAUNCH_STOKES(GMV)                                               \
-  if (mode == 2)                                                              \
-    hipLaunchKernelGGL((stokes_convect_kernel<T, P, DIM, GMV>), grid, block,  \
-                       0, stream, prm, dm);                                   \
-  else if (mode == 3 && sorted)                                               \
-    hipLaunchKernelGGL((stokes_e_first_kernel<T, P, PP, DIM, GMV, CAN_SORT>), \
-                       grid, block, 0, stream, prm, dm, im);                  \
-  else if (mode == 3)                                                         \
-    hipLaunchKernelGGL((stokes_e_first_kernel<T, P, PP, DIM, GMV, false>),    \
-                       grid, block, 0, stream, prm, dm, im);                  \
-  else if (mode == 4)                                                         \
-    hipLaunchKernelGGL((stokes_div_kernel<T, P, PP, DIM, GMV, true>), grid,   \
-                       block, 0, stream, prm, dm, im);                        \
-  else if (grad_t && sorted)                                                  \
-    hipLaunchKernelGGL((stokes_grad_t_kernel<T, P, PP, DIM, GMV, CAN_SORT>),  \
-                       grid, block, 0, stream, prm, dm, im);                  \
-  else if (grad_t)                                                            \
-    hipLaunchKernelGGL((stokes_grad_t_kernel<T, P, PP, DIM, GMV, false>),     \
-                       grid, block, 0, stream, prm, dm, im);                  \
-  else                                                                        \
-    hipLaunchKernelGGL((stokes_div_kernel<T, P, PP, DIM, GMV>), grid, block,  \
-                       0, stream, prm, dm, im)
-  switch (prm.geo_mode) {
-    case GEO_POINT: SFEM_LAUNCH_STOKES(GEO_POINT); break;
-    case GEO_AFFINE: SFEM_LAUNCH_STOKES(GEO_AFFINE); break;
-    default: SFEM_LAUNCH_STOKES(GEO_MULTILINEAR); break;
-  }
-#undef SFEM_LAUNCH_STOKES
+  with_geo_mode(prm.geo_mode, [&](auto gm) {
+    constexpr int GMV = decltype(gm)::value;
+    if (mode == 2)
+      hipLaunchKernelGGL((stokes_convect_kernel<T, P, DIM, GMV>), L.grid,
+                         L.block, 0, stream, prm, L.dm);
+    else if (mode == 3 && sorted)
+      hipLaunchKernelGGL(
+          (stokes_e_first_kernel<T, P, PP, DIM, GMV, CAN_SORT>), L.grid,
+          L.block, 0, stream, prm, L.dm, im);
+    else if (mode == 3)
+      hipLaunchKernelGGL((stokes_e_first_kernel<T, P, PP, DIM, GMV, false>),
+                         L.grid, L.block, 0, stream, prm, L.dm, im);
+    else if (mode == 4)
+      hipLaunchKernelGGL((stokes_div_kernel<T, P, PP, DIM, GMV, true>), L.grid,
+                         L.block, 0, stream, prm, L.dm, im);
+    else if (grad_t && sorted)
+      hipLaunchKernelGGL((stokes_grad_t_kernel<T, P, PP, DIM, GMV, CAN_SORT>),
+                         L.grid, L.block, 0, stream, prm, L.dm, im);
+    else if (grad_t)
+      hipLaunchKernelGGL((stokes_grad_t_kernel<T, P, PP, DIM, GMV, false>),
+                         L.grid, L.block, 0, stream, prm, L.dm, im);
+    else
+      hipLaunchKernelGGL((stokes_div_kernel<T, P, PP, DIM, GMV>), L.grid,
+                         L.block, 0, stream, prm, L.dm, im);
+  });
   SFEM_LAUNCH_CHECK();
   return SFEM_OK;
 }
@@ -1012,24 +980,14 @@ template <typename T, int DIM>
 int dispatch_stokes(const StokesParams<T>& prm, int P, int mode,
                     hipStream_t stream);
 
-#define SFEM_STOKES_CASE(PP_) \
-  case PP_: return launch_stokes<T, PP_, DIM>(prm, mode, stream);
-
 #define SFEM_DEFINE_STOKES_DISPATCH(TYPE, DIMV)                              \
   template <>                                                                \
   int dispatch_stokes<TYPE, DIMV>(const StokesParams<TYPE>& prm, int P,      \
                                   int mode, hipStream_t stream) {            \
-    using T = TYPE;                                                          \
-    constexpr int DIM = DIMV;                                                \
-    switch (P) {                                                             \
-      SFEM_STOKES_CASE(4) SFEM_STOKES_CASE(5)                                \
-      SFEM_STOKES_CASE(6) SFEM_STOKES_CASE(7) SFEM_STOKES_CASE(8)            \
-      SFEM_STOKES_CASE(9) SFEM_STOKES_CASE(10) SFEM_STOKES_CASE(11)          \
-      SFEM_STOKES_CASE(12)                                                   \
-      default:                                                               \
-        set_error("stokes: P=%d outside the compiled range 4..12", P);       \
-        return SFEM_EUNSUPPORTED;                                            \
-    }                                                                        \
+    return with_order<4, 12>("stokes", P, [&](auto p) {                      \
+      return launch_stokes<TYPE, decltype(p)::value, DIMV>(prm, mode,        \
+                                                           stream);          \
+    });                                                                      \
   }
 
 }  // namespace sfem

@@ -26,8 +26,8 @@ stokes_setup_kernel(const T* __restrict__ invjac, const T* __restrict__ jacdet,
 }
 
 template <typename T>
-static int run_stokes(const sfem_stokes_args* a, int mode,
-                      hipStream_t stream) {
+static int run_stokes_as(const sfem_stokes_args* a, int mode,
+                         hipStream_t stream) {
   StokesParams<T> prm{};
   prm.u = (const T*)a->u; prm.out = (T*)a->out;
   prm.p_in = (const T*)a->p_in; prm.p_out = (T*)a->p_out;
@@ -60,8 +60,16 @@ static int run_stokes(const sfem_stokes_args* a, int mode,
     return dispatch_stokes_facet<T>(fprm, a->P, mode, a->num_chains,
                                     a->num_nodes, stream);
   }
-  if (a->ndim == 3) return dispatch_stokes<T, 3>(prm, a->P, mode, stream);
-  return dispatch_stokes<T, 2>(prm, a->P, mode, stream);
+  return with_dim(a->ndim, [&](auto d) {
+    return dispatch_stokes<T, decltype(d)::value>(prm, a->P, mode, stream);
+  });
+}
+
+static int run_stokes(const sfem_stokes_args* a, int mode,
+                      hipStream_t stream) {
+  return with_real(a->dtype, [&](auto zero) {
+    return run_stokes_as<decltype(zero)>(a, mode, stream);
+  });
 }
 
 static int check_stokes(const char* who, const sfem_stokes_args* a) {
@@ -75,23 +83,15 @@ static int check_stokes(const char* who, const sfem_stokes_args* a) {
                "%s: unknown dtype %d", who, a->dtype);
   if (a->num_elements == 0) return SFEM_OK;
   SFEM_REQUIRE(a->dmat, "%s: null pointer", who);
-  if (a->geo_mode == SFEM_GEO_POINT) {
-    SFEM_REQUIRE(a->kfac, "%s: per-point geometry needs `kfac`", who);
-  } else if (a->geo_mode == SFEM_GEO_AFFINE ||
-             a->geo_mode == SFEM_GEO_MULTILINEAR ||
-             a->geo_mode == SFEM_GEO_BOX) {
-    SFEM_REQUIRE(a->geo_elem && a->weights && a->nodes,
-                 "%s: on-the-fly geometry needs geo_elem, weights and nodes",
-                 who);
-    SFEM_REQUIRE(a->geo_mode != SFEM_GEO_BOX || a->facet_table,
-                 "%s: SFEM_GEO_BOX is a facet-table (chain) launch", who);
-  } else {
-    set_error("%s: unknown geo_mode %d", who, a->geo_mode);
-    return SFEM_EINVAL;
-  }
-  if (a->elem_list)
-    SFEM_REQUIRE(a->num_listed >= 0 && a->num_listed <= a->num_elements,
-                 "%s: bad element list length", who);
+  int rc = check_geometry(who, a->geo_mode, a->kfac, "kfac", a->geo_elem,
+                          a->weights, a->nodes);
+  if (rc) return rc;
+  SFEM_REQUIRE(a->geo_mode != SFEM_GEO_BOX || a->facet_table,
+               "%s: SFEM_GEO_BOX is a facet-table (chain) launch", who);
+  int64_t work;
+  rc = check_elem_list(who, a->elem_list, a->num_listed, a->num_elements,
+                       &work);
+  if (rc) return rc;
   if (a->facet_table) {
     SFEM_REQUIRE(a->ndim == 3 && stokes_facet_supported_p(a->P),
                  "%s: facet tables are 3D, P = 6..8", who);
@@ -143,8 +143,7 @@ int sfem_stokes_convect_local(const sfem_stokes_args* a, sfem_stream_t stream) {
   const int64_t work = a->elem_list ? a->num_listed : a->num_elements;
   if (work == 0) return SFEM_OK;
   SFEM_REQUIRE(a->u && a->out, "sfem_stokes_convect_local: null pointer");
-  if (a->dtype == SFEM_F64) return run_stokes<double>(a, 2, as_stream(stream));
-  return run_stokes<float>(a, 2, as_stream(stream));
+  return run_stokes(a, 2, as_stream(stream));
 }
 
 int sfem_stokes_div(const sfem_stokes_args* a, sfem_stream_t stream) {
@@ -157,8 +156,7 @@ int sfem_stokes_div(const sfem_stokes_args* a, sfem_stream_t stream) {
   SFEM_REQUIRE(a->u && a->p_out, "sfem_stokes_div: null pointer");
   SFEM_REQUIRE(!a->dot_out || a->p_in,
                "sfem_stokes_div: dot_out needs p_in (the vector to dot with)");
-  if (a->dtype == SFEM_F64) return run_stokes<double>(a, 0, as_stream(stream));
-  return run_stokes<float>(a, 0, as_stream(stream));
+  return run_stokes(a, 0, as_stream(stream));
 }
 
 // zero-fill of the shared-node range of `out` (all components)
@@ -193,8 +191,7 @@ int sfem_stokes_grad_t(const sfem_stokes_args* a, sfem_stream_t stream) {
   rc = zero_shared_range(a, stream);
   if (rc) return rc;
   if (work == 0) return SFEM_OK;
-  if (a->dtype == SFEM_F64) return run_stokes<double>(a, 1, as_stream(stream));
-  return run_stokes<float>(a, 1, as_stream(stream));
+  return run_stokes(a, 1, as_stream(stream));
 }
 
 int sfem_stokes_e_first(const sfem_stokes_args* a, sfem_stream_t stream) {
@@ -212,8 +209,7 @@ int sfem_stokes_e_first(const sfem_stokes_args* a, sfem_stream_t stream) {
   rc = zero_shared_range(a, stream);
   if (rc) return rc;
   if (work == 0) return SFEM_OK;
-  if (a->dtype == SFEM_F64) return run_stokes<double>(a, 3, as_stream(stream));
-  return run_stokes<float>(a, 3, as_stream(stream));
+  return run_stokes(a, 3, as_stream(stream));
 }
 
 int sfem_stokes_e_second(const sfem_stokes_args* a, sfem_stream_t stream) {
@@ -223,8 +219,7 @@ int sfem_stokes_e_second(const sfem_stokes_args* a, sfem_stream_t stream) {
   const int64_t work = a->elem_list ? a->num_listed : a->num_elements;
   if (work == 0) return SFEM_OK;
   SFEM_REQUIRE(a->u && a->p_out, "sfem_stokes_e_second: null pointer");
-  if (a->dtype == SFEM_F64) return run_stokes<double>(a, 4, as_stream(stream));
-  return run_stokes<float>(a, 4, as_stream(stream));
+  return run_stokes(a, 4, as_stream(stream));
 }
 
 }  // extern "C"

@@ -723,61 +723,34 @@ int launch_stokes_facet(const StokesFacetParams<T>& fprm, int mode,
                         hipStream_t stream) {
   constexpr int PP = P - 2;
   const StokesParams<T>& prm = fprm.base;
-  if (num_chains > 0x7fffffff) {
-    set_error("stokes (facet): too many workgroups (%lld)",
-              (long long)num_chains);
-    return SFEM_EINVAL;
-  }
-  const DMat<T, P> dm =
-      make_dmat<T, P>(prm.dmat_host, prm.weights_host, prm.nodes_host);
+  ElementLaunch<T, P> L;
+  if (int rc = element_launch("stokes (facet)", num_chains, 64, prm.dmat_host,
+                              prm.weights_host, prm.nodes_host, &L))
+    return rc;
   IMat<T, P, PP> im;
   for (int q = 0; q < P * PP; ++q)
     im.m[q] = prm.interp_host ? prm.interp_host[q] : T(0);
-  const dim3 grid((unsigned)num_chains), block(64);
-  const char* force64 = getenv("SFEM_FACET_OFF64");
-  const bool off32 = (uint64_t)field_reals * sizeof(T) < ((uint64_t)1 << 32) &&
-                     !(force64 && force64[0] == '1');
-#define SFEM_STOKES_FACET_GO(GMV)                                             \
-  do {                                                                        \
-    if (mode == 1) {                                                          \
-      if (off32)                                                              \
-        hipLaunchKernelGGL((stokes_grad_t_chain_kernel<T, P, GMV, true>),     \
-                           grid, block, 0, stream, fprm, dm, im);             \
-      else                                                                    \
-        hipLaunchKernelGGL((stokes_grad_t_chain_kernel<T, P, GMV, false>),    \
-                           grid, block, 0, stream, fprm, dm, im);             \
-    } else {                                                                  \
-      if (off32)                                                              \
-        hipLaunchKernelGGL((stokes_div_chain_kernel<T, P, GMV, true>), grid,  \
-                           block, 0, stream, fprm, dm, im);                   \
-      else                                                                    \
-        hipLaunchKernelGGL((stokes_div_chain_kernel<T, P, GMV, false>), grid, \
-                           block, 0, stream, fprm, dm, im);                   \
-    }                                                                         \
-  } while (0)
-  switch (prm.geo_mode) {
-    case GEO_BOX:
-      if (mode == 1) {
-        if (off32)
-          hipLaunchKernelGGL((stokes_grad_t_box_kernel<T, P, true>), grid,
-                             block, 0, stream, fprm, dm, im);
-        else
-          hipLaunchKernelGGL((stokes_grad_t_box_kernel<T, P, false>), grid,
-                             block, 0, stream, fprm, dm, im);
-      } else {
-        if (off32)
-          hipLaunchKernelGGL((stokes_div_box_kernel<T, P, true>), grid, block,
-                             0, stream, fprm, dm, im);
-        else
-          hipLaunchKernelGGL((stokes_div_box_kernel<T, P, false>), grid, block,
-                             0, stream, fprm, dm, im);
-      }
-      break;
-    case GEO_POINT: SFEM_STOKES_FACET_GO(GEO_POINT); break;
-    case GEO_AFFINE: SFEM_STOKES_FACET_GO(GEO_AFFINE); break;
-    default: SFEM_STOKES_FACET_GO(GEO_MULTILINEAR); break;
-  }
-#undef SFEM_STOKES_FACET_GO
+  with_flag(facet_off32<T>(field_reals), [&](auto o32) {
+    constexpr bool O32 = decltype(o32)::value;
+    if (prm.geo_mode == GEO_BOX) {
+      if (mode == 1)
+        hipLaunchKernelGGL((stokes_grad_t_box_kernel<T, P, O32>), L.grid,
+                           L.block, 0, stream, fprm, L.dm, im);
+      else
+        hipLaunchKernelGGL((stokes_div_box_kernel<T, P, O32>), L.grid,
+                           L.block, 0, stream, fprm, L.dm, im);
+      return;
+    }
+    with_geo_mode(prm.geo_mode, [&](auto gm) {
+      constexpr int GMV = decltype(gm)::value;
+      if (mode == 1)
+        hipLaunchKernelGGL((stokes_grad_t_chain_kernel<T, P, GMV, O32>),
+                           L.grid, L.block, 0, stream, fprm, L.dm, im);
+      else
+        hipLaunchKernelGGL((stokes_div_chain_kernel<T, P, GMV, O32>), L.grid,
+                           L.block, 0, stream, fprm, L.dm, im);
+    });
+  });
   SFEM_LAUNCH_CHECK();
   return SFEM_OK;
 }
@@ -794,20 +767,10 @@ inline bool stokes_facet_supported_p(int P) { return P >= 6 && P <= 8; }
   int dispatch_stokes_facet<TYPE>(const StokesFacetParams<TYPE>& fprm, int P, \
                                   int mode, int64_t num_chains,               \
                                   int64_t field_reals, hipStream_t stream) {  \
-    switch (P) {                                                              \
-      case 6:                                                                 \
-        return launch_stokes_facet<TYPE, 6>(fprm, mode, num_chains,           \
-                                            field_reals, stream);             \
-      case 7:                                                                 \
-        return launch_stokes_facet<TYPE, 7>(fprm, mode, num_chains,           \
-                                            field_reals, stream);             \
-      case 8:                                                                 \
-        return launch_stokes_facet<TYPE, 8>(fprm, mode, num_chains,           \
-                                            field_reals, stream);             \
-      default:                                                                \
-        set_error("stokes (facet): P=%d outside 6..8", P);                    \
-        return SFEM_EUNSUPPORTED;                                             \
-    }                                                                         \
+    return with_order<6, 8>("stokes (facet)", P, [&](auto p) {                \
+      return launch_stokes_facet<TYPE, decltype(p)::value>(                   \
+          fprm, mode, num_chains, field_reals, stream);                       \
+    });                                                                       \
   }
 
 }  // namespace sfem

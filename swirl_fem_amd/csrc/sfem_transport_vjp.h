@@ -73,19 +73,7 @@ transport_vjp_kernel(TransportVjpParams<T> tp, DMat<T, P> dm) {
   constexpr int N = DIM == 3 ? P * P * P : P * P;
   __shared__ T lds[2 * EPB * W];
   const StokesParams<T>& prm = tp.geo;
-  const int tid = threadIdx.x;
-  const int el = tid / TPE;
-  const int t = tid - el * TPE;
-  const int i = DIM == 3 ? t / P : 0;
-  const int j = DIM == 3 ? t - i * P : t;
-  const bool lane_ok = el < EPB;
-  const int64_t work = (int64_t)blockIdx.x * EPB + (lane_ok ? el : 0);
-  const bool active = lane_ok && work < prm.num_elements;
-  const int64_t e =
-      prm.elem_list ? (active ? (int64_t)prm.elem_list[work] : 0) : work;
-  T* s0 = lds + (lane_ok ? el : 0) * 2 * W;
-  T* s1 = s0 + W;
-  (void)s1;
+  SFEM_LANE_PROLOGUE(prm);
   ElemCof<T, P, DIM, GM> geom;
   geom.init(prm, dm, e, active, i, j, t);
   // per-point arrays of this element: lane t of slice a reads point
@@ -257,26 +245,14 @@ transport_vjp_kernel(TransportVjpParams<T> tp, DMat<T, P> dm) {
 
 template <typename T, int P, int DIM>
 int launch_transport_vjp(const TransportVjpParams<T>& tp, hipStream_t stream) {
-  using Tile = HelmholtzTile<T, P, DIM>;
-  const StokesParams<T>& prm = tp.geo;
-  const int64_t groups = (prm.num_elements + Tile::EPB - 1) / Tile::EPB;
-  if (groups > 0x7fffffff) {
-    set_error("transport_rhs_vjp: too many workgroups (%lld)",
-              (long long)groups);
-    return SFEM_EINVAL;
-  }
-  const DMat<T, P> dm =
-      make_dmat<T, P>(prm.dmat_host, prm.weights_host, prm.nodes_host);
-  const dim3 grid((unsigned)groups), block(Tile::BLOCK);
-#define SFEM_LAUNCH_TRANSPORT_VJP(GMV)                                       \
-  hipLaunchKernelGGL((transport_vjp_kernel<T, P, DIM, GMV>), grid, block, 0, \
-                     stream, tp, dm)
-  switch (prm.geo_mode) {
-    case GEO_POINT: SFEM_LAUNCH_TRANSPORT_VJP(GEO_POINT); break;
-    case GEO_AFFINE: SFEM_LAUNCH_TRANSPORT_VJP(GEO_AFFINE); break;
-    default: SFEM_LAUNCH_TRANSPORT_VJP(GEO_MULTILINEAR); break;
-  }
-#undef SFEM_LAUNCH_TRANSPORT_VJP
+  ElementLaunch<T, P> L;
+  if (int rc = element_launch<HelmholtzTile<T, P, DIM>>("transport_rhs_vjp",
+                                                        tp.geo, &L))
+    return rc;
+  with_geo_mode(tp.geo.geo_mode, [&](auto gm) {
+    hipLaunchKernelGGL((transport_vjp_kernel<T, P, DIM, decltype(gm)::value>),
+                       L.grid, L.block, 0, stream, tp, L.dm);
+  });
   SFEM_LAUNCH_CHECK();
   return SFEM_OK;
 }
@@ -286,27 +262,14 @@ template <typename T, int DIM>
 int dispatch_transport_vjp(const TransportVjpParams<T>& tp, int P,
                            hipStream_t stream);
 
-#define SFEM_TRANSPORT_VJP_CASE(PP_) \
-  case PP_: return launch_transport_vjp<T, PP_, DIM>(tp, stream);
-
 #define SFEM_DEFINE_TRANSPORT_VJP_DISPATCH(TYPE, DIMV)                       \
   template <>                                                                \
   int dispatch_transport_vjp<TYPE, DIMV>(                                    \
       const TransportVjpParams<TYPE>& tp, int P, hipStream_t stream) {       \
-    using T = TYPE;                                                          \
-    constexpr int DIM = DIMV;                                                \
-    switch (P) {                                                             \
-      SFEM_TRANSPORT_VJP_CASE(2) SFEM_TRANSPORT_VJP_CASE(3)                  \
-      SFEM_TRANSPORT_VJP_CASE(4) SFEM_TRANSPORT_VJP_CASE(5)                  \
-      SFEM_TRANSPORT_VJP_CASE(6) SFEM_TRANSPORT_VJP_CASE(7)                  \
-      SFEM_TRANSPORT_VJP_CASE(8) SFEM_TRANSPORT_VJP_CASE(9)                  \
-      SFEM_TRANSPORT_VJP_CASE(10) SFEM_TRANSPORT_VJP_CASE(11)                \
-      SFEM_TRANSPORT_VJP_CASE(12)                                            \
-      default:                                                               \
-        set_error("transport_rhs_vjp: P=%d outside the compiled range 2..12",\
-                  P);                                                        \
-        return SFEM_EUNSUPPORTED;                                            \
-    }                                                                        \
+    return with_order<2, 12>("transport_rhs_vjp", P, [&](auto p) {           \
+      return launch_transport_vjp<TYPE, decltype(p)::value, DIMV>(tp,        \
+                                                                  stream);   \
+    });                                                                      \
   }
 
 }  // namespace sfem

@@ -12,27 +12,15 @@ int sfem_transport_rhs_vjp(const sfem_transport_vjp_args* a,
   SFEM_REQUIRE(a, "%s: null args", who);
   SFEM_REQUIRE(a->num_elements >= 0 && a->num_levels >= 0,
                "%s: bad sizes", who);
-  SFEM_REQUIRE(a->dtype == SFEM_F32 || a->dtype == SFEM_F64,
-               "%s: unknown dtype %d", who, a->dtype);
-  if (a->ndim != 2 && a->ndim != 3) {
-    set_error("%s: ndim=%d (the kernel supports 2 and 3)", who, a->ndim);
-    return SFEM_EUNSUPPORTED;
-  }
-  if (a->P < 2 || a->P > 12) {
-    set_error("%s: P=%d outside the compiled range 2..12", who, a->P);
-    return SFEM_EUNSUPPORTED;
-  }
+  int rc = check_shape(who, a->dtype, a->ndim, "P", a->P, 2, 12);
+  if (rc) return rc;
   if (a->num_levels > SFEM_TRANSPORT_LEVELS) {
     set_error("%s: %d levels (at most %d)", who, a->num_levels,
               SFEM_TRANSPORT_LEVELS);
     return SFEM_EUNSUPPORTED;
   }
-  if (a->geo_mode != SFEM_GEO_POINT && a->geo_mode != SFEM_GEO_AFFINE &&
-      a->geo_mode != SFEM_GEO_MULTILINEAR) {
-    set_error("%s: geo_mode %d (point, affine or multilinear)", who,
-              a->geo_mode);
-    return SFEM_EUNSUPPORTED;
-  }
+  rc = check_geo_mode(who, a->geo_mode);
+  if (rc) return rc;
   if (a->num_elements == 0) return SFEM_OK;
   SFEM_REQUIRE(a->cotangent && a->dmat, "%s: null pointer", who);
   bool needs_wdet = a->dsource != nullptr;
@@ -44,17 +32,15 @@ int sfem_transport_rhs_vjp(const sfem_transport_vjp_args* a,
   }
   SFEM_REQUIRE(!needs_wdet || a->wdet,
                "%s: mass terms and dsource need `wdet`", who);
-  if (a->geo_mode == SFEM_GEO_POINT)
-    SFEM_REQUIRE(a->kfac, "%s: per-point geometry needs `kfac`", who);
-  else
-    SFEM_REQUIRE(a->geo_elem && a->weights && a->nodes,
-                 "%s: on-the-fly geometry needs geo_elem, weights and nodes",
-                 who);
-  const int64_t work = a->elem_list ? a->num_listed : a->num_elements;
-  SFEM_REQUIRE(work >= 0 && work <= a->num_elements,
-               "%s: bad element list length", who);
+  rc = check_geometry(who, a->geo_mode, a->kfac, "kfac", a->geo_elem,
+                      a->weights, a->nodes);
+  if (rc) return rc;
+  int64_t work;
+  rc = check_elem_list(who, a->elem_list, a->num_listed, a->num_elements,
+                       &work);
+  if (rc) return rc;
   if (work == 0) return SFEM_OK;
-  auto run = [&](auto zero) -> int {
+  return with_real(a->dtype, [&](auto zero) {
     using T = decltype(zero);
     TransportVjpParams<T> tp{};
     tp.geo.kfac = (const T*)a->kfac;
@@ -78,12 +64,11 @@ int sfem_transport_rhs_vjp(const sfem_transport_vjp_args* a,
     tp.wdet = (const T*)a->wdet;
     tp.dsource = (T*)a->dsource;
     tp.num_levels = a->num_levels;
-    if (a->ndim == 3)
-      return dispatch_transport_vjp<T, 3>(tp, a->P, as_stream(stream));
-    return dispatch_transport_vjp<T, 2>(tp, a->P, as_stream(stream));
-  };
-  if (a->dtype == SFEM_F64) return run(double(0));
-  return run(float(0));
+    return with_dim(a->ndim, [&](auto d) {
+      return dispatch_transport_vjp<T, decltype(d)::value>(tp, a->P,
+                                                           as_stream(stream));
+    });
+  });
 }
 
 }  // extern "C"

@@ -612,3 +612,76 @@ def test_refusals():
   assert rc == -1, rc                                        # SFEM_EINVAL
   with pytest.raises(ValueError):
     op.sensitivity(ul, ul, 0.0, 1.0)                         # not nodal
+
+
+def test_entry_point_refusals():
+  """Return codes of `sfem_helmholtz_sens` and `sfem_helmholtz_local` on a raw
+  args struct: one valid call each, then one field wrong at a time."""
+  import ctypes
+  mesh, _, rp = G.affine(2, 3, 4).finalize(DEV, F64)
+  fes = FiniteElementSpace.create(mesh, Quadrature1D.create(4, GLL))
+  op = fes.helmholtz_operator(None)
+  part, = op.parts
+  assert part['geo_mode'] == _lib.GEO_AFFINE
+  E, n = mesh.num_elements, mesh.num_nodes_per_element
+  z = lambda *s: torch.zeros(s, dtype=F64, device=DEV)
+  keep = dict(u=z(E, n), lam=z(E, n), out=z(E, n), dk=z(E, n), db=z(E, n, 3),
+              lst=torch.zeros(E, dtype=torch.int32, device=DEV),
+              host={k: _ops._host(v, F64) for k, v in op.host.items()})
+  lst = keep['lst'].data_ptr()
+  lib = _lib.load()
+
+  def sens(**over):
+    a = _lib.HelmholtzSensArgs(
+        u=keep['u'].data_ptr(), lam=keep['lam'].data_ptr(),
+        dkappa=keep['dk'].data_ptr(), dbeta=keep['db'].data_ptr(),
+        **_ops._launch_fields(part, keep['host']), num_elements=E, ndim=3,
+        P=4, ncomp=1, dtype=_lib.SFEM_F64, lambda0=1.0, lambda1=1.0)
+    for k, v in over.items():
+      setattr(a, k, v)
+    return lib.sfem_helmholtz_sens(ctypes.byref(a), None)
+
+  def local(**over):
+    a = _ops._helmholtz_args(keep['u'], keep['out'], None, part, keep['host'],
+                             3, 4, E, 0, 1.0, 1.0, (0, 0))
+    for k, v in over.items():
+      setattr(a, k, v)
+    return lib.sfem_helmholtz_local(ctypes.byref(a), None)
+
+  # what both refuse alike; an unknown geo_mode is SFEM_EINVAL here
+  unsupported = (dict(P=13), dict(P=1), dict(ndim=1), dict(ndim=4))
+  invalid = (dict(dtype=5), dict(geo_mode=7), dict(geo_mode=_lib.GEO_POINT),
+             dict(u=None), dict(dmat=None), dict(geo_elem=None),
+             dict(weights=None), dict(nodes=None), dict(num_elements=-1),
+             dict(ncomp=0), dict(elem_list=lst, num_listed=E + 1),
+             dict(elem_list=lst, num_listed=-1))
+  for call in (sens, local):
+    assert call() == 0, call
+    torch.cuda.synchronize()
+    for over in unsupported:
+      assert call(**over) == -3, (call, over)
+    for over in invalid:
+      assert call(**over) == -1, (call, over)
+    assert call(num_elements=0, dmat=None) == 0, call
+    assert call(elem_list=lst, num_listed=0) == 0, call
+  # the sensitivities: scalar fields, no box launches; nothing asked for is
+  # nothing to do
+  for over in (dict(ncomp=3), dict(geo_mode=_lib.GEO_BOX)):
+    assert sens(**over) == -3, over
+  assert sens(lam=None) == -1
+  assert sens(dkappa=None, dbeta=None, geo_elem=None) == 0
+  # the element-local apply: up to 8 components; the terms it cannot combine
+  for over in (dict(out=None), dict(ncomp=9), dict(coef_mode=3),
+               dict(coef_mode=_lib.COEF_POINT),
+               dict(coef_mode=_lib.COEF_POINT, kappa=keep['dk'].data_ptr(),
+                    geo_mode=_lib.GEO_POINT, geo=keep['dk'].data_ptr())):
+    assert local(**over) == -1, over
+  beta = keep['db'].data_ptr()
+  for over in (dict(beta=beta, coef_mode=_lib.COEF_ELEM,
+                    kappa=keep['dk'].data_ptr()),
+               dict(beta=beta, geo_mode=_lib.GEO_BOX),
+               dict(beta=beta, ndim=4)):
+    assert local(**over) == -3, over
+  assert lib.sfem_helmholtz_sens(None, None) == -1
+  assert lib.sfem_helmholtz_local(None, None) == -1
+  torch.cuda.synchronize()

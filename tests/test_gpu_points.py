@@ -428,3 +428,52 @@ def test_refusals():
   # a non-contiguous field is copied, not misread
   u = torch.randn((N, 6), dtype=F64, device=DEV)[:, ::2]
   assert torch.equal(ev(u), ev(u.contiguous()))
+
+
+def test_entry_point_refusals():
+  """Return codes of `sfem_point_eval` / `sfem_point_eval_t` on a raw args
+  struct: one valid call each, then one field wrong at a time."""
+  import ctypes
+  from swirl_fem_amd import _lib, _ops
+  mesh, _, rp = G.affine(2, 3, 4).finalize(DEV, F64)
+  pts = _dev(np.asarray(rp.node_coords, np.float64)[::7][:9])
+  plan = PT.PointEvaluator.create(mesh, pts).plan
+  assert plan.num_found == plan.num_points == 9
+  S, n = plan.seg_elem.numel(), mesh.elements.shape[1]
+  keep = dict(u=torch.zeros(mesh.num_nodes, dtype=F64, device=DEV),
+              vals=torch.zeros(9, dtype=F64, device=DEV),
+              rows=torch.zeros((S, n, 1), dtype=F64, device=DEV))
+  lib = _lib.load()
+
+  def raw(**over):
+    a = _ops._point_args(plan, keep['vals'], 1)
+    a.field, a.rows = keep['u'].data_ptr(), keep['rows'].data_ptr()
+    a.node_stride, a.comp_stride = 1, 1
+    for k, v in over.items():
+      setattr(a, k, v)
+    return a
+  calls = {'eval': lambda a: lib.sfem_point_eval(ctypes.byref(a), None),
+           'eval_t': lambda a: lib.sfem_point_eval_t(ctypes.byref(a), None)}
+  unsupported = (dict(P1=13), dict(P1=1), dict(ndim=1), dict(ndim=4))
+  invalid = (dict(dtype=5), dict(ncomp=0), dict(nodes=None), dict(bary=None),
+             dict(num_points=-1), dict(num_found=10), dict(num_elements=-1),
+             dict(num_nodes=-1), dict(values=None), dict(elements=None),
+             dict(xi=None), dict(perm=None))
+  own = {'eval': (dict(field=None), dict(chunk_elem=None),
+                  dict(chunk_start=None), dict(chunk_count=None),
+                  dict(num_chunks=-1), dict(num_chunks=2 ** 31)),
+         'eval_t': (dict(rows=None), dict(seg_elem=None),
+                    dict(seg_offsets=None), dict(num_segments=-1),
+                    dict(num_segments=2 ** 31))}
+  for which, call in calls.items():
+    assert call(raw()) == 0, which
+    torch.cuda.synchronize()
+    for over in unsupported:
+      assert call(raw(**over)) == -3, (which, over)
+    for over in invalid + own[which]:
+      assert call(raw(**over)) == -1, (which, over)
+    # nothing found, or nothing to launch: nothing to do
+    assert call(raw(num_found=0, values=None)) == 0, which
+  assert calls['eval'](raw(num_chunks=0, field=None)) == 0
+  assert calls['eval_t'](raw(num_segments=0, rows=None)) == 0
+  torch.cuda.synchronize()

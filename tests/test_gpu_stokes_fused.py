@@ -424,3 +424,63 @@ def test_fused_convection_matches_oracle(ndim, n, P, extra, dtype):
   for geometry in ('auto', 'stored'):
     op = operators.ConvectionOperator.create(fes, geometry)
     assert relerr(op.apply_local(dev(ul, dtype)), ref) < tol, geometry
+
+
+def test_entry_point_refusals():
+  """Return codes of `sfem_stokes_div` / `sfem_stokes_grad_t` on a raw args
+  struct: one valid call each, then one field wrong at a time.  (The velocity
+  and the pressure mesh of `build` with shear: 2 affine elements per axis.)"""
+  import ctypes
+  from swirl_fem_amd import _lib, _ops
+  _, vsp, psp, _, _ = build(3, 2, 4, torch.float64, jitter=0.0, shear=True)
+  fused = operators.StokesDivGrad.create(vsp, psp, None)
+  assert [q['geo_mode'] for q in fused.parts] == [_lib.GEO_AFFINE]
+  N, Np = vsp.mesh.num_nodes, fused.num_pressure_nodes
+  E = vsp.mesh.num_elements
+  z = lambda *s: torch.zeros(s, dtype=torch.float64, device=DEV)
+  keep = dict(u=z(N, 3), out=z(N, 3), p=z(Np), p_out=z(Np), dots=z(1024),
+              lst=torch.zeros(E, dtype=torch.int32, device=DEV),
+              host={k: _ops._host(v, torch.float64)
+                    for k, v in fused.host.items()})
+
+  def raw(which, **over):
+    ptrs = (dict(u=keep['u'].data_ptr(), p_out=keep['p_out'].data_ptr())
+            if which == 'div' else
+            dict(out=keep['out'].data_ptr(), p_in=keep['p'].data_ptr()))
+    a = _ops._stokes_args(keep['u'], fused.enc, fused.penc, fused.parts[0],
+                          keep['host'], 3, 4, (0, 0), None, **ptrs)
+    for k, v in over.items():
+      setattr(a, k, v)
+    return a
+  lib = _lib.load()
+  calls = {'div': lambda a: lib.sfem_stokes_div(ctypes.byref(a), None),
+           'grad_t': lambda a: lib.sfem_stokes_grad_t(ctypes.byref(a), None)}
+  # SFEM_EINVAL, but for an order that the header admits (P <= SFEM_MAX_P)
+  # and no kernel was compiled for: SFEM_EUNSUPPORTED
+  common = (dict(P=17), dict(P=3), dict(P=1), dict(ndim=1), dict(ndim=4),
+            dict(dtype=5), dict(geo_mode=7), dict(geo_mode=_lib.GEO_BOX),
+            dict(geo_mode=_lib.GEO_POINT), dict(num_elements=-1),
+            dict(dmat=None), dict(geo_elem=None), dict(weights=None),
+            dict(nodes=None), dict(enc=None), dict(interp=None),
+            dict(elem_list=keep['lst'].data_ptr(), num_listed=E + 1),
+            dict(elem_list=keep['lst'].data_ptr(), num_listed=-1),
+            dict(facet_table=keep['lst'].data_ptr()))
+  own = {'div': (dict(u=None), dict(p_out=None),
+                 dict(dot_out=keep['dots'].data_ptr())),
+         'grad_t': (dict(out=None), dict(p_in=None),
+                    dict(zero_begin=-1), dict(zero_begin=2, zero_end=1),
+                    dict(zero_end=N + 1))}
+  for which, call in calls.items():
+    assert call(raw(which)) == 0, which
+    torch.cuda.synchronize()
+    for over in common + own[which]:
+      assert call(raw(which, **over)) == -1, (which, over)
+    for P in (13, 16):
+      assert call(raw(which, P=P)) == -3, (which, P)
+    # nothing to do: no elements, or an empty element list
+    assert call(raw(which, num_elements=0, dmat=None)) == 0, which
+    assert call(raw(which, elem_list=keep['lst'].data_ptr(),
+                    num_listed=0)) == 0, which
+  assert lib.sfem_stokes_div(None, None) == -1
+  assert lib.sfem_stokes_grad_t(None, None) == -1
+  torch.cuda.synchronize()
