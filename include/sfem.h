@@ -639,6 +639,49 @@ typedef struct sfem_transport_vjp_args {
 int sfem_transport_rhs_vjp(const sfem_transport_vjp_args* args,
                            sfem_stream_t stream);
 
+/* ------------------------------------------------------ linear elasticity ---
+ * out = K u + lambda0 M_rho u on a collocated grid of P points per direction
+ * (the quadrature grid of the solve, after interpolation to it), element-
+ * local, with v^T K u = int sigma(u) : grad v and
+ * sigma = lam tr(eps) I + 2 mu eps (plane strain in 2D).  Per element and
+ * point, with Kw[a][j] = w_q detJ_q d xi_a / d x_j the weighted cofactors of
+ * sfem_transport_args (same geometry arguments, `elem_list` / `num_listed`)
+ * and W = wdet = w_q detJ_q:
+ *
+ *   G[c][a] = d u_c / d xi_a
+ *   H[c][j] = (1/W) sum_a Kw[a][j] G[c][a]
+ *   S[c][j] = lam (tr H) delta_cj + mu (H[c][j] + H[j][c])
+ *   F[c][a] = sum_j Kw[a][j] S[c][j]
+ *   out[e,m,c] = sum_a sum_q D_a[q,m] F[c][a](q) + lambda0 rho W u_c(m)
+ *
+ * `u` and `out` are (E, n, ndim) row-major, points in slot order; `wdet` is
+ * required.  `lam`, `mu` and `rho` are (E, n) per-point arrays, or NULL for
+ * the scalar lam_const / mu_const / rho_const.  lambda0 = 0 skips the mass
+ * term.  ndim outside 2..3, P outside 2..12 and any other geo_mode return
+ * SFEM_EUNSUPPORTED; a NULL u, out, dmat, wdet or a missing geometry array is
+ * SFEM_EINVAL.  ABI version 10 (a pure addition).                            */
+typedef struct sfem_elasticity_args {
+  const void* u;          /* (E, n, ndim)                                     */
+  void* out;              /* (E, n, ndim)                                     */
+  const void* wdet;       /* (E, n)                                           */
+  const void* lam;        /* (E, n) or NULL                                   */
+  const void* mu;         /* (E, n) or NULL                                   */
+  const void* rho;        /* (E, n) or NULL                                   */
+  double lam_const, mu_const, rho_const, lambda0;
+  const void* kfac;       /* per-point weighted cofactors or NULL             */
+  const void* geo_elem;   /* (E, 24) or NULL                                  */
+  const int32_t* geo_index; /* (E,) slot of element e in kfac, or NULL = e    */
+  const int32_t* elem_list; /* element ids of this launch, or NULL = all      */
+  const void* dmat;       /* HOST (P, P)                                      */
+  const void* weights;    /* HOST (P,)                                        */
+  const void* nodes;      /* HOST (P,)                                        */
+  int64_t num_elements;
+  int64_t num_listed;
+  int32_t ndim, P, dtype, geo_mode;
+} sfem_elasticity_args;
+int sfem_elasticity_local(const sfem_elasticity_args* args,
+                          sfem_stream_t stream);
+
 /* ------------------------------------- fields at points: locate, eval, eval^T ---
  * A field of order P1 - 1 on element e is u(xi) = sum_n u[elements[e, n]]
  * l_n(xi) with l_n the tensor product of the 1D Lagrange polynomials on

@@ -143,6 +143,19 @@ class TransportVjpArgs(ctypes.Structure):
   ]
 
 
+class ElasticityArgs(ctypes.Structure):
+  """Mirror of `struct sfem_elasticity_args`."""
+  _fields_ = [
+      ('u', c_ptr), ('out', c_ptr), ('wdet', c_ptr), ('lam', c_ptr),
+      ('mu', c_ptr), ('rho', c_ptr), ('lam_const', c_dbl), ('mu_const', c_dbl),
+      ('rho_const', c_dbl), ('lambda0', c_dbl), ('kfac', c_ptr),
+      ('geo_elem', c_ptr), ('geo_index', c_ptr), ('elem_list', c_ptr),
+      ('dmat', c_ptr), ('weights', c_ptr), ('nodes', c_ptr),
+      ('num_elements', c_i64), ('num_listed', c_i64), ('ndim', c_i32),
+      ('P', c_i32), ('dtype', c_i32), ('geo_mode', c_i32),
+  ]
+
+
 SFEM_POINT_CHUNK = 64
 
 
@@ -301,6 +314,7 @@ SIGNATURES = {
     'sfem_stokes_convect_local': [c_ptr, c_ptr],
     'sfem_transport_rhs': [ctypes.POINTER(TransportArgs), c_ptr],
     'sfem_transport_rhs_vjp': [ctypes.POINTER(TransportVjpArgs), c_ptr],
+    'sfem_elasticity_local': [ctypes.POINTER(ElasticityArgs), c_ptr],
     'sfem_point_locate': [ctypes.POINTER(PointLocateArgs), c_ptr],
     'sfem_point_eval': [ctypes.POINTER(PointArgs), c_ptr],
     'sfem_point_eval_t': [ctypes.POINTER(PointArgs), c_ptr],

@@ -1321,6 +1321,44 @@ def transport_rhs_vjp(cotangent, levels, parts, host, ndim, P, wdet, want):
   return out, dsource
 
 
+def elasticity_local(u_q, parts, host, ndim, P, wdet, lam, mu, rho=None,
+                     lambda0=0.0):
+  """Linear elasticity on a collocated grid (`sfem_elasticity_local`): `u_q`
+  (E, P^d, d) -> K u + lambda0 M_rho u there, (E, P^d, d).  `wdet` (E, P^d);
+  `lam`, `mu`, `rho`: a float or an (E, P^d) tensor each (`rho` None = 1)."""
+  u_q = u_q.contiguous()
+  dev = _dev(u_q)
+  E, n, d = u_q.shape
+  if d != ndim or n != P ** ndim:
+    raise ValueError(f'expected (E, {P ** ndim}, {ndim}) local values, got '
+                     f'{tuple(u_q.shape)}')
+  if wdet is None:
+    raise ValueError('elasticity_local needs `wdet`')
+  tensors = []
+  field = lambda t, name: _field(t, name, (E, n), u_q, 'displacement', tensors)
+  args = _lib.ElasticityArgs(u=u_q.data_ptr(), lambda0=float(lambda0),
+                             wdet=field(wdet, 'wdet').data_ptr())
+  for name, value in (('lam', lam), ('mu', mu),
+                      ('rho', 1.0 if rho is None else rho)):
+    if isinstance(value, torch.Tensor):
+      setattr(args, name, field(value, name).data_ptr())
+    else:
+      setattr(args, name + '_const', float(value))
+  out = torch.empty_like(u_q)
+  host = {k: _host(v, u_q.dtype) for k, v in host.items()}
+  args.out = out.data_ptr()
+  args.num_elements, args.ndim, args.P = E, ndim, P
+  args.dtype = _dtype_code(u_q)
+  with torch.cuda.device(dev):
+    for part in parts:
+      for name, value in _launch_fields(part, host, 'kfac').items():
+        setattr(args, name, value)
+      _lib.check(_lib.load().sfem_elasticity_local(ctypes.byref(args),
+                                                   _stream(dev)),
+                 'sfem_elasticity_local')
+  return out
+
+
 # ------------------------------------------------------------ fields at points
 def point_locate(points, node_coords, elements, grid, nodes, bary, max_iter,
                  tol_xi, tol_x):

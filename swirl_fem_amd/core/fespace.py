@@ -595,6 +595,23 @@ class FiniteElementSpace:
     self._cache[key] = (dirichlet_mask, op)
     return op
 
+  def elasticity_operator(self, dirichlet_mask=None, *, lame_lambda, lame_mu,
+                          density=None, geometry='auto'):
+    """Fused linear elasticity, `out = mask * scatter((K + lambda0 M_rho)_local
+    (gather(u)))` for displacements u (N, d): `v^T K u = int sigma(u) : grad
+    v` with sigma = lambda tr(eps) I + 2 mu eps (plane strain in 2D).
+
+    `lame_lambda` >= 0, `lame_mu` > 0 and `density` >= 0 (None: 1) are each a
+    scalar, an (E,) tensor, an (E, Q^d) tensor at the quadrature points or a
+    callable (M, d) -> (M,) on their coordinates (`operators.coefficient`;
+    `operators.lame_parameters` makes the first two from E and nu).
+    `dirichlet_mask`: (N, d) bool per component, or (N,) for all components
+    of a node."""
+    from swirl_fem_amd.core import operators
+    return operators.ElasticityOperator.create(
+        self, dirichlet_mask, lame_lambda=lame_lambda, lame_mu=lame_mu,
+        density=density, geometry=geometry)
+
 
 class BoundaryMassOperator:
   """`scale * M u` with M the facet mass matrix `(B (x) B)^T diag(aw) (B (x) B)`

@@ -517,18 +517,21 @@ def first_toucher_violations(elements, first, launches):
   return int((slot_launch[later] <= first_launch[el[later]]).sum())
 
 
-def coefficient(value, name, num_elements, npts, points, dtype, device):
+def coefficient(value, name, num_elements, npts, points, dtype, device,
+                positive=None):
   """A diffusivity (`name` 'diffusivity': finite, > 0) or reaction coefficient
   ('reaction': finite, >= 0) in normal form: None, a float, or
   (mode, tensor) with mode `_lib.COEF_ELEM` and an (E,) tensor or
   `_lib.COEF_POINT` and an (E, npts) tensor at the operator's points
   (lexicographic, axis 0 slowest).  `value` is one of those, or a callable
   that maps (M, d) coordinates to (M,) values: it is evaluated once at
-  `points()` (E, npts, d).  Anything else raises ValueError."""
+  `points()` (E, npts, d).  Anything else raises ValueError.  `positive`
+  states the sign rule of a coefficient with another `name`."""
   from swirl_fem_amd import _lib
   if value is None:
     return None
-  positive = name == 'diffusivity'
+  if positive is None:
+    positive = name == 'diffusivity'
   what = '> 0' if positive else '>= 0'
 
   def check(t):
@@ -559,7 +562,7 @@ def coefficient(value, name, num_elements, npts, points, dtype, device):
   numeric = t.is_floating_point() or t.dtype in (torch.int32, torch.int64)
   if t.dim() == 0 and numeric:
     return coefficient(float(t), name, num_elements, npts, points, dtype,
-                       device)
+                       device, positive)
   if t.dim() == 0 or not (t.is_floating_point() or t.dtype in (
       torch.int32, torch.int64)):
     raise ValueError(f'{name}: expected a scalar, an (E,) or (E, Q^d) '
@@ -2229,3 +2232,183 @@ class TransportRhs:
                          f'({mesh.num_nodes},) or ({mesh.num_elements}, {nq})')
     rq = self.apply_local(local, sq)
     return mesh.scatter(fes._interpolate_t(rq[..., None], grad)[..., 0])
+
+
+# ---------------------------------------------------------------------------
+# Linear elasticity
+# ---------------------------------------------------------------------------
+def lame_parameters(youngs_modulus, poisson_ratio, plane_stress=False):
+  """(lambda, mu) of an isotropic material from Young's modulus E and
+  Poisson's ratio nu: mu = E / (2 (1 + nu)), lambda = E nu / ((1 + nu)
+  (1 - 2 nu)).  `plane_stress`: the modified lambda = 2 lambda mu / (lambda +
+  2 mu) = E nu / (1 - nu^2) with which the 2D (plane-strain) operator solves
+  the plane-stress problem."""
+  E, nu = youngs_modulus, poisson_ratio
+  mu = E / (2.0 * (1.0 + nu))
+  lam = E * nu / ((1.0 + nu) * (1.0 - 2.0 * nu))
+  if plane_stress:
+    lam = 2.0 * lam * mu / (lam + 2.0 * mu)
+  return lam, mu
+
+
+@dataclasses.dataclass(eq=False)
+class ElasticityOperator:
+  """`K u + lambda0 M_rho u` for displacements u (N, d), with `v^T K u = int
+  sigma(u) : grad v`, sigma = lambda tr(eps) I + 2 mu eps (plane strain in
+  2D) and M_rho the mass matrix with density rho.  Interpolate
+  the element's displacement to the quadrature grid (`sfem_basis_eval`, d
+  components), one fused kernel there (`sfem_elasticity_local`: collocated
+  derivative lines, cofactor geometry, stress, transposed derivative lines,
+  mass term), transposed interpolation (`sfem_basis_eval_t`).  Nothing of
+  size (E, Q^d, d, d) is stored.  `lam`, `mu`, `rho`: a float or an (E, Q^d)
+  tensor each; `mask` (N, d): 0 on the fixed components."""
+  fespace: object
+  parts: list
+  host: dict
+  lam: object
+  mu: object
+  rho: object
+  mask: torch.Tensor | None = None
+  _wdet: torch.Tensor | None = None
+  _diag: tuple | None = None
+
+  @classmethod
+  def create(cls, fespace, dirichlet_mask=None, *, lame_lambda, lame_mu,
+             density=None, geometry='auto') -> 'ElasticityOperator':
+    mesh = fespace.mesh
+    if mesh.axis_name is not None or mesh.neighbor_plan is not None:
+      raise NotImplementedError('ElasticityOperator on a partitioned mesh')
+    if mesh._cache.get('replicas', 1) > 1:
+      raise NotImplementedError('ElasticityOperator on an ensemble '
+                                '(Mesh.replicate)')
+    why = supports_two_grid(fespace)
+    if why is not None:
+      raise NotImplementedError(f'fused elasticity unavailable: {why}')
+    if geometry not in ('auto', 'stored'):
+      raise ValueError(f'unknown geometry mode {geometry!r}')
+    E, d = mesh.num_elements, mesh.ndim
+    npts = fespace.quadrature.num_points ** d
+    points = lambda: fespace._interpolate(mesh.element_coords())
+
+    def intake(value, name, positive):
+      c = coefficient(value, name, E, npts, points, fespace.dtype,
+                      fespace.device, positive)
+      if isinstance(c, tuple):      # per-element values are expanded here: the
+        mode, t = c                 # kernel reads per-point arrays only
+        from swirl_fem_amd import _lib
+        if mode == _lib.COEF_ELEM:
+          t = t[:, None].expand(E, npts)
+        return t.contiguous()
+      return c
+    if lame_lambda is None or lame_mu is None:
+      raise ValueError('lame_lambda and lame_mu are required')
+    lam = intake(lame_lambda, 'lame_lambda', False)
+    mu = intake(lame_mu, 'lame_mu', True)
+    rho = intake(1.0 if density is None else density, 'density', False)
+    mask = None
+    if dirichlet_mask is not None:
+      m = torch.as_tensor(dirichlet_mask, device=fespace.device)
+      if tuple(m.shape) == (mesh.num_nodes,):
+        m = m[:, None].expand(mesh.num_nodes, d)
+      if tuple(m.shape) != (mesh.num_nodes, d):
+        raise ValueError(f'dirichlet_mask: shape {tuple(m.shape)}; expected '
+                         f'({mesh.num_nodes}, {d}) or ({mesh.num_nodes},)')
+      mask = (m == 0).to(fespace.dtype).contiguous()
+    parts = _grid_geometry_parts(fespace, _ops.stokes_setup, geometry)
+    return cls(fespace=fespace, parts=parts, host=_host_tables(fespace, True),
+               lam=lam, mu=mu, rho=rho, mask=mask)
+
+  def point_weights(self):
+    """W = w detJ (E, Q^d)."""
+    if self._wdet is None:
+      self._wdet = self.fespace.wdet()
+    return self._wdet
+
+  def apply_local(self, u_local, lambda0=0.0):
+    """(E, n, d) element displacements -> (E, n, d) local covector."""
+    fes = self.fespace
+    if autodiff.needs_grad(u_local):
+      raise NotImplementedError('autograd through ElasticityOperator')
+    d = fes.mesh.ndim
+    if u_local.dim() != 3 or u_local.shape[-1] != d:
+      raise ValueError(f'expected (E, n, {d}) local values, got '
+                       f'{tuple(u_local.shape)}')
+    uq = fes._interpolate(u_local.to(fes.dtype)).contiguous()
+    rq = _ops.elasticity_local(uq, self.parts, self.host, d,
+                               fes.quadrature.num_points,
+                               self.point_weights(), self.lam, self.mu,
+                               self.rho, lambda0)
+    return fes._interpolate_t(rq)
+
+  def apply(self, u, lambda0=0.0):
+    """u (N, d), dense or component-major -> mask * scatter(local(gather(u)))
+    in the layout of `u`."""
+    mesh = self.fespace.mesh
+    if tuple(u.shape) != (mesh.num_nodes, mesh.ndim):
+      raise ValueError(f'expected ({mesh.num_nodes}, {mesh.ndim}) nodal '
+                       f'displacements, got {tuple(u.shape)}')
+    if autodiff.needs_grad(u):
+      raise NotImplementedError('autograd through ElasticityOperator')
+    v = u.to(self.fespace.dtype).contiguous()
+    loc = self.apply_local(_ops.gather_rows(v, mesh.elements), lambda0)
+    out = _ops.scatter_add(loc, mesh.elements, mesh.num_nodes, ncomp=mesh.ndim)
+    if self.mask is not None:
+      out = out * self.mask
+    return _like_layout(out, u) if u.dtype == out.dtype else out
+
+  def linear_operator(self, lambda0=0.0):
+    return lambda u: self.apply(u, lambda0)
+
+  def _component_factors(self, i):
+    """Stored per-point factors of the scalar operator that is the diagonal
+    block of component i: the tensor mu I + (lambda + mu) e_i e_i^T folded as
+    G_i = W J^-1 (.) J^-T, and rho W, in the layout of `sfem_helmholtz_setup`
+    for every element."""
+    fes = self.fespace
+    d = fes.mesh.ndim
+    ij, W = fes.invjacs, self.point_weights()    # ij[e,q,j,a] = d xi_a / d x_j
+    lm = self.lam + self.mu
+    vals = []
+    for a in range(d):
+      for b in range(a, d):
+        g = (ij[..., a] * ij[..., b]).sum(-1) * self.mu
+        vals.append(W * (g + lm * ij[..., i, a] * ij[..., i, b]))
+    Wm = W * self.rho
+    E, Q = W.shape
+    if d == 3:
+      pairs = torch.stack(vals).view(3, 2, E, Q).permute(2, 0, 3, 1)
+      return torch.cat([pairs.reshape(E, 6 * Q), Wm], dim=1).view(
+          E, 7, Q).contiguous()
+    pairs = torch.stack(vals + [Wm]).view(2, 2, E, Q).permute(2, 0, 3, 1)
+    return pairs.reshape(E, 4, Q).contiguous()
+
+  def diagonal(self, lambda0=0.0):
+    """The assembled (N, d) diagonal of `apply(u, lambda0)`: per component the
+    element diagonals of I^T K_ii I from `sfem_helmholtz_diag` on stored
+    factors, summed per node in a fixed order, fixed components zero."""
+    fes = self.fespace
+    mesh = fes.mesh
+    d = mesh.ndim
+    if self._diag is None:
+      P = mesh.gridpoints_1d.num_points
+      bmat = None if fes.is_collocated else np.asarray(
+          fes.interpolator._interpolation_matrix_1d(), dtype=np.float64)
+      dq = np.asarray(self.host['dmat'], dtype=np.float64)
+      dtil = dq if bmat is None else dq @ bmat
+      offsets, slots = mesh.assembly_plan().csr()
+      mass, stiff = None, []
+      for i in range(d):
+        part = {'geo_mode': _GEO_POINT, 'geo': self._component_factors(i)}
+        m, k = _ops.helmholtz_diag(
+            [part], mesh.num_elements, d, P, dtil, self.host['weights'],
+            self.host['nodes'], bmat, want_mass=i == 0, dtype=fes.dtype,
+            device=fes.device)
+        stiff.append(_ops.scatter_csr(k.reshape(-1), offsets, slots,
+                                      mesh.num_nodes))
+        if i == 0:
+          mass = _ops.scatter_csr(m.reshape(-1), offsets, slots,
+                                  mesh.num_nodes)
+      self._diag = (mass, torch.stack(stiff, dim=1).contiguous())
+    mass, stiff = self._diag
+    out = stiff if lambda0 == 0.0 else stiff + lambda0 * mass[:, None]
+    return out if self.mask is None else out * self.mask
