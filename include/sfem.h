@@ -682,6 +682,45 @@ typedef struct sfem_elasticity_args {
 int sfem_elasticity_local(const sfem_elasticity_args* args,
                           sfem_stream_t stream);
 
+/* Lame and density sensitivities of that operator: for two displacement
+ * fields `u` and `v` on the collocated grid ((E, n, ndim) each) and
+ * H_u = (1/W) Kw G_u, H_v = (1/W) Kw G_v as above, per point q
+ *
+ *   dlam[q] = W tr(H_u) tr(H_v)
+ *   dmu[q]  = W sum_{c,j} (H_u[c][j] + H_u[j][c]) H_v[c][j]
+ *   drho[q] = lambda0 W sum_c u_c v_c
+ *
+ * the derivatives of v^T (K + lambda0 M_rho) u with respect to lam[q], mu[q]
+ * and rho[q].  Each output is (E, n) in the layout of the per-point
+ * coefficients, or NULL: its product and its stores are skipped, and with
+ * `dlam` and `dmu` both NULL no derivative is formed.  Element-local: no
+ * gather, no scatter, no atomics.  Geometry and launch arguments are those of
+ * sfem_elasticity_args.  ndim outside 2..3, P outside 2..12 and any other
+ * geo_mode return SFEM_EUNSUPPORTED; a NULL u, v, dmat or wdet, all three
+ * outputs NULL or a missing geometry array is SFEM_EINVAL.  ABI version 10 (a
+ * pure addition).                                                            */
+typedef struct sfem_elasticity_sens_args {
+  const void* u;          /* (E, n, ndim)                                     */
+  const void* v;          /* (E, n, ndim)                                     */
+  const void* wdet;       /* (E, n)                                           */
+  void* dlam;             /* (E, n) or NULL                                   */
+  void* dmu;              /* (E, n) or NULL                                   */
+  void* drho;             /* (E, n) or NULL                                   */
+  double lambda0;
+  const void* kfac;       /* per-point weighted cofactors or NULL             */
+  const void* geo_elem;   /* (E, 24) or NULL                                  */
+  const int32_t* geo_index; /* (E,) slot of element e in kfac, or NULL = e    */
+  const int32_t* elem_list; /* element ids of this launch, or NULL = all      */
+  const void* dmat;       /* HOST (P, P)                                      */
+  const void* weights;    /* HOST (P,)                                        */
+  const void* nodes;      /* HOST (P,)                                        */
+  int64_t num_elements;
+  int64_t num_listed;
+  int32_t ndim, P, dtype, geo_mode;
+} sfem_elasticity_sens_args;
+int sfem_elasticity_sens(const sfem_elasticity_sens_args* args,
+                         sfem_stream_t stream);
+
 /* ------------------------------------- fields at points: locate, eval, eval^T ---
  * A field of order P1 - 1 on element e is u(xi) = sum_n u[elements[e, n]]
  * l_n(xi) with l_n the tensor product of the 1D Lagrange polynomials on

@@ -156,6 +156,18 @@ class ElasticityArgs(ctypes.Structure):
   ]
 
 
+class ElasticitySensArgs(ctypes.Structure):
+  """Mirror of `struct sfem_elasticity_sens_args`."""
+  _fields_ = [
+      ('u', c_ptr), ('v', c_ptr), ('wdet', c_ptr), ('dlam', c_ptr),
+      ('dmu', c_ptr), ('drho', c_ptr), ('lambda0', c_dbl), ('kfac', c_ptr),
+      ('geo_elem', c_ptr), ('geo_index', c_ptr), ('elem_list', c_ptr),
+      ('dmat', c_ptr), ('weights', c_ptr), ('nodes', c_ptr),
+      ('num_elements', c_i64), ('num_listed', c_i64), ('ndim', c_i32),
+      ('P', c_i32), ('dtype', c_i32), ('geo_mode', c_i32),
+  ]
+
+
 SFEM_POINT_CHUNK = 64
 
 
@@ -315,6 +327,7 @@ SIGNATURES = {
     'sfem_transport_rhs': [ctypes.POINTER(TransportArgs), c_ptr],
     'sfem_transport_rhs_vjp': [ctypes.POINTER(TransportVjpArgs), c_ptr],
     'sfem_elasticity_local': [ctypes.POINTER(ElasticityArgs), c_ptr],
+    'sfem_elasticity_sens': [ctypes.POINTER(ElasticitySensArgs), c_ptr],
     'sfem_point_locate': [ctypes.POINTER(PointLocateArgs), c_ptr],
     'sfem_point_eval': [ctypes.POINTER(PointArgs), c_ptr],
     'sfem_point_eval_t': [ctypes.POINTER(PointArgs), c_ptr],

@@ -1359,6 +1359,47 @@ def elasticity_local(u_q, parts, host, ndim, P, wdet, lam, mu, rho=None,
   return out
 
 
+def elasticity_sens(u_q, v_q, parts, host, ndim, P, wdet, lambda0=0.0,
+                    want=(True, True, True)):
+  """Per-point sensitivities of v . (K + lambda0 M_rho) u with respect to
+  (lam, mu, rho) on a collocated grid (`sfem_elasticity_sens`): `u_q`, `v_q`
+  (E, P^d, d), `wdet` (E, P^d).  Returns (dlam, dmu, drho), (E, P^d) each,
+  None where `want` is false."""
+  u_q = u_q.contiguous()
+  dev = _dev(u_q)
+  E, n, d = u_q.shape
+  if d != ndim or n != P ** ndim:
+    raise ValueError(f'expected (E, {P ** ndim}, {ndim}) local values, got '
+                     f'{tuple(u_q.shape)}')
+  if wdet is None:
+    raise ValueError('elasticity_sens needs `wdet`')
+  want = tuple(bool(w) for w in want)
+  if len(want) != 3 or not any(want):
+    raise ValueError('`want` names (dlam, dmu, drho), at least one of them')
+  tensors = []
+  v_q = _field(v_q, 'second field', (E, n, d), u_q, 'displacement', tensors)
+  if v_q is None:
+    raise ValueError('elasticity_sens needs two fields')
+  wdet = _field(wdet, 'wdet', (E, n), u_q, 'displacement', tensors)
+  out = tuple(torch.zeros((E, n), dtype=u_q.dtype, device=dev) if w else None
+              for w in want)
+  args = _lib.ElasticitySensArgs(
+      u=u_q.data_ptr(), v=v_q.data_ptr(), wdet=wdet.data_ptr(),
+      dlam=_dptr(out[0]), dmu=_dptr(out[1]), drho=_dptr(out[2]),
+      lambda0=float(lambda0))
+  host = {k: _host(v, u_q.dtype) for k, v in host.items()}
+  args.num_elements, args.ndim, args.P = E, ndim, P
+  args.dtype = _dtype_code(u_q)
+  with torch.cuda.device(dev):
+    for part in parts:
+      for name, value in _launch_fields(part, host, 'kfac').items():
+        setattr(args, name, value)
+      _lib.check(_lib.load().sfem_elasticity_sens(ctypes.byref(args),
+                                                  _stream(dev)),
+                 'sfem_elasticity_sens')
+  return out
+
+
 # ------------------------------------------------------------ fields at points
 def point_locate(points, node_coords, elements, grid, nodes, bary, max_iter,
                  tol_xi, tol_x):

@@ -2271,6 +2271,9 @@ class ElasticityOperator:
   mask: torch.Tensor | None = None
   _wdet: torch.Tensor | None = None
   _diag: tuple | None = None
+  # (lame_lambda, lame_mu, density) as the caller passed them: `sensitivity`
+  # returns its gradients in these forms
+  coef_source: tuple = (None, None, None)
 
   @classmethod
   def create(cls, fespace, dirichlet_mask=None, *, lame_lambda, lame_mu,
@@ -2316,7 +2319,8 @@ class ElasticityOperator:
       mask = (m == 0).to(fespace.dtype).contiguous()
     parts = _grid_geometry_parts(fespace, _ops.stokes_setup, geometry)
     return cls(fespace=fespace, parts=parts, host=_host_tables(fespace, True),
-               lam=lam, mu=mu, rho=rho, mask=mask)
+               lam=lam, mu=mu, rho=rho, mask=mask,
+               coef_source=(lame_lambda, lame_mu, density))
 
   def point_weights(self):
     """W = w detJ (E, Q^d)."""
@@ -2358,6 +2362,37 @@ class ElasticityOperator:
 
   def linear_operator(self, lambda0=0.0):
     return lambda u: self.apply(u, lambda0)
+
+  def sensitivity(self, u, v, lambda0=0.0, want=(True, True, True)):
+    """The gradient of v . (K + lambda0 M_rho) u WITHOUT the Dirichlet mask
+    with respect to (lame_lambda, lame_mu, density), each in the form the
+    caller passed to `create` (`reduce_coefficient_gradient`): a scalar gives
+    a 0-dim tensor (the sum over all points), (E,) the sum over each
+    element's points, (E, Q^d) per-point values.  None for a callable, for an
+    absent density and where `want` is false.  `u`, `v`: nodal (N, d), dense
+    or component-major; they are gathered and interpolated to the quadrature
+    grid as in `apply_local`, then one launch of `sfem_elasticity_sens` per
+    part.  Nothing of size (E, Q^d, d, d) is stored."""
+    fes = self.fespace
+    mesh = fes.mesh
+    d = mesh.ndim
+    for w in (u, v):
+      if tuple(w.shape) != (mesh.num_nodes, d):
+        raise ValueError(f'expected ({mesh.num_nodes}, {d}) nodal '
+                         f'displacements, got {tuple(w.shape)}')
+    tensor = lambda s: s is not None and not _is_callable_source(s)
+    wanted = tuple(bool(w) and tensor(s)
+                   for w, s in zip(want, self.coef_source))
+    if not any(wanted):
+      return None, None, None
+    uq, vq = (fes._interpolate(_ops.gather_rows(
+        w.detach().to(fes.dtype).contiguous(), mesh.elements)).contiguous()
+              for w in (u, v))
+    grads = _ops.elasticity_sens(uq, vq, self.parts, self.host, d,
+                                 fes.quadrature.num_points,
+                                 self.point_weights(), lambda0, want=wanted)
+    return tuple(reduce_coefficient_gradient(g, s)
+                 for g, s in zip(grads, self.coef_source))
 
   def _component_factors(self, i):
     """Stored per-point factors of the scalar operator that is the diagonal

@@ -63,6 +63,65 @@ def _nodal(mesh, value, dtype, device):
   return v
 
 
+def _requires_grad(*values) -> bool:
+  return torch.is_grad_enabled() and any(
+      isinstance(v, torch.Tensor) and v.requires_grad for v in values)
+
+
+def _detached(v):
+  return v.detach() if isinstance(v, torch.Tensor) else v
+
+
+class _ElasticitySolve(torch.autograd.Function):
+  """`_solve` as one autograd node: the adjoint solve, the mass apply and the
+  coefficient sensitivities in `backward`."""
+
+  @staticmethod
+  def forward(ctx, body_force, lame_lambda, lame_mu, density, mesh,
+              boundary_conditions, kwargs, holder):
+    state = {}
+    u, info = _solve(mesh, _detached(body_force), boundary_conditions,
+                     lame_lambda=_detached(lame_lambda),
+                     lame_mu=_detached(lame_mu), density=_detached(density),
+                     return_info=True, _state=state, **kwargs)
+    holder['info'] = info
+    state['holder'] = holder
+    ctx.state = state
+    ctx.save_for_backward(u)
+    ctx.force_shape = (tuple(body_force.shape)
+                       if isinstance(body_force, torch.Tensor) else None)
+    ctx.like = [(v.dtype, v.device) if isinstance(v, torch.Tensor) else None
+                for v in (body_force, lame_lambda, lame_mu, density)]
+    return u
+
+  @staticmethod
+  @torch.autograd.function.once_differentiable
+  def backward(ctx, u_bar):
+    st = ctx.state
+    op, keep, l0 = st['op'], st['keep'], st['lambda0']
+    N, d = keep.shape
+    rhs = (u_bar.detach().to(keep.dtype) * keep).reshape(-1).contiguous()
+    lam, info = cg(st['A'], rhs, tol=st['rtol'], atol=st['atol'], M=st['M'])
+    st['adjoint_info'] = info
+    st['holder']['info']['adjoint'] = info
+    lam = lam.view(N, d)
+    need = ctx.needs_input_grad
+    grads = [None, None, None, None]
+    if need[0]:
+      g = st['Bf'](lam)
+      grads[0] = g.sum(dim=0) if ctx.force_shape == (d,) else g
+    if any(need[1:4]):
+      sens = op.sensitivity(ctx.saved_tensors[0], lam, l0,
+                            want=tuple(need[1:4]))
+      for n, g in enumerate(sens):
+        if need[1 + n] and g is not None:
+          grads[1 + n] = -g
+    for n, like in enumerate(ctx.like):
+      if grads[n] is not None and like is not None:
+        grads[n] = grads[n].to(dtype=like[0], device=like[1])
+    return (*grads, None, None, None, None)
+
+
 def solve_elasticity(mesh: Mesh, body_force,
                      boundary_conditions: Mapping[str, Tuple[BCType, object]],
                      *, lame_lambda, lame_mu, density=None,
@@ -89,7 +148,40 @@ def solve_elasticity(mesh: Mesh, body_force,
 
   `preconditioner`: None or 'jacobi' (the operator's assembled diagonal).
   `rtol` is relative to the norm of the lifted right-hand side; `info` is
-  CG's."""
+  CG's.
+
+  Autograd: the result is differentiable with respect to
+  `body_force` and to `lame_lambda`, `lame_mu` and `density` given as tensors
+  that require grad (scalar, (E,) or (E, Q^d); the gradient has the form
+  passed in).  Backward is one adjoint CG solve on the same masked operator
+  with the forward solve's `rtol`, `atol` and preconditioner, one launch of
+  the sensitivity kernel (`ElasticityOperator.sensitivity`) and one mass
+  apply; with `return_info` the info then also carries `adjoint`, the adjoint
+  solve's CG info.  Gradients with respect to Dirichlet values, tractions,
+  through callables and with respect to the mesh are not propagated, nor are
+  second derivatives.  When nothing requires grad the solve runs exactly as
+  without this feature and builds no autograd node."""
+  kwargs = dict(lambda0=lambda0, rtol=rtol, atol=atol,
+                preconditioner=preconditioner)
+  if not _requires_grad(body_force, lame_lambda, lame_mu, density):
+    return _solve(mesh, body_force, boundary_conditions,
+                  lame_lambda=lame_lambda, lame_mu=lame_mu, density=density,
+                  return_info=return_info, **kwargs)
+  holder = {}
+  u = _ElasticitySolve.apply(body_force, lame_lambda, lame_mu, density, mesh,
+                             boundary_conditions, kwargs, holder)
+  return (u, holder['info']) if return_info else u
+
+
+def _solve(mesh: Mesh, body_force,
+           boundary_conditions: Mapping[str, Tuple[BCType, object]],
+           *, lame_lambda, lame_mu, density=None,
+           lambda0: float = 0.0, rtol: float = 1e-8,
+           atol: float = 0.0, preconditioner=None,
+           return_info: bool = False, _state=None):
+  """The body of `solve_elasticity`.  `_state`: a dict that receives what the
+  adjoint solve needs (the operator, the mask, the preconditioner, the mass
+  apply)."""
   if preconditioner == 'pmg':
     raise NotImplementedError("preconditioner='pmg' for elasticity: the "
                               'V-cycle is built for the scalar operator')
@@ -169,6 +261,11 @@ def solve_elasticity(mesh: Mesh, body_force,
     M = JacobiPreconditioner(op.diagonal(lambda0).reshape(-1))
   w, info = cg(A, b, tol=rtol, atol=atol, M=M)
   u = w.view(N, d) + u_D
+  if _state is not None:
+    _state.update(op=op, keep=keep, A=A, M=M, rtol=rtol, atol=atol,
+                  lambda0=lambda0,
+                  Bf=lambda x: fespace.helmholtz_operator(None).apply(
+                      x.contiguous(), 1.0, 0.0))
   if return_info:
     return u, info
   return u
