@@ -13,9 +13,9 @@
 //   F[c][a] = sum_j Kw[a][j] S[c][j]
 //   out[e,m,c] = sum_a sum_q D_a[q,m] F[c][a](q) + lambda0 rho W u_c(m)
 //
-// elasticity_kernel is a sibling of stokes_convect_kernel (sfem_stokes.h): the
-// same lane mapping (lane (i, j) owns the points (*, i, j)), the same LDS
-// tensor pair, ElemCof, line_apply and HelmholtzTile.  What differs:
+// elasticity_kernel is a sibling of stokes_convect_kernel (sfem_stokes.h):
+// ElemCof, and the lane mapping and LDS derivative stage shared through the
+// macros of sfem_helmholtz.h (SFEM_PAIR_LINES_DM).  What differs:
 //   * the pointwise stage couples the components: it needs all DIM x DIM
 //     reference derivatives of a point at once.  The components pass one
 //     after another through the one LDS tensor pair and every lane takes the
@@ -64,11 +64,7 @@ template <typename T, int P, int DIM, int GM>
 __global__ void __launch_bounds__((HelmholtzTile<T, P, DIM>::BLOCK),
                                   (ElasticityBudget<T, P, DIM>::MINW))
 elasticity_kernel(ElasticityParams<T> ep, DMat<T, P> dm) {
-  using Tile = HelmholtzTile<T, P, DIM>;
-  constexpr int TPE = Tile::TPE, SA = Tile::SA, SB = Tile::SB;
-  constexpr int EPB = Tile::EPB, W = Tile::ELEM_WORDS;
-  constexpr int N = DIM == 3 ? P * P * P : P * P;
-  __shared__ T lds[2 * EPB * W];
+  SFEM_TILE_PREAMBLE(HelmholtzTile<T, P, DIM>);
   const StokesParams<T>& prm = ep.geo;
   SFEM_LANE_PROLOGUE(prm);
   ElemCof<T, P, DIM, GM> geom;
@@ -85,32 +81,9 @@ elasticity_kernel(ElasticityParams<T> ep, DMat<T, P> dm) {
     for (int a = 0; a < P; ++a)
       ua[a] = active ? ue[(int64_t)(t + a * TPE) * DIM + c] : T(0);
     line_apply<T, P, false>(dm, ua, g[c][0]);
-    if (lane_ok) {
-#pragma unroll
-      for (int a = 0; a < P; ++a) {
-        s0[a * SA + i * SB + j] = ua[a];
-        if (DIM == 3) s1[a * SA + i * SB + j] = ua[a];
-      }
-    }
+    SFEM_PAIR_SPREAD(ua);
     __syncthreads();
-    if (lane_ok) {  // last axis
-      T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
-      T x[P], y[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) x[m] = line[m];
-      line_apply<T, P, false>(dm, x, y);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m] = y[m];
-    }
-    if (DIM == 3 && lane_ok) {  // middle axis
-      T* line = s0 + i * SA + j;
-      T x[P], y[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-      line_apply<T, P, false>(dm, x, y);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m * SB] = y[m];
-    }
+    SFEM_PAIR_LINES_DM(false);
     __syncthreads();
 #pragma unroll
     for (int a = 0; a < P; ++a) {
@@ -177,24 +150,7 @@ elasticity_kernel(ElasticityParams<T> ep, DMat<T, P> dm) {
       }
     }
     __syncthreads();
-    if (lane_ok) {  // transposed derivative along the last axis, in place
-      T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
-      T x[P], y[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) x[m] = line[m];
-      line_apply<T, P, true>(dm, x, y);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m] = y[m];
-    }
-    if (DIM == 3 && lane_ok) {  // middle axis
-      T* line = s0 + i * SA + j;
-      T x[P], y[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-      line_apply<T, P, true>(dm, x, y);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m * SB] = y[m];
-    }
+    SFEM_PAIR_LINES_DM(true);   // the transposed derivatives, in place
     T dt0[P];
     line_apply<T, P, true>(dm, g[c][0], dt0);
     __syncthreads();

@@ -12,8 +12,8 @@
 // arrays indexed by element id, in the layout the forward kernel reads its
 // per-point coefficients in (lane t of slice a writes point a * TPE + t).
 //
-// elasticity_sens_kernel is a sibling of elasticity_kernel: the same lane
-// mapping, LDS tensor pair, ElemCof, line_apply and HelmholtzTile.  Holding
+// elasticity_sens_kernel is a sibling of elasticity_kernel: ElemCof and the
+// shared lane mapping and LDS derivative stage (sfem_helmholtz.h).  Holding
 // the DIM x DIM reference derivatives of both fields would take 2 DIM^2 P
 // reals per lane.  Row c of H depends on the DIM reference derivatives of
 // component c alone, so the components pass one after another:
@@ -63,12 +63,8 @@ template <typename T, int P, int DIM, int GM>
 __global__ void __launch_bounds__((HelmholtzTile<T, P, DIM>::BLOCK),
                                   (ElasticitySensBudget<T, P, DIM>::MINW))
 elasticity_sens_kernel(ElasticitySensParams<T> sp, DMat<T, P> dm) {
-  using Tile = HelmholtzTile<T, P, DIM>;
-  constexpr int TPE = Tile::TPE, SA = Tile::SA, SB = Tile::SB;
-  constexpr int EPB = Tile::EPB, W = Tile::ELEM_WORDS;
-  constexpr int N = DIM == 3 ? P * P * P : P * P;
+  SFEM_TILE_PREAMBLE(HelmholtzTile<T, P, DIM>);
   constexpr int NSYM = DIM * (DIM + 1) / 2;
-  __shared__ T lds[2 * EPB * W];
   const StokesParams<T>& prm = sp.geo;
   SFEM_LANE_PROLOGUE(prm);
   const bool want_l = sp.dlam != nullptr;
@@ -92,32 +88,9 @@ elasticity_sens_kernel(ElasticitySensParams<T> sp, DMat<T, P> dm) {
     // derivatives at (a, i, j) are left in s0 / s1
     auto derivatives = [&](const T (&x)[P], T (&dx0)[P]) {
       line_apply<T, P, false>(dm, x, dx0);
-      if (lane_ok) {
-#pragma unroll
-        for (int a = 0; a < P; ++a) {
-          s0[a * SA + i * SB + j] = x[a];
-          if (DIM == 3) s1[a * SA + i * SB + j] = x[a];
-        }
-      }
+      SFEM_PAIR_SPREAD(x);
       __syncthreads();
-      if (lane_ok) {  // last axis
-        T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
-        T xx[P], yy[P];
-#pragma unroll
-        for (int m = 0; m < P; ++m) xx[m] = line[m];
-        line_apply<T, P, false>(dm, xx, yy);
-#pragma unroll
-        for (int m = 0; m < P; ++m) line[m] = yy[m];
-      }
-      if (DIM == 3 && lane_ok) {  // middle axis
-        T* line = s0 + i * SA + j;
-        T xx[P], yy[P];
-#pragma unroll
-        for (int m = 0; m < P; ++m) xx[m] = line[m * SB];
-        line_apply<T, P, false>(dm, xx, yy);
-#pragma unroll
-        for (int m = 0; m < P; ++m) line[m * SB] = yy[m];
-      }
+      SFEM_PAIR_LINES_DM(false);
       __syncthreads();
     };
 

@@ -882,6 +882,17 @@ __device__ __forceinline__ void scatter_shared_sorted(
   }
 }
 
+// The tile constants and the LDS tensor pairs of an element kernel, for the
+// tile type given (helmholtz_kernel chooses its PAD, everyone else takes
+// HelmholtzTile<T, P, DIM>): Tile, TPE, SA, SB, EPB, W, N (nodes per element)
+// and `lds`, the names SFEM_LANE_PROLOGUE and the macros below expect.
+#define SFEM_TILE_PREAMBLE(...)                                               \
+  using Tile = __VA_ARGS__;                                                   \
+  constexpr int TPE = Tile::TPE, SA = Tile::SA, SB = Tile::SB;                \
+  constexpr int EPB = Tile::EPB, W = Tile::ELEM_WORDS;                        \
+  constexpr int N = DIM == 3 ? P * P * P : P * P;                             \
+  __shared__ T lds[2 * EPB * W]
+
 // Where a lane of an element kernel stands (every kernel on HelmholtzTile):
 // lane t = (i, j) of element `el` of the workgroup owns the nodes (*, i, j);
 // `e` is the element's id and s0 / s1 its pair of LDS tensors.  Expects TPE,
@@ -924,6 +935,66 @@ __device__ __forceinline__ void scatter_shared_sorted(
 #else
 #define SFEM_LINE_APPLY(PRM_, TR, X, Y) line_apply<T, P, TR>(dmat, X, Y)
 #endif
+// The same product for the ElemCof siblings (Stokes, transport, elasticity),
+// which take the by-value DMat `dm` at every order.
+#define SFEM_LINE_APPLY_DM(TR, X, Y) line_apply<T, P, TR>(dm, X, Y)
+
+// Spread: the lane copies its P values X[a], the nodes (a, i, j), into BOTH
+// tensors of the element's pair (2D: into s0), ahead of SFEM_PAIR_LINES.  The
+// caller's barrier follows.
+#define SFEM_PAIR_SPREAD(X)                                                   \
+  do {                                                                        \
+    if (lane_ok) {                                                            \
+      _Pragma("unroll") for (int a = 0; a < P; ++a) {                         \
+        s0[a * SA + i * SB + j] = (X)[a];                                     \
+        if (DIM == 3) s1[a * SA + i * SB + j] = (X)[a];                       \
+      }                                                                       \
+    }                                                                         \
+  } while (0)
+
+// The LDS derivative stage of every kernel on the HelmholtzTile lane mapping.
+// Lane (i, j) owns the line [i, j, *] of the LAST axis on s1 (2D: the line
+// [j, *] on s0) and, in 3D, the line [i, *, j] of the MIDDLE axis on s0.  It
+// reads each line into registers, multiplies it by D (TR: D^T) and writes the
+// product back over the line, so that afterwards s0 / s1 hold the axis-1 /
+// axis-2 derivative (TR: the transposed one) of what they held.  No lane
+// touches another lane's line, hence no barrier in between; every lane reads
+// and writes other lanes' nodes, hence the CALLER puts a barrier before the
+// stage (after the spread or the pointwise stage that filled the pair) and one
+// after it (before lanes read their own nodes (a, i, j) again).
+//
+// A macro like the two above, for the same reason.  Measured with
+// scripts/device_code_digest.py: as a force-inlined function template taking
+// the line product as a callable, 9 of the 33 kernels of
+// sfem_elasticity_f64_3d (P = 2, 6, 7) came out with renumbered registers and
+// reordered instructions (register, scratch and spill counts equal; the
+// transport and 2D units byte-identical); as this macro every kernel of every
+// unit is byte-identical to its open-coded text.
+//
+// SFEM_PAIR_LINES(PRM, TR): the product is SFEM_LINE_APPLY(PRM, TR, x, y)
+// (helmholtz_kernel, the advective and the sensitivity kernel);
+// SFEM_PAIR_LINES_DM(TR): it is line_apply<T, P, TR>(dm, x, y) (the ElemCof
+// siblings).  Expect s0, s1, i, j, lane_ok, SA and SB in scope.
+#define SFEM_PAIR_LINES_WITH(APPLY_, ...)                                     \
+  do {                                                                        \
+    if (lane_ok) { /* last axis: the line [i, j, *] (3D) / [j, *] */          \
+      T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);              \
+      T xl[P], yl[P];                                                         \
+      _Pragma("unroll") for (int m = 0; m < P; ++m) xl[m] = line[m];          \
+      APPLY_(__VA_ARGS__, xl, yl);                                            \
+      _Pragma("unroll") for (int m = 0; m < P; ++m) line[m] = yl[m];          \
+    }                                                                         \
+    if (DIM == 3 && lane_ok) { /* middle axis: the line [i, *, j] */          \
+      T* line = s0 + i * SA + j;                                              \
+      T xl[P], yl[P];                                                         \
+      _Pragma("unroll") for (int m = 0; m < P; ++m) xl[m] = line[m * SB];     \
+      APPLY_(__VA_ARGS__, xl, yl);                                            \
+      _Pragma("unroll") for (int m = 0; m < P; ++m) line[m * SB] = yl[m];     \
+    }                                                                         \
+  } while (0)
+#define SFEM_PAIR_LINES(PRM_, TR) \
+  SFEM_PAIR_LINES_WITH(SFEM_LINE_APPLY, PRM_, TR)
+#define SFEM_PAIR_LINES_DM(TR) SFEM_PAIR_LINES_WITH(SFEM_LINE_APPLY_DM, TR)
 
 // SORTED: the sorted shared scatter below, its own instantiation (compiled
 // together with the slot-order scatter it cost registers in both).
@@ -947,11 +1018,7 @@ helmholtz_kernel(typename HelmholtzPrm<T, COEF>::type prm, DMat<T, P> dm) {
   // unpadded LDS rows for the light (affine) kernels at P = 8, see the tile
   constexpr bool PAD =
       !(GS && SCALAR && DIM == 3 && P == 8 && GM == GEO_AFFINE);
-  using Tile = HelmholtzTile<T, P, DIM, PAD>;
-  constexpr int TPE = Tile::TPE, SA = Tile::SA, SB = Tile::SB;
-  constexpr int EPB = Tile::EPB, W = Tile::ELEM_WORDS;
-  constexpr int N = DIM == 3 ? P * P * P : P * P;        // nodes per element
-  __shared__ T lds[2 * EPB * W];
+  SFEM_TILE_PREAMBLE(HelmholtzTile<T, P, DIM, PAD>);
 
   SFEM_LANE_PROLOGUE(prm);
   const DMat<T, P>& dmat = dm;
@@ -1048,32 +1115,9 @@ helmholtz_kernel(typename HelmholtzPrm<T, COEF>::type prm, DMat<T, P> dm) {
     if (has_stiff) {
       T d0[P];   // derivative along axis 0 at (a, i, j)
       SFEM_LINE_APPLY(PRM, false, ua, d0);
-      if (lane_ok) {
-#pragma unroll
-        for (int a = 0; a < P; ++a) {
-          s0[a * SA + i * SB + j] = ua[a];
-          if (DIM == 3) s1[a * SA + i * SB + j] = ua[a];
-        }
-      }
+      SFEM_PAIR_SPREAD(ua);
       __syncthreads();
-      if (lane_ok) {  // last axis: lane owns the line [i, j, *] (3D) / [j, *]
-        T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
-        T x[P], y[P];
-#pragma unroll
-        for (int m = 0; m < P; ++m) x[m] = line[m];
-        SFEM_LINE_APPLY(PRM, false, x, y);
-#pragma unroll
-        for (int m = 0; m < P; ++m) line[m] = y[m];
-      }
-      if (DIM == 3 && lane_ok) {  // middle axis: lane owns the line [i, *, j]
-        T* line = s0 + i * SA + j;
-        T x[P], y[P];
-#pragma unroll
-        for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-        SFEM_LINE_APPLY(PRM, false, x, y);
-#pragma unroll
-        for (int m = 0; m < P; ++m) line[m * SB] = y[m];
-      }
+      SFEM_PAIR_LINES(PRM, false);
       __syncthreads();
       // pointwise: w = G * (reference gradient), G symmetric; the mass term
       // rides along when both are requested
@@ -1120,24 +1164,7 @@ helmholtz_kernel(typename HelmholtzPrm<T, COEF>::type prm, DMat<T, P> dm) {
         }
       }
       __syncthreads();
-      if (lane_ok) {  // transposed derivative along the last axis, in place
-        T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
-        T x[P], y[P];
-#pragma unroll
-        for (int m = 0; m < P; ++m) x[m] = line[m];
-        SFEM_LINE_APPLY(PRM, true, x, y);
-#pragma unroll
-        for (int m = 0; m < P; ++m) line[m] = y[m];
-      }
-      if (DIM == 3 && lane_ok) {
-        T* line = s0 + i * SA + j;
-        T x[P], y[P];
-#pragma unroll
-        for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-        SFEM_LINE_APPLY(PRM, true, x, y);
-#pragma unroll
-        for (int m = 0; m < P; ++m) line[m * SB] = y[m];
-      }
+      SFEM_PAIR_LINES(PRM, true);   // the transposed derivatives, in place
       T dt0[P];
       SFEM_LINE_APPLY(PRM, true, w0, dt0);
       __syncthreads();

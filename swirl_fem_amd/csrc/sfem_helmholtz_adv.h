@@ -12,11 +12,11 @@
 // derivative line.
 //
 // helmholtz_adv_kernel is a sibling of helmholtz_kernel (sfem_helmholtz.h): the
-// same lane mapping (one line of P nodes per lane, one element per wave or
-// workgroup), the same LDS tensor pair, the same device functions (ElemGeom,
-// line_apply*, HelmholtzTile).  It is kept apart so that the constant- and
-// variable-coefficient instantiations compile from code this file never
-// touches.  Scalar fields, slot-order scatter; kappa / sigma per point or null
+// same lane mapping and LDS derivative stage (SFEM_TILE_PREAMBLE,
+// SFEM_LANE_PROLOGUE, SFEM_PAIR_SPREAD, SFEM_PAIR_LINES there) and ElemGeom.
+// It is kept apart so that the constant- and variable-coefficient
+// instantiations compile from code this file never touches.
+// Scalar fields, slot-order scatter; kappa / sigma per point or null
 // (one form bounds the number of instantiations: Python expands scalars and
 // per-element values).  The derivative lines are always computed (C_b needs
 // them when lambda1 = 0 as well); lambda0 is tested at run time.
@@ -50,11 +50,7 @@ __global__ void __launch_bounds__((HelmholtzTile<T, P, DIM>::BLOCK),
                                   (HelmholtzTile<T, P, DIM>::MINW))
 helmholtz_adv_kernel(HelmholtzAdvParams<T> prm, DMat<T, P> dm) {
   using PRM = HelmholtzAdvParams<T>;
-  using Tile = HelmholtzTile<T, P, DIM, true>;
-  constexpr int TPE = Tile::TPE, SA = Tile::SA, SB = Tile::SB;
-  constexpr int EPB = Tile::EPB, W = Tile::ELEM_WORDS;
-  constexpr int N = DIM == 3 ? P * P * P : P * P;        // nodes per element
-  __shared__ T lds[2 * EPB * W];
+  SFEM_TILE_PREAMBLE(HelmholtzTile<T, P, DIM>);
 
   SFEM_LANE_PROLOGUE(prm);
   const DMat<T, P>& dmat = dm;
@@ -104,32 +100,9 @@ helmholtz_adv_kernel(HelmholtzAdvParams<T> prm, DMat<T, P> dm) {
   }
   T d0[P];   // derivative along axis 0 at (a, i, j)
   SFEM_LINE_APPLY(PRM, false, ua, d0);
-  if (lane_ok) {
-#pragma unroll
-    for (int a = 0; a < P; ++a) {
-      s0[a * SA + i * SB + j] = ua[a];
-      if (DIM == 3) s1[a * SA + i * SB + j] = ua[a];
-    }
-  }
+  SFEM_PAIR_SPREAD(ua);
   __syncthreads();
-  if (lane_ok) {  // last axis: lane owns the line [i, j, *] (3D) / [j, *]
-    T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
-    T x[P], y[P];
-#pragma unroll
-    for (int m = 0; m < P; ++m) x[m] = line[m];
-    SFEM_LINE_APPLY(PRM, false, x, y);
-#pragma unroll
-    for (int m = 0; m < P; ++m) line[m] = y[m];
-  }
-  if (DIM == 3 && lane_ok) {  // middle axis: lane owns the line [i, *, j]
-    T* line = s0 + i * SA + j;
-    T x[P], y[P];
-#pragma unroll
-    for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-    SFEM_LINE_APPLY(PRM, false, x, y);
-#pragma unroll
-    for (int m = 0; m < P; ++m) line[m * SB] = y[m];
-  }
+  SFEM_PAIR_LINES(PRM, false);
   __syncthreads();
   // pointwise: the advective and mass terms go to acc, w = k G * (reference
   // gradient) replaces the gradient
@@ -180,24 +153,7 @@ helmholtz_adv_kernel(HelmholtzAdvParams<T> prm, DMat<T, P> dm) {
     }
   }
   __syncthreads();
-  if (lane_ok) {  // transposed derivative along the last axis, in place
-    T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
-    T x[P], y[P];
-#pragma unroll
-    for (int m = 0; m < P; ++m) x[m] = line[m];
-    SFEM_LINE_APPLY(PRM, true, x, y);
-#pragma unroll
-    for (int m = 0; m < P; ++m) line[m] = y[m];
-  }
-  if (DIM == 3 && lane_ok) {
-    T* line = s0 + i * SA + j;
-    T x[P], y[P];
-#pragma unroll
-    for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-    SFEM_LINE_APPLY(PRM, true, x, y);
-#pragma unroll
-    for (int m = 0; m < P; ++m) line[m * SB] = y[m];
-  }
+  SFEM_PAIR_LINES(PRM, true);   // the transposed derivatives, in place
   T dt0[P];
   SFEM_LINE_APPLY(PRM, true, w0, dt0);
   __syncthreads();

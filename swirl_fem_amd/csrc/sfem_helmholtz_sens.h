@@ -10,8 +10,8 @@
 // WITHOUT any coefficient folded in.  No gather and no scatter: inputs and
 // outputs are (E, N[, DIM]) arrays indexed by element id.
 //
-// helmholtz_sens_kernel shares lane mapping, LDS tensor pair and device
-// functions (ElemGeom, line_apply*, HelmholtzTile) with helmholtz_adv_kernel.
+// helmholtz_sens_kernel is a sibling of helmholtz_adv_kernel: lane mapping and
+// LDS derivative stage are the shared macros of sfem_helmholtz.h.
 // The derivative stage runs once per field: the DIM * P derivatives of u are
 // kept in registers while those of lam go through the LDS pair again, so a
 // lane holds 6 P values (u, lam, three derivatives of u, the axis-0 derivative
@@ -47,11 +47,7 @@ __global__ void __launch_bounds__((HelmholtzTile<T, P, DIM>::BLOCK),
                                   (SensTile<T, P>::MINW))
 helmholtz_sens_kernel(HelmholtzSensParams<T> prm, DMat<T, P> dm) {
   using PRM = HelmholtzSensParams<T>;
-  using Tile = HelmholtzTile<T, P, DIM, true>;
-  constexpr int TPE = Tile::TPE, SA = Tile::SA, SB = Tile::SB;
-  constexpr int EPB = Tile::EPB, W = Tile::ELEM_WORDS;
-  constexpr int N = DIM == 3 ? P * P * P : P * P;        // points per element
-  __shared__ T lds[2 * EPB * W];
+  SFEM_TILE_PREAMBLE(HelmholtzTile<T, P, DIM>);
 
   SFEM_LANE_PROLOGUE(prm);
   const DMat<T, P>& dmat = dm;
@@ -76,32 +72,9 @@ helmholtz_sens_kernel(HelmholtzSensParams<T> prm, DMat<T, P> dm) {
   // (a, i, j) are left in s0 / s1
   auto derivatives = [&](const T (&x)[P], T (&dx0)[P]) {
     SFEM_LINE_APPLY(PRM, false, x, dx0);
-    if (lane_ok) {
-#pragma unroll
-      for (int a = 0; a < P; ++a) {
-        s0[a * SA + i * SB + j] = x[a];
-        if (DIM == 3) s1[a * SA + i * SB + j] = x[a];
-      }
-    }
+    SFEM_PAIR_SPREAD(x);
     __syncthreads();
-    if (lane_ok) {  // last axis: lane owns the line [i, j, *] (3D) / [j, *]
-      T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
-      T xx[P], yy[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) xx[m] = line[m];
-      SFEM_LINE_APPLY(PRM, false, xx, yy);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m] = yy[m];
-    }
-    if (DIM == 3 && lane_ok) {  // middle axis: lane owns the line [i, *, j]
-      T* line = s0 + i * SA + j;
-      T xx[P], yy[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) xx[m] = line[m * SB];
-      SFEM_LINE_APPLY(PRM, false, xx, yy);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m * SB] = yy[m];
-    }
+    SFEM_PAIR_LINES(PRM, false);
     __syncthreads();
   };
 

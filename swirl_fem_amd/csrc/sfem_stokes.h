@@ -299,12 +299,8 @@ __device__ __forceinline__ void cof_fence(ElemCof<T, P, DIM, GM>& g) {
 }
 
 #define SFEM_STOKES_PROLOGUE                                                  \
-  using Tile = HelmholtzTile<T, P, DIM>;                                      \
-  constexpr int TPE = Tile::TPE, SA = Tile::SA, SB = Tile::SB;                \
-  constexpr int EPB = Tile::EPB, W = Tile::ELEM_WORDS;                        \
-  constexpr int N = DIM == 3 ? P * P * P : P * P;                             \
+  SFEM_TILE_PREAMBLE(HelmholtzTile<T, P, DIM>);                               \
   constexpr int NP = DIM == 3 ? PP * PP * PP : PP * PP;                       \
-  __shared__ T lds[2 * EPB * W];                                              \
   SFEM_LANE_PROLOGUE(prm);                                                    \
   const int64_t ns = prm.node_stride, ks = prm.comp_stride;                   \
   ElemCof<T, P, DIM, GM> geom;                                                \
@@ -350,32 +346,9 @@ stokes_div_kernel(StokesParams<T> prm, DMat<T, P> dm, IMat<T, P, PP> im) {
       ua[a] = v;
     }
     line_apply<T, P, false>(dm, ua, d0);
-    if (lane_ok) {
-#pragma unroll
-      for (int a = 0; a < P; ++a) {
-        s0[a * SA + i * SB + j] = ua[a];
-        if (DIM == 3) s1[a * SA + i * SB + j] = ua[a];
-      }
-    }
+    SFEM_PAIR_SPREAD(ua);
     __syncthreads();
-    if (lane_ok) {  // last axis
-      T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
-      T x[P], y[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) x[m] = line[m];
-      line_apply<T, P, false>(dm, x, y);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m] = y[m];
-    }
-    if (DIM == 3 && lane_ok) {  // middle axis
-      T* line = s0 + i * SA + j;
-      T x[P], y[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-      line_apply<T, P, false>(dm, x, y);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m * SB] = y[m];
-    }
+    SFEM_PAIR_LINES_DM(false);
     __syncthreads();
     if (active) {
 #pragma unroll
@@ -535,24 +508,7 @@ stokes_grad_t_kernel(StokesParams<T> prm, DMat<T, P> dm, IMat<T, P, PP> im) {
       }
     }
     __syncthreads();
-    if (lane_ok) {
-      T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
-      T x[P], y[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) x[m] = line[m];
-      line_apply<T, P, true>(dm, x, y);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m] = y[m];
-    }
-    if (DIM == 3 && lane_ok) {
-      T* line = s0 + i * SA + j;
-      T x[P], y[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-      line_apply<T, P, true>(dm, x, y);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m * SB] = y[m];
-    }
+    SFEM_PAIR_LINES_DM(true);   // the transposed derivatives, in place
     T dt0[P];
     line_apply<T, P, true>(dm, w0, dt0);
     __syncthreads();
@@ -697,24 +653,7 @@ stokes_e_first_kernel(StokesParams<T> prm, DMat<T, P> dm, IMat<T, P, PP> im) {
       }
     }
     __syncthreads();
-    if (lane_ok) {
-      T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
-      T x[P], y[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) x[m] = line[m];
-      line_apply<T, P, true>(dm, x, y);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m] = y[m];
-    }
-    if (DIM == 3 && lane_ok) {
-      T* line = s0 + i * SA + j;
-      T x[P], y[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-      line_apply<T, P, true>(dm, x, y);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m * SB] = y[m];
-    }
+    SFEM_PAIR_LINES_DM(true);   // the transposed derivatives, in place
     T ua[P];
     line_apply<T, P, true>(dm, w0, ua);
     __syncthreads();
@@ -762,32 +701,9 @@ stokes_e_first_kernel(StokesParams<T> prm, DMat<T, P> dm, IMat<T, P, PP> im) {
     // ---- D of the complete part, component c (stokes_div_kernel)
     T d0[P];
     line_apply<T, P, false>(dm, ua, d0);
-    if (lane_ok) {
-#pragma unroll
-      for (int a = 0; a < P; ++a) {
-        s0[a * SA + i * SB + j] = ua[a];
-        if (DIM == 3) s1[a * SA + i * SB + j] = ua[a];
-      }
-    }
+    SFEM_PAIR_SPREAD(ua);
     __syncthreads();
-    if (lane_ok) {
-      T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
-      T x[P], y[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) x[m] = line[m];
-      line_apply<T, P, false>(dm, x, y);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m] = y[m];
-    }
-    if (DIM == 3 && lane_ok) {
-      T* line = s0 + i * SA + j;
-      T x[P], y[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-      line_apply<T, P, false>(dm, x, y);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m * SB] = y[m];
-    }
+    SFEM_PAIR_LINES_DM(false);
     __syncthreads();
     if (active) {
 #pragma unroll
@@ -861,11 +777,7 @@ template <typename T, int P, int DIM, int GM>
 __global__ void __launch_bounds__((HelmholtzTile<T, P, DIM>::BLOCK),
                                   (HelmholtzTile<T, P, DIM>::MINW))
 stokes_convect_kernel(StokesParams<T> prm, DMat<T, P> dm) {
-  using Tile = HelmholtzTile<T, P, DIM>;
-  constexpr int TPE = Tile::TPE, SA = Tile::SA, SB = Tile::SB;
-  constexpr int EPB = Tile::EPB, W = Tile::ELEM_WORDS;
-  constexpr int N = DIM == 3 ? P * P * P : P * P;
-  __shared__ T lds[2 * EPB * W];
+  SFEM_TILE_PREAMBLE(HelmholtzTile<T, P, DIM>);
   SFEM_LANE_PROLOGUE(prm);
   ElemCof<T, P, DIM, GM> geom;
   geom.init(prm, dm, e, active, i, j, t);
@@ -884,32 +796,9 @@ stokes_convect_kernel(StokesParams<T> prm, DMat<T, P> dm) {
     cof_fence(geom);
     T d0[P];
     line_apply<T, P, false>(dm, uall[c], d0);
-    if (lane_ok) {
-#pragma unroll
-      for (int a = 0; a < P; ++a) {
-        s0[a * SA + i * SB + j] = uall[c][a];
-        if (DIM == 3) s1[a * SA + i * SB + j] = uall[c][a];
-      }
-    }
+    SFEM_PAIR_SPREAD(uall[c]);
     __syncthreads();
-    if (lane_ok) {  // last axis
-      T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
-      T x[P], y[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) x[m] = line[m];
-      line_apply<T, P, false>(dm, x, y);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m] = y[m];
-    }
-    if (DIM == 3 && lane_ok) {  // middle axis
-      T* line = s0 + i * SA + j;
-      T x[P], y[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-      line_apply<T, P, false>(dm, x, y);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m * SB] = y[m];
-    }
+    SFEM_PAIR_LINES_DM(false);
     __syncthreads();
     if (active) {
 #pragma unroll

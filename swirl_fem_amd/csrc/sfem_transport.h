@@ -11,8 +11,8 @@
 // stepper passes mass_coef = -bdf[j] / dt and conv_coef = -ext[j].
 //
 // transport_rhs_kernel is a sibling of stokes_convect_kernel (sfem_stokes.h):
-// the same lane mapping (lane (i, j) owns the points (*, i, j)), the same LDS
-// tensor pair, ElemCof, line_apply and HelmholtzTile.  What differs:
+// ElemCof, and the lane mapping and LDS derivative stage shared through the
+// macros of sfem_helmholtz.h (SFEM_PAIR_LINES_DM).  What differs:
 //   * the differentiated field is a scalar and the advecting velocity is data
 //     of its own, so a level's velocity is needed at the pointwise stage only
 //     and is read there, DIM reals per point, instead of being held as
@@ -48,11 +48,7 @@ template <typename T, int P, int DIM, int GM>
 __global__ void __launch_bounds__((HelmholtzTile<T, P, DIM>::BLOCK),
                                   (HelmholtzTile<T, P, DIM>::MINW))
 transport_rhs_kernel(TransportParams<T> tp, DMat<T, P> dm) {
-  using Tile = HelmholtzTile<T, P, DIM>;
-  constexpr int TPE = Tile::TPE, SA = Tile::SA, SB = Tile::SB;
-  constexpr int EPB = Tile::EPB, W = Tile::ELEM_WORDS;
-  constexpr int N = DIM == 3 ? P * P * P : P * P;
-  __shared__ T lds[2 * EPB * W];
+  SFEM_TILE_PREAMBLE(HelmholtzTile<T, P, DIM>);
   const StokesParams<T>& prm = tp.geo;
   SFEM_LANE_PROLOGUE(prm);
   ElemCof<T, P, DIM, GM> geom;
@@ -84,32 +80,9 @@ transport_rhs_kernel(TransportParams<T> tp, DMat<T, P> dm) {
     cof_fence(geom);
     T d0[P];
     line_apply<T, P, false>(dm, ua, d0);
-    if (lane_ok) {
-#pragma unroll
-      for (int a = 0; a < P; ++a) {
-        s0[a * SA + i * SB + j] = ua[a];
-        if (DIM == 3) s1[a * SA + i * SB + j] = ua[a];
-      }
-    }
+    SFEM_PAIR_SPREAD(ua);
     __syncthreads();
-    if (lane_ok) {  // last axis
-      T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
-      T x[P], y[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) x[m] = line[m];
-      line_apply<T, P, false>(dm, x, y);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m] = y[m];
-    }
-    if (DIM == 3 && lane_ok) {  // middle axis
-      T* line = s0 + i * SA + j;
-      T x[P], y[P];
-#pragma unroll
-      for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-      line_apply<T, P, false>(dm, x, y);
-#pragma unroll
-      for (int m = 0; m < P; ++m) line[m * SB] = y[m];
-    }
+    SFEM_PAIR_LINES_DM(false);
     __syncthreads();
     if (active) {
 #pragma unroll

@@ -11,10 +11,10 @@
 //   T_bar_j[q]    = m_j W[q] lam[q] + c_j sum_a (D_a^T (U_j,a . lam))[q]
 //   u_bar_j[q][c] = c_j lam[q] sum_a Kw[a][c][q] (D_a T_j)[q]
 //
-// transport_vjp_kernel is a sibling of transport_rhs_kernel: the same lane
-// mapping (lane (i, j) owns the points (*, i, j)), the same LDS tensor pair,
-// ElemCof with cof_fence, line_apply and HelmholtzTile, the same AFFINE /
-// MULTILINEAR / POINT launches.  Per level:
+// transport_vjp_kernel is a sibling of transport_rhs_kernel: ElemCof with
+// cof_fence, the shared lane mapping and LDS derivative stage
+// (SFEM_PAIR_LINES_DM, sfem_helmholtz.h), the same AFFINE / MULTILINEAR /
+// POINT launches.  Per level:
 //   1. (u_bar wanted) load T_j and run the forward derivative stage: the
 //      axis-0 derivative stays in registers, axes 1 and 2 are left in s0, s1;
 //   2. pointwise, one cofactor evaluation per point: u_bar from the three
@@ -67,11 +67,7 @@ template <typename T, int P, int DIM, int GM>
 __global__ void __launch_bounds__((HelmholtzTile<T, P, DIM>::BLOCK),
                                   (VjpTile<T, P>::MINW))
 transport_vjp_kernel(TransportVjpParams<T> tp, DMat<T, P> dm) {
-  using Tile = HelmholtzTile<T, P, DIM>;
-  constexpr int TPE = Tile::TPE, SA = Tile::SA, SB = Tile::SB;
-  constexpr int EPB = Tile::EPB, W = Tile::ELEM_WORDS;
-  constexpr int N = DIM == 3 ? P * P * P : P * P;
-  __shared__ T lds[2 * EPB * W];
+  SFEM_TILE_PREAMBLE(HelmholtzTile<T, P, DIM>);
   const StokesParams<T>& prm = tp.geo;
   SFEM_LANE_PROLOGUE(prm);
   ElemCof<T, P, DIM, GM> geom;
@@ -125,32 +121,9 @@ transport_vjp_kernel(TransportVjpParams<T> tp, DMat<T, P> dm) {
 #pragma unroll
       for (int a = 0; a < P; ++a) ua[a] = active ? te[t + a * TPE] : T(0);
       line_apply<T, P, false>(dm, ua, d0);
-      if (lane_ok) {
-#pragma unroll
-        for (int a = 0; a < P; ++a) {
-          s0[a * SA + i * SB + j] = ua[a];
-          if (DIM == 3) s1[a * SA + i * SB + j] = ua[a];
-        }
-      }
+      SFEM_PAIR_SPREAD(ua);
       __syncthreads();
-      if (lane_ok) {  // last axis
-        T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
-        T x[P], y[P];
-#pragma unroll
-        for (int m = 0; m < P; ++m) x[m] = line[m];
-        line_apply<T, P, false>(dm, x, y);
-#pragma unroll
-        for (int m = 0; m < P; ++m) line[m] = y[m];
-      }
-      if (DIM == 3 && lane_ok) {  // middle axis
-        T* line = s0 + i * SA + j;
-        T x[P], y[P];
-#pragma unroll
-        for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-        line_apply<T, P, false>(dm, x, y);
-#pragma unroll
-        for (int m = 0; m < P; ++m) line[m * SB] = y[m];
-      }
+      SFEM_PAIR_LINES_DM(false);
       __syncthreads();
     }
     // pointwise: u_bar out, the fluxes over the derivatives this lane read
@@ -206,24 +179,7 @@ transport_vjp_kernel(TransportVjpParams<T> tp, DMat<T, P> dm) {
     }
     if (dT) {
       __syncthreads();
-      if (lane_ok) {  // transposed derivative along the last axis, in place
-        T* line = (DIM == 3 ? s1 + i * SA + j * SB : s0 + j * SA);
-        T x[P], y[P];
-#pragma unroll
-        for (int m = 0; m < P; ++m) x[m] = line[m];
-        line_apply<T, P, true>(dm, x, y);
-#pragma unroll
-        for (int m = 0; m < P; ++m) line[m] = y[m];
-      }
-      if (DIM == 3 && lane_ok) {  // middle axis
-        T* line = s0 + i * SA + j;
-        T x[P], y[P];
-#pragma unroll
-        for (int m = 0; m < P; ++m) x[m] = line[m * SB];
-        line_apply<T, P, true>(dm, x, y);
-#pragma unroll
-        for (int m = 0; m < P; ++m) line[m * SB] = y[m];
-      }
+      SFEM_PAIR_LINES_DM(true);   // the transposed derivatives, in place
       T dt0[P];
       line_apply<T, P, true>(dm, f0, dt0);
       __syncthreads();
