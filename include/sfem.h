@@ -385,6 +385,14 @@ int sfem_facet_table_build(const int32_t* elements, const uint8_t* dirichlet,
  * the first facet launch and refuses to continue on a mismatch.              */
 int sfem_kernarg_selftest(int32_t* bad, sfem_stream_t stream);
 
+/* 1 if a chain launch (chain_offsets set) on a field of `field_bytes` bytes
+ * touches the next element's nodes one compute phase before it gathers them,
+ * else 0.  Decided per launch from the environment variable SFEM_CHAIN_TOUCH:
+ * unset or "0" never (the default), "1" always, "auto" from 256 MiB on
+ * (fields that do not stay in the caches between two kernels).  The results
+ * do not depend on it.                                                       */
+int sfem_chain_touch_enabled(int64_t field_bytes);
+
 /* geo_elem (E, 24) of affine elements -> geo_const (E, 8) =
  * { G00, G01, G02, G11, G12, G22, detJ, box } with G = detJ J^-1 J^-T (no
  * quadrature weight) and box = 1 when |G01|, |G02|, |G12| <= box_tol *

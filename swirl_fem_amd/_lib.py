@@ -272,6 +272,7 @@ SIGNATURES = {
     'sfem_cg_update_r_layered': [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i32,
                                  c_ptr, c_ptr, c_ptr, c_i32, c_i32, c_ptr],
     'sfem_kernarg_selftest': [c_ptr, c_ptr],
+    'sfem_chain_touch_enabled': [c_i64],
     'sfem_fdm_solve': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i32,
                        c_i32, c_i32, c_ptr],
     'sfem_fdm_solve_sums': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,

@@ -614,6 +614,10 @@ int sfem_kernarg_selftest(int32_t* bad, sfem_stream_t stream) {
   return SFEM_OK;
 }
 
+int sfem_chain_touch_enabled(int64_t field_bytes) {
+  return chain_touch_enabled(field_bytes) ? 1 : 0;
+}
+
 int sfem_facet_table_build(const int32_t* elements, const uint8_t* dirichlet,
                            const int32_t* multiplicity, int32_t* table,
                            uint8_t* ok, int64_t num_elements,

@@ -76,6 +76,10 @@ struct FacetParams {
   // so all results leave as plain stores; the consumer adds the layers up
   // (`sfem_cg_update_r_layered`, `sfem_fold_layers`).  Scalar fields.
   int layered;
+  // chain launches: != 0 = the wave touches the next element's nodes one
+  // compute phase before it gathers them (facet_touch; set by the launcher
+  // from SFEM_CHAIN_TOUCH, see chain_touch_enabled)
+  int touch;
   // layered launches: > 0 = `dot_out` holds this many doubles, one per wave of
   // the launch; every wave STORES its partial sum of u . out at its own index
   // (nothing accumulated, nothing to clear: the sum over the slots in index
@@ -274,6 +278,55 @@ __device__ __forceinline__ T* facet_node(T* base, uint32_t code) {
     return (T*)((const char*)base + off);
   }
   return base + (code & SFEM_IDX_MASK);
+}
+
+// A touch: a load of node `code` whose result nobody reads, issued a compute
+// phase before the real gather so that the gather finds its lines in L2 (or
+// merges with the fill on its way).  Same address forms as facet_node.  The
+// load is the direct-to-LDS form: it has no register destination (nothing the
+// register allocator could hand on while the load is in flight) and drops its
+// four bytes per lane into `dump_lds`, the LDS byte address of 256 bytes that
+// nobody reads.  The compiler does not count these loads; they are older than
+// any load it waits for afterwards and loads return in order, so its own waits
+// stay sufficient.  M0 (the LDS base of such a load) is the compiler's: saved
+// and restored inside the statement.
+template <typename T, bool OFF32>
+__device__ __forceinline__ void facet_touch(uint32_t dump_lds, const T* base,
+                                            uint32_t code) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint32_t keep;
+  if (OFF32) {
+    const uint32_t off = code << (sizeof(T) == 8 ? 3 : 2);
+    asm volatile(
+        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
+        "global_load_lds_dword %2, %3\n\ts_mov_b32 m0, %0"
+        : "=&s"(keep) : "s"(dump_lds), "v"(off), "s"(base));
+  } else {
+    const T* p = base + (code & SFEM_IDX_MASK);
+    asm volatile(
+        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
+        "global_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
+        : "=&s"(keep) : "s"(dump_lds), "v"(p));
+  }
+#endif
+}
+
+// Byte address of a __shared__ object inside the workgroup's LDS.
+__device__ __forceinline__ uint32_t lds_byte_address(const void* shared) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (uint32_t)(uintptr_t)(
+      const __attribute__((address_space(3))) void*)shared;
+#else
+  return 0;
+#endif
+}
+
+// After the last touch and before the wave gives its LDS back: none of them
+// may still be on its way.
+__device__ __forceinline__ void facet_touch_drain() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("s_waitcnt vmcnt(0)");
+#endif
 }
 
 // Per-lane connectivity of one element: the lane's nodes in the three slice
@@ -986,6 +1039,9 @@ helmholtz_chain_kernel(FacetParams<T> prm, typename ELEM::Mat dm) {
   const T wij = w.template wij<T>(kdm);
   double udot = 0.0;
   T carry = T(0);
+  // where the touches land (facet_touch): 4 bytes per lane, never read
+  __shared__ uint32_t touch_dump[64];
+  const uint32_t dump_lds = lds_byte_address(touch_dump);
   {
   FL fl, fn;
   typename FL::Raw traw;
@@ -1006,6 +1062,18 @@ helmholtz_chain_kernel(FacetParams<T> prm, typename ELEM::Mat dm) {
     if (has_succ) {    // requested one element ago: arrives with the gather
       fn.finish(traw, w.i, w.j);
       ELEM::fetch(graw, prm, (int64_t)prm.chain_elems[k + 1]);
+      // its nodes (slice 0 is the carried face): touched now, gathered after
+      // this element's compute phase (one-wave elements: the dump area is one
+      // wave's)
+      if (L::WAVES == 1 && prm.touch && w.ok) {
+        FL ft = fn;
+        // (a copy the compiler cannot tell from fn: the touched offsets die
+        // here instead of staying live until the gather forms them again)
+        asm volatile("" : "+v"(ft.t[1]), "+v"(ft.t[2]), "+v"(ft.sa));
+#pragma unroll
+        for (int a = 1; a < P; ++a)
+          facet_touch<T, OFF32>(dump_lds, ug, ft.code(a));
+      }
     }
     T acc[P];
     el.apply(prm, dm, w, lds, ua, acc);
@@ -1046,6 +1114,7 @@ helmholtz_chain_kernel(FacetParams<T> prm, typename ELEM::Mat dm) {
     }
   }
   }
+  if (prm.touch) facet_touch_drain();
   if (prm.dot_out) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) udot += __shfl_down(udot, off, 64);
@@ -1060,6 +1129,19 @@ helmholtz_chain_kernel(FacetParams<T> prm, typename ELEM::Mat dm) {
 }
 
 // ----------------------------------------------------------------- launch ---
+// SFEM_CHAIN_TOUCH (read per launch): unset or 0 = chain kernels do not touch
+// (the default: measured slower, profiles/chain_touch_notes.md), 1 = they
+// always do, auto = they do where the field does not stay in the caches
+// between two kernels (the threshold of the non-temporal vector kernels;
+// below it the caches serve the gather and a touch is only issue slots).
+inline bool chain_touch_enabled(int64_t field_bytes) {
+  const char* v = getenv("SFEM_CHAIN_TOUCH");
+  if (!v) return false;
+  if (v[0] == '1' && v[1] == 0) return true;
+  if (v[0] == 'a') return streams_past_caches(field_bytes, 1);   // auto
+  return false;
+}
+
 // fields of 4 GiB and more take the 64-bit addressing instantiations
 // (SFEM_FACET_OFF64=1 forces them: tests)
 template <typename T>
@@ -1111,11 +1193,14 @@ int launch_facet_elem(const FacetParams<T>& prm, const typename ELEM::Mat& mat,
 // `groups`: workgroups of the launch = elements, or chain segments when
 // prm.chain_off is set (scalar fields only).
 template <typename T, int P>
-int launch_helmholtz_facet(const FacetParams<T>& prm, int geo_mode,
+int launch_helmholtz_facet(const FacetParams<T>& prm_in, int geo_mode,
                            int64_t groups, int64_t field_reals,
                            const T* dmat, const T* weights, const T* nodes,
                            hipStream_t stream) {
   if (int rc = check_groups("helmholtz (facet)", groups)) return rc;
+  FacetParams<T> prm = prm_in;
+  prm.touch = prm.chain_off &&
+              chain_touch_enabled(field_reals * (int64_t)sizeof(T));
   if (prm.chain_off && prm.ncomp != 1) {
     set_error("helmholtz (facet): chain launches take scalar fields");
     return SFEM_EINVAL;

@@ -73,6 +73,12 @@ SWITCHES = {
     'SFEM_FACET_OFF64': ('0', 'the library (getenv per launch)',
                          '1: facet kernels form 64-bit addresses even for '
                          'fields below 4 GiB (tests)'),
+    'SFEM_CHAIN_TOUCH': ('0', 'the library (getenv per launch)',
+                         '1: Helmholtz chain kernels touch the next element\'s '
+                         'nodes (a load nobody reads) one compute phase before '
+                         'they gather them; auto: only on fields of 256 MiB '
+                         'and more (slower: 1.43 vs 1.34 ms per CG iteration, '
+                         '`profiles/chain_touch_notes.md`)'),
     'SFEM_STOKES_FACET': ('1', 'core/operators.py',
                           '0: Stokes div / grad_t keep their index rows'),
     'SFEM_STOKES_FACET_DIV': ('box', 'core/operators.py',
