@@ -729,6 +729,90 @@ typedef struct sfem_elasticity_sens_args {
 int sfem_elasticity_sens(const sfem_elasticity_sens_args* args,
                          sfem_stream_t stream);
 
+/* Stress recovery on the collocated grid: for a displacement field `u`
+ * ((E, n, ndim)) and H = (1/W) Kw G, t = tr H as above, per point q
+ *
+ *   sigma_cc = lam t + 2 mu H[c][c],   sigma_cj = mu (H[c][j] + H[j][c])
+ *   vm = sqrt(0.5 ((sxx-syy)^2 + (syy-szz)^2 + (szz-sxx)^2)
+ *             + 3 (sxy^2 + sxz^2 + syz^2))
+ *
+ * `sigma` is (E, n, NV): NV = 6 in 3D, slots (xx, yy, zz, xy, xz, yz); NV = 4
+ * in 2D, slots (xx, yy, xy, zz) with sigma_zz = lam t (plane strain), or 0
+ * when `plane_stress` is set (the caller then passes the modified lambda).
+ * `vm` is (E, n).  Either output may be NULL and is then skipped.  Points
+ * with W = 0 (the all -1 rows of a padded mesh) give zeros.  `lam` and `mu`
+ * are (E, n) arrays or NULL for lam_const / mu_const.  Element-local: no
+ * gather, no scatter, no atomics.  Geometry and launch arguments are those of
+ * sfem_elasticity_args.  ndim outside 2..3, P outside 2..12 and any other
+ * geo_mode return SFEM_EUNSUPPORTED; a NULL u, dmat or wdet, both outputs
+ * NULL or a missing geometry array is SFEM_EINVAL.  ABI version 10 (a pure
+ * addition).                                                                 */
+typedef struct sfem_elasticity_stress_args {
+  const void* u;          /* (E, n, ndim)                                     */
+  void* sigma;            /* (E, n, NV) or NULL                               */
+  void* vm;               /* (E, n) or NULL                                   */
+  const void* wdet;       /* (E, n)                                           */
+  const void* lam;        /* (E, n) or NULL                                   */
+  const void* mu;         /* (E, n) or NULL                                   */
+  double lam_const, mu_const;
+  const void* kfac;       /* per-point weighted cofactors or NULL             */
+  const void* geo_elem;   /* (E, 24) or NULL                                  */
+  const int32_t* geo_index; /* (E,) slot of element e in kfac, or NULL = e    */
+  const int32_t* elem_list; /* element ids of this launch, or NULL = all      */
+  const void* dmat;       /* HOST (P, P)                                      */
+  const void* weights;    /* HOST (P,)                                        */
+  const void* nodes;      /* HOST (P,)                                        */
+  int64_t num_elements;
+  int64_t num_listed;
+  int32_t ndim, P, dtype, geo_mode;
+  int32_t plane_stress;   /* 2D: sigma_zz = 0                                 */
+} sfem_elasticity_stress_args;
+int sfem_elasticity_stress(const sfem_elasticity_stress_args* args,
+                           sfem_stream_t stream);
+
+/* The vector-Jacobian product of sfem_elasticity_stress: for a cotangent
+ * `sbar` ((E, n, NV), the slots of `sigma`) and dbar = sum_c sbar_cc (plus
+ * sbar_zz in 2D plane strain)
+ *
+ *   Hbar[c][j] = lam dbar delta_cj + mu (c == j ? 2 sbar_cc : sbar_cj)
+ *   Gbar[c][a] = (1/W) sum_j Kw[a][j] Hbar[c][j]
+ *   ubar[e,m,c] = sum_a sum_q D_a[q,m] Gbar[c][a](q)
+ *   dlam[q] = tr(H_u) dbar
+ *   dmu[q]  = sum_c 2 H_u[c][c] sbar_cc
+ *             + sum_{c<j} (H_u[c][j] + H_u[j][c]) sbar_cj
+ *
+ * No W weights the sums: stress is a pointwise value.  `ubar` is (E, n, ndim),
+ * `dlam` and `dmu` are (E, n); each may be NULL and is then skipped.  `u` is
+ * read for `dlam` / `dmu` only and may be NULL without them.  Points with
+ * W = 0 give zeros.  A NULL sbar, dmat or wdet, a NULL u where dlam or dmu is
+ * asked for, all three outputs NULL or a missing geometry array is
+ * SFEM_EINVAL; the shape checks are those above.  ABI version 10 (a pure
+ * addition).                                                                 */
+typedef struct sfem_elasticity_stress_vjp_args {
+  const void* sbar;       /* (E, n, NV)                                       */
+  const void* u;          /* (E, n, ndim), or NULL without dlam and dmu       */
+  void* ubar;             /* (E, n, ndim) or NULL                             */
+  void* dlam;             /* (E, n) or NULL                                   */
+  void* dmu;              /* (E, n) or NULL                                   */
+  const void* wdet;       /* (E, n)                                           */
+  const void* lam;        /* (E, n) or NULL                                   */
+  const void* mu;         /* (E, n) or NULL                                   */
+  double lam_const, mu_const;
+  const void* kfac;       /* per-point weighted cofactors or NULL             */
+  const void* geo_elem;   /* (E, 24) or NULL                                  */
+  const int32_t* geo_index; /* (E,) slot of element e in kfac, or NULL = e    */
+  const int32_t* elem_list; /* element ids of this launch, or NULL = all      */
+  const void* dmat;       /* HOST (P, P)                                      */
+  const void* weights;    /* HOST (P,)                                        */
+  const void* nodes;      /* HOST (P,)                                        */
+  int64_t num_elements;
+  int64_t num_listed;
+  int32_t ndim, P, dtype, geo_mode;
+  int32_t plane_stress;   /* 2D: sbar_zz takes no part                        */
+} sfem_elasticity_stress_vjp_args;
+int sfem_elasticity_stress_vjp(const sfem_elasticity_stress_vjp_args* args,
+                               sfem_stream_t stream);
+
 /* ------------------------------------- fields at points: locate, eval, eval^T ---
  * A field of order P1 - 1 on element e is u(xi) = sum_n u[elements[e, n]]
  * l_n(xi) with l_n the tensor product of the 1D Lagrange polynomials on

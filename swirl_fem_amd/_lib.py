@@ -168,6 +168,34 @@ class ElasticitySensArgs(ctypes.Structure):
   ]
 
 
+class ElasticityStressArgs(ctypes.Structure):
+  """Mirror of `struct sfem_elasticity_stress_args`."""
+  _fields_ = [
+      ('u', c_ptr), ('sigma', c_ptr), ('vm', c_ptr), ('wdet', c_ptr),
+      ('lam', c_ptr), ('mu', c_ptr), ('lam_const', c_dbl),
+      ('mu_const', c_dbl), ('kfac', c_ptr),
+      ('geo_elem', c_ptr), ('geo_index', c_ptr), ('elem_list', c_ptr),
+      ('dmat', c_ptr), ('weights', c_ptr), ('nodes', c_ptr),
+      ('num_elements', c_i64), ('num_listed', c_i64), ('ndim', c_i32),
+      ('P', c_i32), ('dtype', c_i32), ('geo_mode', c_i32),
+      ('plane_stress', c_i32),
+  ]
+
+
+class ElasticityStressVjpArgs(ctypes.Structure):
+  """Mirror of `struct sfem_elasticity_stress_vjp_args`."""
+  _fields_ = [
+      ('sbar', c_ptr), ('u', c_ptr), ('ubar', c_ptr), ('dlam', c_ptr),
+      ('dmu', c_ptr), ('wdet', c_ptr), ('lam', c_ptr), ('mu', c_ptr),
+      ('lam_const', c_dbl), ('mu_const', c_dbl), ('kfac', c_ptr),
+      ('geo_elem', c_ptr), ('geo_index', c_ptr), ('elem_list', c_ptr),
+      ('dmat', c_ptr), ('weights', c_ptr), ('nodes', c_ptr),
+      ('num_elements', c_i64), ('num_listed', c_i64), ('ndim', c_i32),
+      ('P', c_i32), ('dtype', c_i32), ('geo_mode', c_i32),
+      ('plane_stress', c_i32),
+  ]
+
+
 SFEM_POINT_CHUNK = 64
 
 
@@ -329,6 +357,9 @@ SIGNATURES = {
     'sfem_transport_rhs_vjp': [ctypes.POINTER(TransportVjpArgs), c_ptr],
     'sfem_elasticity_local': [ctypes.POINTER(ElasticityArgs), c_ptr],
     'sfem_elasticity_sens': [ctypes.POINTER(ElasticitySensArgs), c_ptr],
+    'sfem_elasticity_stress': [ctypes.POINTER(ElasticityStressArgs), c_ptr],
+    'sfem_elasticity_stress_vjp': [ctypes.POINTER(ElasticityStressVjpArgs),
+                                   c_ptr],
     'sfem_point_locate': [ctypes.POINTER(PointLocateArgs), c_ptr],
     'sfem_point_eval': [ctypes.POINTER(PointArgs), c_ptr],
     'sfem_point_eval_t': [ctypes.POINTER(PointArgs), c_ptr],

@@ -1400,6 +1400,103 @@ def elasticity_sens(u_q, v_q, parts, host, ndim, P, wdet, lambda0=0.0,
   return out
 
 
+def _lame_fields(args, field, lam, mu):
+  """`lam` and `mu` of a stress launch: a float or an (E, P^d) tensor each."""
+  for name, value in (('lam', lam), ('mu', mu)):
+    if isinstance(value, torch.Tensor):
+      setattr(args, name, field(value, name).data_ptr())
+    else:
+      setattr(args, name + '_const', float(value))
+
+
+def elasticity_stress(u_q, parts, host, ndim, P, wdet, lam, mu,
+                      want=(True, False), plane_stress=False):
+  """Stress of a displacement on a collocated grid
+  (`sfem_elasticity_stress`): `u_q` (E, P^d, d), `wdet` (E, P^d); `lam`, `mu`:
+  a float or an (E, P^d) tensor each.  Returns (sigma (E, P^d, NV), von Mises
+  (E, P^d)), None where `want` is false; NV = 6 with slots (xx, yy, zz, xy,
+  xz, yz) in 3D, 4 with slots (xx, yy, xy, zz) in 2D, where `plane_stress`
+  sets sigma_zz = 0 (lam is then the modified lambda of `lame_parameters`).
+  Rows of elements that no part lists and points with wdet = 0 are zero."""
+  u_q = u_q.contiguous()
+  dev = _dev(u_q)
+  E, n, d = u_q.shape
+  if d != ndim or n != P ** ndim:
+    raise ValueError(f'expected (E, {P ** ndim}, {ndim}) local values, got '
+                     f'{tuple(u_q.shape)}')
+  if wdet is None:
+    raise ValueError('elasticity_stress needs `wdet`')
+  want = tuple(bool(w) for w in want)
+  if len(want) != 2 or not any(want):
+    raise ValueError('`want` names (sigma, von Mises), at least one of them')
+  nv = 6 if ndim == 3 else 4
+  tensors = []
+  field = lambda t, name: _field(t, name, (E, n), u_q, 'displacement', tensors)
+  zeros = lambda *s: torch.zeros(s, dtype=u_q.dtype, device=dev)
+  sigma = zeros(E, n, nv) if want[0] else None
+  vm = zeros(E, n) if want[1] else None
+  args = _lib.ElasticityStressArgs(
+      u=u_q.data_ptr(), sigma=_dptr(sigma), vm=_dptr(vm),
+      wdet=field(wdet, 'wdet').data_ptr(), plane_stress=int(bool(plane_stress)))
+  _lame_fields(args, field, lam, mu)
+  host = {k: _host(v, u_q.dtype) for k, v in host.items()}
+  args.num_elements, args.ndim, args.P = E, ndim, P
+  args.dtype = _dtype_code(u_q)
+  with torch.cuda.device(dev):
+    for part in parts:
+      for name, value in _launch_fields(part, host, 'kfac').items():
+        setattr(args, name, value)
+      _lib.check(_lib.load().sfem_elasticity_stress(ctypes.byref(args),
+                                                    _stream(dev)),
+                 'sfem_elasticity_stress')
+  return sigma, vm
+
+
+def elasticity_stress_vjp(s_bar, u_q, parts, host, ndim, P, wdet, lam, mu,
+                          want=(True, True, True), plane_stress=False):
+  """The vector-Jacobian product of `elasticity_stress`
+  (`sfem_elasticity_stress_vjp`): `s_bar` (E, P^d, NV) the cotangent of
+  sigma, `u_q` (E, P^d, d) the displacement (needed for dlam / dmu only, else
+  it may be None).  Returns (ubar (E, P^d, d), dlam (E, P^d), dmu (E, P^d)),
+  None where `want` is false."""
+  s_bar = s_bar.contiguous()
+  dev = _dev(s_bar)
+  nv = 6 if ndim == 3 else 4
+  E, n = s_bar.shape[0], P ** ndim
+  if tuple(s_bar.shape) != (E, n, nv):
+    raise ValueError(f'expected an (E, {n}, {nv}) stress cotangent, got '
+                     f'{tuple(s_bar.shape)}')
+  if wdet is None:
+    raise ValueError('elasticity_stress_vjp needs `wdet`')
+  want = tuple(bool(w) for w in want)
+  if len(want) != 3 or not any(want):
+    raise ValueError('`want` names (ubar, dlam, dmu), at least one of them')
+  tensors = []
+  field = lambda t, name: _field(t, name, (E, n), s_bar, 'cotangent', tensors)
+  u_q = _field(u_q, 'displacement', (E, n, ndim), s_bar, 'cotangent', tensors)
+  if u_q is None and (want[1] or want[2]):
+    raise ValueError('dlam and dmu need the displacement')
+  zeros = lambda *s: torch.zeros(s, dtype=s_bar.dtype, device=dev)
+  out = (zeros(E, n, ndim) if want[0] else None,
+         zeros(E, n) if want[1] else None, zeros(E, n) if want[2] else None)
+  args = _lib.ElasticityStressVjpArgs(
+      sbar=s_bar.data_ptr(), u=_dptr(u_q), ubar=_dptr(out[0]),
+      dlam=_dptr(out[1]), dmu=_dptr(out[2]),
+      wdet=field(wdet, 'wdet').data_ptr(), plane_stress=int(bool(plane_stress)))
+  _lame_fields(args, field, lam, mu)
+  host = {k: _host(v, s_bar.dtype) for k, v in host.items()}
+  args.num_elements, args.ndim, args.P = E, ndim, P
+  args.dtype = _dtype_code(s_bar)
+  with torch.cuda.device(dev):
+    for part in parts:
+      for name, value in _launch_fields(part, host, 'kfac').items():
+        setattr(args, name, value)
+      _lib.check(_lib.load().sfem_elasticity_stress_vjp(ctypes.byref(args),
+                                                        _stream(dev)),
+                 'sfem_elasticity_stress_vjp')
+  return out
+
+
 # ------------------------------------------------------------ fields at points
 def point_locate(points, node_coords, elements, grid, nodes, bary, max_iter,
                  tol_xi, tol_x):

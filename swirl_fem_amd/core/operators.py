@@ -2251,6 +2251,30 @@ def lame_parameters(youngs_modulus, poisson_ratio, plane_stress=False):
   return lam, mu
 
 
+def von_mises(sigma, ndim):
+  """The von Mises stress of `sigma` (..., NV) in the Voigt slots of
+  `ElasticityOperator.stress`: NV = 6, (xx, yy, zz, xy, xz, yz) for ndim 3;
+  NV = 4, (xx, yy, xy, zz) for ndim 2.  Plain torch arithmetic on the last
+  axis, so autograd differentiates it; the gradient does not exist where the
+  result is zero (a square root at zero): use `von_mises(...) ** 2` or a
+  p-norm in an objective that can reach it."""
+  nv = {2: 4, 3: 6}.get(ndim)
+  if nv is None or sigma.shape[-1] != nv:
+    raise ValueError(f'von_mises: ndim={ndim} takes {nv} stress slots on the '
+                     f'last axis, got shape {tuple(sigma.shape)}')
+  if ndim == 3:
+    sxx, syy, szz, sxy, sxz, syz = sigma.unbind(-1)
+    shear = sxy ** 2 + sxz ** 2 + syz ** 2
+  else:
+    sxx, syy, sxy, szz = sigma.unbind(-1)
+    shear = sxy ** 2
+  return torch.sqrt(0.5 * ((sxx - syy) ** 2 + (syy - szz) ** 2 +
+                           (szz - sxx) ** 2) + 3.0 * shear)
+
+
+_von_mises = von_mises   # `ElasticityOperator.stress` has a flag of that name
+
+
 @dataclasses.dataclass(eq=False)
 class ElasticityOperator:
   """`K u + lambda0 M_rho u` for displacements u (N, d), with `v^T K u = int
@@ -2271,6 +2295,7 @@ class ElasticityOperator:
   mask: torch.Tensor | None = None
   _wdet: torch.Tensor | None = None
   _diag: tuple | None = None
+  _lumped: torch.Tensor | None = None
   # (lame_lambda, lame_mu, density) as the caller passed them: `sensitivity`
   # returns its gradients in these forms
   coef_source: tuple = (None, None, None)
@@ -2393,6 +2418,120 @@ class ElasticityOperator:
                                  self.point_weights(), lambda0, want=wanted)
     return tuple(reduce_coefficient_gradient(g, s)
                  for g, s in zip(grads, self.coef_source))
+
+  # ------------------------------------------------------------------ stress
+  def _stress_q(self, uq, von_mises, plane_stress):
+    """(sigma, von Mises or None) at the quadrature points from `uq`
+    (E, Q^d, d) there: the kernel alone, or its autograd node where `uq` or a
+    Lame parameter the operator was created with requires grad."""
+    fes = self.fespace
+    lam_src, mu_src = self.coef_source[:2]
+    if autodiff.needs_grad(uq, lam_src, mu_src):
+      sigma = autodiff.elasticity_stress_local(self, uq.contiguous(),
+                                               plane_stress)
+      # the fused von Mises output has no adjoint: sqrt is taken by autograd
+      vm = _von_mises(sigma, fes.mesh.ndim) if von_mises else None
+      return sigma, vm
+    return _ops.elasticity_stress(
+        uq.contiguous(), self.parts, self.host, fes.mesh.ndim,
+        fes.quadrature.num_points, self.point_weights(), self.lam, self.mu,
+        want=(True, bool(von_mises)), plane_stress=plane_stress)
+
+  def stress_local(self, u_local, *, von_mises=False, plane_stress=False):
+    """(E, n, d) element displacements -> the stress (E, Q^d, NV) at the
+    quadrature points; with `von_mises` the pair (stress, von Mises (E, Q^d)).
+    NV = 6, slots (xx, yy, zz, xy, xz, yz) in 3D; NV = 4, slots (xx, yy, xy,
+    zz) in 2D with sigma_zz = lambda tr(eps) (plane strain) or, with
+    `plane_stress`, 0 (the operator then holds the modified lambda of
+    `lame_parameters(..., plane_stress=True)`).  Interpolation
+    (`sfem_basis_eval`) and one fused kernel (`sfem_elasticity_stress`, DESIGN
+    §3.18); nothing of size (E, Q^d, d, d) is stored.
+
+    Differentiable with respect to `u_local` and to `lame_lambda` / `lame_mu`
+    given to `create` as tensors that require grad; backward is one launch of
+    `sfem_elasticity_stress_vjp`.  Without grad the von Mises value is the
+    kernel's fused output, with grad it is `von_mises(sigma)`.  The von Mises
+    stress has no gradient where it is zero (a square root at zero):
+    differentiate `vm ** 2` or a p-norm there."""
+    fes = self.fespace
+    d = fes.mesh.ndim
+    if u_local.dim() != 3 or tuple(u_local.shape[::2]) != (
+        fes.mesh.num_elements, d):
+      raise ValueError(f'expected ({fes.mesh.num_elements}, n, {d}) local '
+                       f'values, got {tuple(u_local.shape)}')
+    uq = fes._interpolate(u_local.to(fes.dtype))
+    sigma, vm = self._stress_q(uq, von_mises, bool(plane_stress))
+    return (sigma, vm) if von_mises else sigma
+
+  def _lumped_weights(self):
+    """scatter(I^T W) (N,), the row sums of the mass matrix; checked > 0."""
+    if self._lumped is None:
+      fes = self.fespace
+      mesh = fes.mesh
+      W = self.point_weights()
+      den = _ops.scatter_add(fes._interpolate_t(W[..., None].contiguous()),
+                             mesh.elements, mesh.num_nodes, ncomp=1)
+      den = den.reshape(mesh.num_nodes)
+      if not float(den.min()) > 0.0:
+        raise ValueError(
+            'lumped stress recovery: a node has a non-positive lumped weight '
+            f'(min {float(den.min()):.3e}); use recovery=\'l2\'')
+      self._lumped = den
+    return self._lumped
+
+  def stress(self, u, *, at='nodes', recovery='lumped', von_mises=False,
+             plane_stress=False, rtol=None):
+    """The stress of nodal displacements `u` (N, d), dense or component-major.
+
+    `at='quadrature'`: what `stress_local` gives, (E, Q^d, NV).
+    `at='nodes'`: (N, NV) by `recovery`
+      'lumped': scatter(I^T (W sigma_q)) / scatter(I^T W), the quadrature
+        values averaged with the weights of the lumped mass matrix;
+      'l2': the L2 projection M sigma_N = scatter(I^T (W sigma_q)) with the
+        plain mass matrix of the space, one CG solve per column (relative
+        tolerance `rtol`, default 1e-12 in fp64 and 1e-6 in fp32).
+    With `von_mises` the pair (stress, von Mises); at nodes the von Mises
+    stress is `von_mises` of the nodal stress.  Differentiable as
+    `stress_local` is ('l2' through `linalg.cg.symmetric_solve`)."""
+    fes = self.fespace
+    mesh = fes.mesh
+    d, N = mesh.ndim, mesh.num_nodes
+    if at not in ('nodes', 'quadrature'):
+      raise ValueError(f"at={at!r}: expected 'nodes' or 'quadrature'")
+    if recovery not in ('lumped', 'l2'):
+      raise ValueError(f"recovery={recovery!r}: expected 'lumped' or 'l2'")
+    if not isinstance(u, torch.Tensor) or tuple(u.shape) != (N, d):
+      raise ValueError(f'expected ({N}, {d}) nodal displacements, got '
+                       f'{tuple(getattr(u, "shape", ()))}')
+    grad = autodiff.needs_grad(u, *self.coef_source[:2])
+    gather_rows = autodiff.gather_rows if grad else _ops.gather_rows
+    v = u.to(fes.dtype).contiguous()
+    uq = fes._interpolate(gather_rows(v, mesh.elements))
+    quad = at == 'quadrature'
+    sigma, vm = self._stress_q(uq, von_mises and quad, bool(plane_stress))
+    if quad:
+      return (sigma, vm) if von_mises else sigma
+    W = self.point_weights()
+    loc = fes._interpolate_t(sigma * W[..., None], grad)
+    scatter = autodiff.scatter_add if grad else _ops.scatter_add
+    rhs = scatter(loc.contiguous(), mesh.elements, N, ncomp=sigma.shape[-1])
+    if recovery == 'lumped':
+      nodal = rhs / self._lumped_weights()[:, None]
+    else:
+      from swirl_fem_amd.linalg.cg import cg, symmetric_solve
+      mass = fes.helmholtz_operator(None)
+      A = lambda x: mass.apply(x, 1.0, 0.0)
+      if rtol is None:
+        rtol = 1e-12 if fes.dtype == torch.float64 else 1e-6
+      cols = []
+      for k in range(rhs.shape[1]):
+        b = rhs[:, k].contiguous()
+        cols.append(symmetric_solve(A, b, tol=rtol) if grad
+                    else cg(A, b, tol=rtol)[0])
+      nodal = torch.stack(cols, dim=1)
+    if von_mises:
+      return nodal, _von_mises(nodal, d)
+    return nodal
 
   def _component_factors(self, i):
     """Stored per-point factors of the scalar operator that is the diagonal

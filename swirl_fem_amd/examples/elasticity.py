@@ -187,15 +187,7 @@ def _solve(mesh: Mesh, body_force,
                               'V-cycle is built for the scalar operator')
   if preconditioner not in (None, 'jacobi'):
     raise ValueError(f'unknown preconditioner {preconditioner!r}')
-  if mesh.axis_name is not None or mesh.neighbor_plan is not None:
-    raise NotImplementedError('solve_elasticity on a partitioned mesh')
-  if mesh._cache.get('replicas', 1) > 1:
-    raise NotImplementedError('solve_elasticity on an ensemble '
-                              '(Mesh.replicate)')
-  gi = mesh.exchange_gather_indices
-  if gi is not None and gi.numel() > 0:
-    raise NotImplementedError('solve_elasticity on a mesh with periodic '
-                              'images')
+  _check_mesh(mesh, 'solve_elasticity')
   d, N = mesh.ndim, mesh.num_nodes
   dtype, device = mesh.dtype, mesh.device
   lambda0 = float(lambda0)
@@ -271,4 +263,50 @@ def _solve(mesh: Mesh, body_force,
   return u
 
 
-__all__ = ['BCType', 'solve_elasticity']
+def _check_mesh(mesh, who):
+  if mesh.axis_name is not None or mesh.neighbor_plan is not None:
+    raise NotImplementedError(f'{who} on a partitioned mesh')
+  if mesh._cache.get('replicas', 1) > 1:
+    raise NotImplementedError(f'{who} on an ensemble (Mesh.replicate)')
+  gi = mesh.exchange_gather_indices
+  if gi is not None and gi.numel() > 0:
+    raise NotImplementedError(f'{who} on a mesh with periodic images')
+
+
+def recover_stress(mesh: Mesh, u, *, lame_lambda, lame_mu, at: str = 'nodes',
+                   recovery: str = 'lumped', von_mises: bool = False,
+                   plane_stress: bool = False):
+  """The stress sigma(u) of displacements `u` (N, d), e.g. those of
+  `solve_elasticity`, on the Gauss rule and the operator of that solve
+  (`ElasticityOperator.stress`).
+
+  `at='nodes'` returns (N, NV) nodal values by `recovery`: 'lumped' (the
+  quadrature values averaged with the lumped mass weights) or 'l2' (the L2
+  projection, one CG solve per stress component); `at='quadrature'` returns
+  the values (E, Q^d, NV) at the quadrature points.  NV = 6 with slots (xx,
+  yy, zz, xy, xz, yz) in 3D; NV = 4 with slots (xx, yy, xy, zz) in 2D, where
+  sigma_zz = lambda tr(eps) (plane strain) or 0 with `plane_stress`
+  (`lame_lambda` is then the modified one of `operators.lame_parameters(...,
+  plane_stress=True)`, as for the solve).  With `von_mises` the pair (stress,
+  von Mises stress) is returned.  `lame_lambda`, `lame_mu`: the forms
+  `solve_elasticity` takes.
+
+  Autograd: differentiable with respect to `u` (so it chains into the adjoint
+  of `solve_elasticity`) and, through the explicit dependence of sigma on
+  them, with respect to `lame_lambda` and `lame_mu` given as tensors that
+  require grad.  The von Mises stress has no gradient where it is zero;
+  differentiate its square or a p-norm.  Values at points:
+  `mesh.point_evaluator(points)(recover_stress(mesh, u, ...))`."""
+  _check_mesh(mesh, 'recover_stress')
+  d = mesh.ndim
+  quadrature = Quadrature1D.create(
+      num_points=mesh.order + (d + 1) // 2,
+      quadrature_type=NodeType.GAUSS_LEGENDRE)
+  fespace = FiniteElementSpace.create(mesh, quadrature)
+  op = fespace.elasticity_operator(None, lame_lambda=lame_lambda,
+                                   lame_mu=lame_mu)
+  return op.stress(u, at=at, recovery=recovery, von_mises=von_mises,
+                   plane_stress=plane_stress)
+
+
+__all__ = ['BCType', 'recover_stress', 'solve_elasticity']
