@@ -56,6 +56,29 @@ def test_local_apply_equals_dense_matrices():
         1e-12 * np.abs(A @ u).max()
 
 
+def test_collocated_diagonal_equals_diagonal():
+  """The closed form the order sweep uses where `diagonal`'s (E, Q, n, d)
+  array is too large, pinned to `diagonal`: every term alone and together,
+  with and without coefficients and a mask."""
+  rng = np.random.default_rng(2)
+  for ndim, P in ((2, 5), (3, 3)):
+    rp = G.three_kinds(3, ndim, P).rp
+    fes = AR.space(rp.node_coords, rp.elements, P, (P, 'gll'))
+    b = _velocity(fes, rng)
+    xq = AR.quad_points(fes)
+    k, c = 1.0 + xq[..., 0] ** 2, 0.5 + xq[..., -1]
+    keep = (rng.random(fes.num_nodes) > 0.2).astype(np.float64)
+    for l0, l1, kq, cq, bq, kp in ((0.7, 1.3, k, c, b, keep),
+                                   (0.7, 1.3, None, None, b, None),
+                                   (0.0, 0.0, None, None, b, None),
+                                   (1.0, 0.0, None, c, None, None),
+                                   (0.0, 1.0, k, None, None, keep)):
+      want = AR.diagonal(fes, l0, l1, kq, cq, bq, kp)
+      got = AR.collocated_diagonal(fes, l0, l1, kq, cq, bq, kp)
+      assert np.abs(want).max() > 0
+      assert np.abs(got - want).max() <= 1e-13 * np.abs(want).max(), (ndim, l0)
+
+
 def test_divergence_free_velocity_is_skew_on_the_interior():
   """int (b . grad u) v + (b . grad v) u = int b . grad(uv) = -int div(b) uv
   + boundary terms: for div b = 0 the interior block of C_b + C_b^T is 0,

@@ -3,7 +3,12 @@ operator (collocated and two-grid, every velocity form, every geometry kind)
 against the NumPy reference (`tests/advection_reference.py`), its consistency
 across apply_local / diagonal, BiCGStab against its NumPy restatement
 (`tests/bicgstab_reference.py`), discrete solves against dense solves,
-manufactured solutions, a periodic box and the refusals."""
+manufactured solutions, a periodic box and the refusals.
+
+Per-order coverage of the forward kernels (every P = 2..12 in 2D and 3D, both
+precisions, every geometry path and coefficient form, `apply_local`, the
+diagonal) is in `tests/test_gpu_advection_sweep.py`; the BiCGStab kernels and
+scalar phases are called directly in `tests/test_gpu_bicgstab_kernels.py`."""
 import warnings
 
 import numpy as np
