@@ -938,6 +938,12 @@ int sfem_point_eval_t(const sfem_point_args* args, sfem_stream_t stream);
  * and poll [7] asynchronously; unless one of the two breakdowns occurs, the
  * iterate and the iteration count are exactly those of a loop that tests the
  * condition of cg.py:68-73 every iteration.
+ * No-op means: the vectors and `scalars` keep their bits.  Phase 2 starts the
+ * next solve whatever [7] holds.  The `partials` an operator accumulates into
+ * are workspace, not state: phases 1, 2 and 5 of sfem_cg_scalars clear them
+ * whether `done` is set or not, because the apply that ran ahead of the flag
+ * has added to them.  sfem_cg_flush_x is not guarded: it runs after the solve
+ * has stopped.
  *
  * sfem_dot:            *result  = sum a*b          (clears result first)
  * sfem_dot_accumulate: *result += sum a*b

@@ -48,7 +48,7 @@ def _reference(rp, mesh, M, bm, l0, l1, quad=None):
       coarse=(M.coarse_steps,) + tuple(M.coarse_bounds))
 
 
-PAIRS = sorted({(pc, pf) for p in range(2, 12)
+PAIRS = sorted({(pc, pf) for p in range(2, 13)    # 12: 13 -> 7 points
                 for pf, pc in zip(pmg.default_orders(p),
                                   pmg.default_orders(p)[1:])})
 
@@ -62,12 +62,18 @@ def test_transfers_every_default_pair(ndim, dtype):
     _check_transfer(ndim, dtype, pc, pf)
 
 
+RUN_TIME_PAIRS = ((2, 7), (1, 4), (3, 9), (4, 12))
+
+
 @pytest.mark.parametrize('ndim', [2, 3])
 def test_transfers_run_time_sizes(ndim):
   """Pairs outside the default schedules (orders=[7, 2, 1], ...) take the
-  run-time-size kernels."""
-  for pc, pf in ((2, 7), (1, 4), (3, 9)):
-    _check_transfer(ndim, torch.float64, pc, pf)
+  run-time-size kernels; (4, 12) has the 13 fine points of the largest
+  compiled pair."""
+  assert not set(RUN_TIME_PAIRS) & set(PAIRS) and (6, 12) in PAIRS
+  for dtype in (torch.float64, torch.float32):
+    for pc, pf in RUN_TIME_PAIRS:
+      _check_transfer(ndim, dtype, pc, pf)
 
 
 def _check_transfer(ndim, dtype, pc, pf):
