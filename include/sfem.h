@@ -1316,6 +1316,35 @@ int sfem_pmg_restrict(const void* rf, void* rc_local, const int32_t* cidx,
                       const int32_t* fidx, const uint32_t* owner,
                       const void* mat, int64_t num_elements, int ndim, int pc,
                       int pf, int dtype, sfem_stream_t stream);
+/* The same transfers for nodal vector fields with ndim components per node,
+ * dense (N, ndim): the flat vectors of the elasticity solve
+ * (linalg/pmg_elasticity.py).  Sizes, pairs, `owner` and `mat` as above.
+ * Fixed components are per component, not per node, so
+ *   cidx (E, pc^ndim), fidx (E, pf^ndim): plain int32 ids in [0, N), and
+ *   cfix (N_c,), ffix (N_f,) uint8: bit c of a node's byte is set iff its
+ *       component c is fixed (reads as 0; prolong stores 0 there).
+ * One launch, one wave per element: the components go one after another
+ * through the same LDS buffers, so the index rows, owner words and flag bytes
+ * are fetched from memory once per element.
+ * sfem_pmg_prolong_vec:  uf (N_f, ndim) = P uc (N_c, ndim) per component
+ *                    (add != 0: uf += P uc, fixed fine components left as
+ *                    they are), every fine node written at its owner only;
+ * sfem_pmg_restrict_vec: rc_local (E, pc^ndim, ndim) = the transposed
+ *                    contraction of the owned, non-fixed fine values, fixed
+ *                    coarse slots 0; sfem_scatter_csr with ncomp = ndim sums
+ *                    them in a fixed order.  No atomics.
+ * Status codes as sfem_pmg_prolong / sfem_pmg_restrict.                     */
+int sfem_pmg_prolong_vec(const void* uc, void* uf, const int32_t* cidx,
+                         const int32_t* fidx, const uint32_t* owner,
+                         const uint8_t* cfix, const uint8_t* ffix,
+                         const void* mat, int64_t num_elements, int ndim,
+                         int pc, int pf, int add, int dtype,
+                         sfem_stream_t stream);
+int sfem_pmg_restrict_vec(const void* rf, void* rc_local, const int32_t* cidx,
+                          const int32_t* fidx, const uint32_t* owner,
+                          const uint8_t* cfix, const uint8_t* ffix,
+                          const void* mat, int64_t num_elements, int ndim,
+                          int pc, int pf, int dtype, sfem_stream_t stream);
 /* One step of the Chebyshev-Jacobi smoother in one pass over n values:
  *   mode 0:  d = a d + c dinv (b - ax);  x += d
  *   mode 1:  d = c dinv b;  x = d          (start from x = 0: ax, x, d unread)

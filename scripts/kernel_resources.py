@@ -14,6 +14,7 @@ for line in r.stderr.splitlines():
   if t.startswith('Function Name:'):
     name = t.split(':', 1)[1].strip()
     dem = subprocess.run(['/usr/bin/c++filt', name], capture_output=True, text=True).stdout.strip()
+    dem = dem.replace('(anonymous namespace)::', '')
     cur = re.sub(r'\(.*', '', dem).replace('void sfem::', ''); rows[cur] = {}
   elif cur and ':' in t:
     k, v = t.split(':', 1); rows[cur][k.strip()] = v.strip()

@@ -367,6 +367,11 @@ SIGNATURES = {
                          c_i32, c_i32, c_i32, c_i32, c_i32, c_ptr],
     'sfem_pmg_restrict': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64,
                           c_i32, c_i32, c_i32, c_i32, c_ptr],
+    'sfem_pmg_prolong_vec': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                             c_ptr, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32,
+                             c_ptr],
+    'sfem_pmg_restrict_vec': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                              c_ptr, c_i64, c_i32, c_i32, c_i32, c_i32, c_ptr],
     'sfem_cheb_step': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_dbl, c_dbl,
                        c_i64, c_i32, c_i32, c_ptr],
     'sfem_pmg_dot2': [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i32, c_i32, c_ptr],

@@ -1933,6 +1933,69 @@ def pmg_restrict(rf, rc_local, cidx, fidx, owner, mat, ndim, pc, pf):
   return rc_local
 
 
+def _pmg_vec_check(who, coarse, fine, cidx, fidx, owner, cfix, ffix, mat, ndim,
+                   pc, pf):
+  """Shapes and dtypes of a vector transfer: `coarse` (N_c ndim,), `fine`
+  (N_f ndim,) flat nodal vectors."""
+  ndim, pc, pf = int(ndim), int(pc), int(pf)
+  if coarse.dtype != fine.dtype or mat.dtype != fine.dtype:
+    raise ValueError(f'{who}: one dtype for the two vectors and mat')
+  if cidx.dtype != torch.int32 or fidx.dtype != torch.int32:
+    raise TypeError(f'{who}: int32 index rows')
+  if cfix.dtype != torch.uint8 or ffix.dtype != torch.uint8:
+    raise TypeError(f'{who}: uint8 flag bytes, one per node')
+  if ndim in (2, 3) and 2 <= pc < pf:
+    E = cidx.shape[0]
+    if (tuple(cidx.shape) != (E, pc ** ndim) or
+        tuple(fidx.shape) != (E, pf ** ndim) or
+        owner.numel() != E * ((pf ** ndim + 31) // 32) or
+        mat.numel() != pf * pc):
+      raise ValueError(f'{who}: cidx (E, pc^d), fidx (E, pf^d), owner '
+                       '(E, ceil(pf^d / 32)) and mat (pf, pc) expected')
+  if (coarse.numel() != cfix.numel() * ndim or
+      fine.numel() != ffix.numel() * ndim):
+    raise ValueError(f'{who}: a vector of ndim values per node of its flag '
+                     'bytes expected')
+
+
+def pmg_prolong_vec(uc, uf, cidx, fidx, owner, cfix, ffix, mat, ndim, pc, pf,
+                    add=False):
+  """uf (N_f ndim,) = P uc (N_c ndim,) per component (add: uf += P uc), see
+  `sfem_pmg_prolong_vec`; in place.  Plain int32 index rows; `cfix`, `ffix`:
+  uint8 per node, bit c set iff component c is fixed."""
+  dev = _dev(uc, uf, cidx, fidx, owner, cfix, ffix, mat)
+  _pmg_vec_check('pmg_prolong_vec', uc, uf, cidx, fidx, owner, cfix, ffix, mat,
+                 ndim, pc, pf)
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_pmg_prolong_vec(
+        _ptr(uc), _ptr(uf), _ptr(cidx), _ptr(fidx), _ptr(owner), _ptr(cfix),
+        _ptr(ffix), _ptr(mat), cidx.shape[0], int(ndim), int(pc), int(pf),
+        int(bool(add)), _dtype_code(uf), _stream(dev)), 'sfem_pmg_prolong_vec')
+  return uf
+
+
+def pmg_restrict_vec(rf, rc_local, cidx, fidx, owner, cfix, ffix, mat, ndim,
+                     pc, pf):
+  """rc_local (E, pc^ndim, ndim) = element-local P^T rf (N_f ndim,), see
+  `sfem_pmg_restrict_vec`."""
+  dev = _dev(rf, rc_local, cidx, fidx, owner, cfix, ffix, mat)
+  if rc_local.dtype != rf.dtype:
+    raise ValueError('pmg_restrict_vec: one dtype for rf and rc_local')
+  if rc_local.numel() != cidx.numel() * int(ndim):
+    raise ValueError('pmg_restrict_vec: rc_local must hold ndim values per '
+                     'slot of the coarse index rows')
+  # (the assembled coarse vector is `sfem_scatter_csr`'s: checked by size only)
+  coarse = torch.empty(cfix.numel() * int(ndim), dtype=rf.dtype, device='meta')
+  _pmg_vec_check('pmg_restrict_vec', coarse, rf, cidx, fidx, owner, cfix, ffix,
+                 mat, ndim, pc, pf)
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().sfem_pmg_restrict_vec(
+        _ptr(rf), _ptr(rc_local), _ptr(cidx), _ptr(fidx), _ptr(owner),
+        _ptr(cfix), _ptr(ffix), _ptr(mat), cidx.shape[0], int(ndim), int(pc),
+        int(pf), _dtype_code(rf), _stream(dev)), 'sfem_pmg_restrict_vec')
+  return rc_local
+
+
 CHEB_GENERAL, CHEB_FIRST, CHEB_RESIDUAL, CHEB_RESTART = 0, 1, 2, 3
 
 

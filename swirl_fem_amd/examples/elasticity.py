@@ -72,6 +72,13 @@ def _detached(v):
   return v.detach() if isinstance(v, torch.Tensor) else v
 
 
+def _check_every(M):
+  """How often CG polls its convergence flag: a preconditioner whose apply
+  dwarfs a host synchronisation says so (`check_every`), since every
+  iteration issued after the last one needed costs one more apply."""
+  return getattr(M, 'check_every', 16)
+
+
 class _ElasticitySolve(torch.autograd.Function):
   """`_solve` as one autograd node: the adjoint solve, the mass apply and the
   coefficient sensitivities in `backward`."""
@@ -101,7 +108,8 @@ class _ElasticitySolve(torch.autograd.Function):
     op, keep, l0 = st['op'], st['keep'], st['lambda0']
     N, d = keep.shape
     rhs = (u_bar.detach().to(keep.dtype) * keep).reshape(-1).contiguous()
-    lam, info = cg(st['A'], rhs, tol=st['rtol'], atol=st['atol'], M=st['M'])
+    lam, info = cg(st['A'], rhs, tol=st['rtol'], atol=st['atol'], M=st['M'],
+                   check_every=_check_every(st['M']))
     st['adjoint_info'] = info
     st['holder']['info']['adjoint'] = info
     lam = lam.view(N, d)
@@ -146,7 +154,12 @@ def solve_elasticity(mesh: Mesh, body_force,
   `boundary_covector`).  Where Dirichlet groups share a node, the later group
   in the mapping sets the value of a component both fix.
 
-  `preconditioner`: None or 'jacobi' (the operator's assembled diagonal).
+  `preconditioner`: None, 'jacobi' (the operator's assembled diagonal) or a
+  callable `(op, lambda0) -> M` on the masked `ElasticityOperator` of the
+  solve, whose result CG takes as `M` on the flat (N d,) vectors:
+  `linalg.pmg_elasticity.ElasticityPMultigrid` is one (p-multigrid, DESIGN
+  §3.19; `functools.partial(ElasticityPMultigrid, smoother_degree=3)` sets its
+  options).  With it CG stops on the true residual, r.r <= rtol^2 b.b.
   `rtol` is relative to the norm of the lifted right-hand side; `info` is
   CG's.
 
@@ -182,10 +195,13 @@ def _solve(mesh: Mesh, body_force,
   """The body of `solve_elasticity`.  `_state`: a dict that receives what the
   adjoint solve needs (the operator, the mask, the preconditioner, the mass
   apply)."""
-  if preconditioner == 'pmg':
-    raise NotImplementedError("preconditioner='pmg' for elasticity: the "
-                              'V-cycle is built for the scalar operator')
-  if preconditioner not in (None, 'jacobi'):
+  if isinstance(preconditioner, str) and preconditioner == 'pmg':
+    raise NotImplementedError(
+        "preconditioner='pmg' for elasticity: the V-cycle of that name is "
+        'built for the scalar operator; pass preconditioner='
+        'linalg.pmg_elasticity.ElasticityPMultigrid (or any callable '
+        '(op, lambda0) -> M)')
+  if not callable(preconditioner) and preconditioner not in (None, 'jacobi'):
     raise ValueError(f'unknown preconditioner {preconditioner!r}')
   _check_mesh(mesh, 'solve_elasticity')
   d, N = mesh.ndim, mesh.num_nodes
@@ -251,7 +267,9 @@ def _solve(mesh: Mesh, body_force,
   if preconditioner == 'jacobi':
     from swirl_fem_amd.linalg.jacobi import JacobiPreconditioner
     M = JacobiPreconditioner(op.diagonal(lambda0).reshape(-1))
-  w, info = cg(A, b, tol=rtol, atol=atol, M=M)
+  elif callable(preconditioner):
+    M = preconditioner(op, lambda0)
+  w, info = cg(A, b, tol=rtol, atol=atol, M=M, check_every=_check_every(M))
   u = w.view(N, d) + u_D
   if _state is not None:
     _state.update(op=op, keep=keep, A=A, M=M, rtol=rtol, atol=atol,

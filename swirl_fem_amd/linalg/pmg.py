@@ -487,6 +487,58 @@ def _cheb_coefficients(lo, hi, degree):
   return out
 
 
+def lanczos_max(apply_fn, dinv):
+  """Largest eigenvalue of D^-1 A (rows with dinv > 0) from LANCZOS_STEPS
+  steps of Lanczos on D^-1/2 A D^-1/2 from a fixed start vector, on one rank.
+  `apply_fn(u, out)`: out = A u on vectors of `dinv`'s size and dtype."""
+  sq = dinv.double().sqrt()
+  n = sq.numel()
+  g = torch.Generator().manual_seed(12345)
+  v = torch.rand(n, generator=g, dtype=torch.float64).to(dinv.device) - 0.5
+  v = v * (sq > 0)
+  v = v / v.norm()
+  v_prev = torch.zeros_like(v)
+  alphas, betas = [], []
+  beta = 0.0
+  ax = torch.empty(n, dtype=dinv.dtype, device=dinv.device)
+  for _ in range(min(LANCZOS_STEPS, int((sq > 0).sum()))):
+    apply_fn((sq * v).to(dinv.dtype).contiguous(), ax)
+    w = sq * ax.double()
+    alpha = float(torch.dot(w, v))
+    w = w - alpha * v - beta * v_prev
+    alphas.append(alpha)
+    beta = float(w.norm())
+    if beta <= 1e-14 * abs(alpha):
+      break
+    betas.append(beta)
+    v_prev, v = v, w / beta
+  k = len(alphas)
+  T = np.diag(alphas) + np.diag(betas[:k - 1], 1) + np.diag(betas[:k - 1], -1)
+  return float(np.linalg.eigvalsh(T).max())
+
+
+def jacobi_scaled_extremes(S, ndim):
+  """(lmin, lmax) of the Jacobi-scaled coarse matrix S (scipy sparse,
+  symmetric): exact for up to 400 rows, else a few Lanczos steps from either
+  end (no factorisation of S; the coarse polynomial stays positive definite
+  for any 0 < lmin)."""
+  import scipy.sparse.linalg as spla
+  if S.shape[0] <= 400:
+    ev = np.linalg.eigvalsh(S.toarray())
+    return float(ev[0]), float(ev[-1])
+  lmax = float(spla.eigsh(S, k=1, which='LA', tol=1e-3,
+                          return_eigenvectors=False)[0])
+  try:
+    lmin = float(spla.eigsh(S, k=1, which='SA', tol=1e-2,
+                            maxiter=20 * S.shape[0],
+                            return_eigenvectors=False)[0])
+  except spla.ArpackNoConvergence as exc:
+    got = np.sort(exc.eigenvalues)
+    lmin = (float(got[0]) if got.size else
+            lmax / (4.0 * S.shape[0] ** (2.0 / ndim)))
+  return lmin, lmax
+
+
 def coarse_coefficient(coef, weights):
   """A diffusivity / reaction coefficient of the fine operator as the coarse
   levels take it (the same elements on every level): None, a scalar or an
@@ -839,30 +891,7 @@ class PMultigridPreconditioner:
     if lev.mesh.neighbor_plan is not None:
       sq = lev.dinv.double().sqrt()
       return float(self._lanczos(lev, lev.apply, sq, LANCZOS_STEPS).max())
-    sq = lev.dinv.double().sqrt()
-    n = sq.numel()
-    g = torch.Generator().manual_seed(12345)
-    v = torch.rand(n, generator=g, dtype=torch.float64).to(self.device) - 0.5
-    v = v * (sq > 0)
-    v = v / v.norm()
-    v_prev = torch.zeros_like(v)
-    alphas, betas = [], []
-    beta = 0.0
-    ax = torch.empty(n, dtype=self.dtype, device=self.device)
-    for _ in range(min(LANCZOS_STEPS, int((sq > 0).sum()))):
-      lev.apply((sq * v).to(self.dtype).contiguous(), ax)
-      w = sq * ax.double()
-      alpha = float(torch.dot(w, v))
-      w = w - alpha * v - beta * v_prev
-      alphas.append(alpha)
-      beta = float(w.norm())
-      if beta <= 1e-14 * abs(alpha):
-        break
-      betas.append(beta)
-      v_prev, v = v, w / beta
-    k = len(alphas)
-    T = np.diag(alphas) + np.diag(betas[:k - 1], 1) + np.diag(betas[:k - 1], -1)
-    return float(np.linalg.eigvalsh(T).max())
+    return lanczos_max(lev.apply, lev.dinv)
 
   def _local_matrix(self, lev):
     """The order-1 matrix of this rank's elements (CSR, fp64; Dirichlet rows
@@ -1006,7 +1035,6 @@ class PMultigridPreconditioner:
     """The order-1 matrix in ELL form (Dirichlet rows and columns zero) and
     the bounds of its Jacobi-scaled spectrum (`bounds`: given instead)."""
     import scipy.sparse as sp
-    import scipy.sparse.linalg as spla
     mesh = lev.mesh
     N = mesh.num_nodes
     A = self._local_matrix(lev)
@@ -1019,22 +1047,8 @@ class PMultigridPreconditioner:
     S = sp.diags(dm) @ Ai @ sp.diags(dm)
     if bounds is not None:
       lmin, lmax = None, None
-    elif S.shape[0] <= 400:
-      ev = np.linalg.eigvalsh(S.toarray())
-      lmin, lmax = float(ev[0]), float(ev[-1])
     else:
-      lmax = float(spla.eigsh(S, k=1, which='LA', tol=1e-3,
-                              return_eigenvectors=False)[0])
-      # a few Lanczos steps from the low end (no factorisation of S); the
-      # polynomial stays positive definite for any 0 < lmin
-      try:
-        lmin = float(spla.eigsh(S, k=1, which='SA', tol=1e-2,
-                                maxiter=20 * S.shape[0],
-                                return_eigenvectors=False)[0])
-      except spla.ArpackNoConvergence as exc:
-        got = np.sort(exc.eigenvalues)
-        lmin = (float(got[0]) if got.size else
-                lmax / (4.0 * S.shape[0] ** (2.0 / mesh.ndim)))
+      lmin, lmax = jacobi_scaled_extremes(S, mesh.ndim)
     if bounds is not None:
       self.coarse_bounds = tuple(float(b) for b in bounds)
     elif not lmin > 1e-12 * lmax:
