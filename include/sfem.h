@@ -813,6 +813,71 @@ typedef struct sfem_elasticity_stress_vjp_args {
 int sfem_elasticity_stress_vjp(const sfem_elasticity_stress_vjp_args* args,
                                sfem_stream_t stream);
 
+/* ------------------------------------- finite-strain (neo-Hookean) elasticity ---
+ * Compressible neo-Hookean material, total Lagrangian (the geometry is the
+ * reference mesh), on the collocated grid of sfem_elasticity_args, element-
+ * local.  With F = I + H, H[c][j] = d u_c / d X_j = (1/W) sum_a Kw[a][j]
+ * G[c][a] as above, J = det F (plane strain in 2D: the 2 x 2 block):
+ *
+ *   psi(F) = mu/2 (F:F - d) - mu ln J + lam/2 (ln J)^2
+ *   P(F)   = mu (F - F^-T) + lam ln J F^-T
+ *   dP[dH] = mu dH + (mu - lam ln J) F^-T dH^T F^-T + lam tr(F^-1 dH) F^-T
+ *
+ * mode = SFEM_HYPER_RESIDUAL: `u` is the displacement and
+ *
+ *   out[e,m,c] = sum_a sum_q D_a[q,m] (sum_j Kw[a][j] P[c][j])(q)
+ *                + lambda0 rho W u_c(m)
+ *
+ * the local part of R(u) = int P(F) : grad v + lambda0 int rho u . v.  Where
+ * `state` is non-NULL it receives (E, n, d*d + 1) reals, per point F^-1
+ * row-major in slots 0 .. d*d - 1 and ln J in slot d*d; where `psi` is
+ * non-NULL it receives (E, n) values W psi(F) + lambda0/2 rho W |u|^2, whose
+ * sum is the energy.
+ *
+ * mode = SFEM_HYPER_TANGENT: `u` is an increment w, `state` the output of a
+ * residual launch at the point of linearisation, and
+ *
+ *   out[e,m,c] = sum_a sum_q D_a[q,m] (sum_j Kw[a][j] dP[dH_w][c][j])(q)
+ *                + lambda0 rho W w_c(m)
+ *
+ * with F^-1 and ln J read from `state`: no inverse and no logarithm is taken.
+ * At state (I, 0) this is sfem_elasticity_local.
+ *
+ * J <= 0 at a point (an inverted state) is not an error: the logarithm is
+ * NaN or -inf and the outputs of that element are non-finite.  Points with
+ * W = 0 take H = 0.  `lam`, `mu`, `rho`, the geometry and launch arguments
+ * are those of sfem_elasticity_args.  ndim outside 2..3, P outside 2..12 and
+ * any other geo_mode or mode return SFEM_EUNSUPPORTED; a NULL u, out, dmat,
+ * wdet or a missing geometry array, the tangent mode with a NULL `state` or
+ * with a non-NULL `psi` is SFEM_EINVAL.  ABI version 10 (a pure addition).   */
+#define SFEM_HYPER_RESIDUAL 0
+#define SFEM_HYPER_TANGENT 1
+typedef struct sfem_hyperelastic_args {
+  const void* u;          /* (E, n, ndim): displacement, or the increment     */
+  void* out;              /* (E, n, ndim)                                     */
+  const void* wdet;       /* (E, n)                                           */
+  const void* lam;        /* (E, n) or NULL                                   */
+  const void* mu;         /* (E, n) or NULL                                   */
+  const void* rho;        /* (E, n) or NULL                                   */
+  double lam_const, mu_const, rho_const, lambda0;
+  const void* kfac;       /* per-point weighted cofactors or NULL             */
+  const void* geo_elem;   /* (E, 24) or NULL                                  */
+  const int32_t* geo_index; /* (E,) slot of element e in kfac, or NULL = e    */
+  const int32_t* elem_list; /* element ids of this launch, or NULL = all      */
+  const void* dmat;       /* HOST (P, P)                                      */
+  const void* weights;    /* HOST (P,)                                        */
+  const void* nodes;      /* HOST (P,)                                        */
+  int64_t num_elements;
+  int64_t num_listed;
+  int32_t ndim, P, dtype, geo_mode;
+  void* state;            /* (E, n, ndim*ndim + 1): out (residual, or NULL),
+                             in (tangent)                                     */
+  void* psi;              /* (E, n) or NULL; residual mode only               */
+  int32_t mode;           /* SFEM_HYPER_RESIDUAL / SFEM_HYPER_TANGENT         */
+} sfem_hyperelastic_args;
+int sfem_hyperelastic_local(const sfem_hyperelastic_args* args,
+                            sfem_stream_t stream);
+
 /* ------------------------------------- fields at points: locate, eval, eval^T ---
  * A field of order P1 - 1 on element e is u(xi) = sum_n u[elements[e, n]]
  * l_n(xi) with l_n the tensor product of the 1D Lagrange polynomials on

@@ -196,6 +196,16 @@ class ElasticityStressVjpArgs(ctypes.Structure):
   ]
 
 
+SFEM_HYPER_RESIDUAL, SFEM_HYPER_TANGENT = 0, 1
+
+
+class HyperelasticArgs(ctypes.Structure):
+  """Mirror of `struct sfem_hyperelastic_args`."""
+  _fields_ = ElasticityArgs._fields_ + [
+      ('state', c_ptr), ('psi', c_ptr), ('mode', c_i32),
+  ]
+
+
 SFEM_POINT_CHUNK = 64
 
 
@@ -360,6 +370,7 @@ SIGNATURES = {
     'sfem_elasticity_stress': [ctypes.POINTER(ElasticityStressArgs), c_ptr],
     'sfem_elasticity_stress_vjp': [ctypes.POINTER(ElasticityStressVjpArgs),
                                    c_ptr],
+    'sfem_hyperelastic_local': [ctypes.POINTER(HyperelasticArgs), c_ptr],
     'sfem_point_locate': [ctypes.POINTER(PointLocateArgs), c_ptr],
     'sfem_point_eval': [ctypes.POINTER(PointArgs), c_ptr],
     'sfem_point_eval_t': [ctypes.POINTER(PointArgs), c_ptr],

@@ -1359,6 +1359,70 @@ def elasticity_local(u_q, parts, host, ndim, P, wdet, lam, mu, rho=None,
   return out
 
 
+def hyperelastic_local(u_q, parts, host, ndim, P, wdet, lam, mu, rho=None,
+                       lambda0=0.0, *, mode, state=None, want_state=False,
+                       want_psi=False):
+  """The neo-Hookean residual or tangent on a collocated grid
+  (`sfem_hyperelastic_local`): `u_q` (E, P^d, d), `wdet` (E, P^d); `lam`,
+  `mu`, `rho` as in `elasticity_local`.
+
+  `mode='residual'`: `u_q` is the displacement; returns (R (E, P^d, d), state,
+  psi) with `state` (E, P^d, d*d + 1) -- per point F^-1 row-major, then ln J
+  -- where `want_state`, and `psi` (E, P^d), whose sum is the energy, where
+  `want_psi`; None otherwise.  `mode='tangent'`: `u_q` is the increment and
+  `state` that of a residual launch; returns T w (E, P^d, d).  Rows of
+  `state` and `psi` of elements that no part lists are zero."""
+  if mode not in ('residual', 'tangent'):
+    raise ValueError(f"mode: 'residual' or 'tangent', got {mode!r}")
+  tangent = mode == 'tangent'
+  u_q = u_q.contiguous()
+  dev = _dev(u_q)
+  E, n, d = u_q.shape
+  if d != ndim or n != P ** ndim:
+    raise ValueError(f'expected (E, {P ** ndim}, {ndim}) local values, got '
+                     f'{tuple(u_q.shape)}')
+  if wdet is None:
+    raise ValueError('hyperelastic_local needs `wdet`')
+  if tangent and (want_state or want_psi):
+    raise ValueError('the state and psi are outputs of the residual mode')
+  if tangent and state is None:
+    raise ValueError('the tangent mode needs the `state` of a residual launch')
+  if not tangent and state is not None:
+    raise ValueError('`state` is an input of the tangent mode only')
+  tensors = []
+  field = lambda t, name: _field(t, name, (E, n), u_q, 'displacement', tensors)
+  if tangent:
+    state = _field(state, 'state', (E, n, d * d + 1), u_q, 'displacement',
+                   tensors)
+  elif want_state:
+    state = torch.zeros((E, n, d * d + 1), dtype=u_q.dtype, device=dev)
+  psi = (torch.zeros((E, n), dtype=u_q.dtype, device=dev) if want_psi
+         else None)
+  args = _lib.HyperelasticArgs(
+      u=u_q.data_ptr(), lambda0=float(lambda0),
+      wdet=field(wdet, 'wdet').data_ptr(), state=_dptr(state), psi=_dptr(psi),
+      mode=_lib.SFEM_HYPER_TANGENT if tangent else _lib.SFEM_HYPER_RESIDUAL)
+  for name, value in (('lam', lam), ('mu', mu),
+                      ('rho', 1.0 if rho is None else rho)):
+    if isinstance(value, torch.Tensor):
+      setattr(args, name, field(value, name).data_ptr())
+    else:
+      setattr(args, name + '_const', float(value))
+  out = torch.empty_like(u_q)
+  host = {k: _host(v, u_q.dtype) for k, v in host.items()}
+  args.out = out.data_ptr()
+  args.num_elements, args.ndim, args.P = E, ndim, P
+  args.dtype = _dtype_code(u_q)
+  with torch.cuda.device(dev):
+    for part in parts:
+      for name, value in _launch_fields(part, host, 'kfac').items():
+        setattr(args, name, value)
+      _lib.check(_lib.load().sfem_hyperelastic_local(ctypes.byref(args),
+                                                     _stream(dev)),
+                 'sfem_hyperelastic_local')
+  return out if tangent else (out, state, psi)
+
+
 def elasticity_sens(u_q, v_q, parts, host, ndim, P, wdet, lambda0=0.0,
                     want=(True, True, True)):
   """Per-point sensitivities of v . (K + lambda0 M_rho) u with respect to

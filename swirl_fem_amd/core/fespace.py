@@ -612,6 +612,17 @@ class FiniteElementSpace:
         self, dirichlet_mask, lame_lambda=lame_lambda, lame_mu=lame_mu,
         density=density, geometry=geometry)
 
+  def hyperelastic_operator(self, dirichlet_mask=None, *, lame_lambda,
+                            lame_mu, density=None, geometry='auto'):
+    """Finite-strain elasticity of a compressible neo-Hookean material, total
+    Lagrangian: residual, energy and tangent for displacements u (N, d)
+    (`operators.HyperelasticOperator`).  Arguments as for
+    `elasticity_operator`, which is its tangent at u = 0."""
+    from swirl_fem_amd.core import operators
+    return operators.HyperelasticOperator.create(
+        self, dirichlet_mask, lame_lambda=lame_lambda, lame_mu=lame_mu,
+        density=density, geometry=geometry)
+
 
 class BoundaryMassOperator:
   """`scale * M u` with M the facet mass matrix `(B (x) B)^T diag(aw) (B (x) B)`

@@ -2303,15 +2303,22 @@ class ElasticityOperator:
   @classmethod
   def create(cls, fespace, dirichlet_mask=None, *, lame_lambda, lame_mu,
              density=None, geometry='auto') -> 'ElasticityOperator':
+    return cls._intake(fespace, dirichlet_mask, lame_lambda, lame_mu, density,
+                       geometry, 'ElasticityOperator', 'fused elasticity')
+
+  @classmethod
+  def _intake(cls, fespace, dirichlet_mask, lame_lambda, lame_mu, density,
+              geometry, who, what):
+    """The body of `create`, shared with `HyperelasticOperator.create`: `who`
+    and `what` name the operator in the refusals."""
     mesh = fespace.mesh
     if mesh.axis_name is not None or mesh.neighbor_plan is not None:
-      raise NotImplementedError('ElasticityOperator on a partitioned mesh')
+      raise NotImplementedError(f'{who} on a partitioned mesh')
     if mesh._cache.get('replicas', 1) > 1:
-      raise NotImplementedError('ElasticityOperator on an ensemble '
-                                '(Mesh.replicate)')
+      raise NotImplementedError(f'{who} on an ensemble (Mesh.replicate)')
     why = supports_two_grid(fespace)
     if why is not None:
-      raise NotImplementedError(f'fused elasticity unavailable: {why}')
+      raise NotImplementedError(f'{what} unavailable: {why}')
     if geometry not in ('auto', 'stored'):
       raise ValueError(f'unknown geometry mode {geometry!r}')
     E, d = mesh.num_elements, mesh.ndim
@@ -2586,3 +2593,152 @@ class ElasticityOperator:
     mass, stiff = self._diag
     out = stiff if lambda0 == 0.0 else stiff + lambda0 * mass[:, None]
     return out if self.mask is None else out * self.mask
+
+
+# ---------------------------------------------------------------------------
+# Finite-strain (neo-Hookean) elasticity
+# ---------------------------------------------------------------------------
+@dataclasses.dataclass(eq=False)
+class HyperelasticLinearization:
+  """What `HyperelasticOperator.linearize(u)` leaves: `state` (E, Q^d,
+  d*d + 1), per quadrature point F^-1 row-major and ln J, which the tangent
+  kernel reads; `residual`, mask * R(u) (N, d) from the same launch, and the
+  `lambda0` it was formed with."""
+  state: torch.Tensor
+  residual: torch.Tensor
+  lambda0: float
+
+
+class HyperelasticTangent:
+  """`T(u) w` at a linearisation: `apply(w)` (N, d) in any layout, returned
+  in the layout given; `linear_operator()` the callable CG takes."""
+
+  def __init__(self, op, state, lambda0):
+    self.op, self.state, self.lambda0 = op, state, float(lambda0)
+
+  def apply_local(self, w_local):
+    op = self.op
+    fes = op.fespace
+    wq = op._to_grid(w_local)
+    tq = _ops.hyperelastic_local(
+        wq, op.parts, op.host, fes.mesh.ndim, fes.quadrature.num_points,
+        op.point_weights(), op.lam, op.mu, op.rho, self.lambda0,
+        mode='tangent', state=self.state)
+    return fes._interpolate_t(tq)
+
+  def apply(self, w):
+    return self.op._assembled(w, self.apply_local)
+
+  def linear_operator(self):
+    return self.apply
+
+
+@dataclasses.dataclass(eq=False)
+class HyperelasticOperator:
+  """The internal force of a compressible neo-Hookean solid in the total-
+  Lagrangian formulation, for displacements u (N, d):
+
+      R(u) = int P(F) : grad v + lambda0 int rho u . v,   F = I + grad u,
+      P = mu (F - F^-T) + lambda ln J F^-T,  J = det F,
+
+  its energy `Psi(u) = int psi + lambda0/2 int rho |u|^2` with psi = mu/2
+  (F:F - d) - mu ln J + lambda/2 (ln J)^2, and its tangent `T(u) w = int
+  dP[grad w] : grad v + lambda0 int rho w . v` (plane strain in 2D).  The
+  geometry is the reference mesh.  Interpolation to the quadrature grid, one
+  launch of `sfem_hyperelastic_local` there, transposed interpolation; the
+  tangent reads F^-1 and ln J of the linearisation from the state the
+  residual launch stored.  `linear` is the `ElasticityOperator` with the same
+  mask and coefficients: the tangent at u = 0, and what preconditioners are
+  built on."""
+  linear: ElasticityOperator
+
+  @classmethod
+  def create(cls, fespace, dirichlet_mask=None, *, lame_lambda, lame_mu,
+             density=None, geometry='auto') -> 'HyperelasticOperator':
+    return cls(linear=ElasticityOperator._intake(
+        fespace, dirichlet_mask, lame_lambda, lame_mu, density, geometry,
+        'HyperelasticOperator', 'fused hyperelasticity'))
+
+  fespace = property(lambda self: self.linear.fespace)
+  parts = property(lambda self: self.linear.parts)
+  host = property(lambda self: self.linear.host)
+  lam = property(lambda self: self.linear.lam)
+  mu = property(lambda self: self.linear.mu)
+  rho = property(lambda self: self.linear.rho)
+  mask = property(lambda self: self.linear.mask)
+
+  def point_weights(self):
+    """W = w detJ (E, Q^d)."""
+    return self.linear.point_weights()
+
+  def _to_grid(self, u_local):
+    """(E, n, d) element values -> (E, Q^d, d) on the quadrature grid."""
+    fes = self.fespace
+    if autodiff.needs_grad(u_local):
+      raise NotImplementedError('autograd through HyperelasticOperator')
+    d = fes.mesh.ndim
+    if u_local.dim() != 3 or u_local.shape[-1] != d:
+      raise ValueError(f'expected (E, n, {d}) local values, got '
+                       f'{tuple(u_local.shape)}')
+    return fes._interpolate(u_local.to(fes.dtype)).contiguous()
+
+  def _nodal(self, u):
+    mesh = self.fespace.mesh
+    if tuple(u.shape) != (mesh.num_nodes, mesh.ndim):
+      raise ValueError(f'expected ({mesh.num_nodes}, {mesh.ndim}) nodal '
+                       f'displacements, got {tuple(u.shape)}')
+    if autodiff.needs_grad(u):
+      raise NotImplementedError('autograd through HyperelasticOperator')
+    return _ops.gather_rows(u.to(self.fespace.dtype).contiguous(),
+                            mesh.elements)
+
+  def _assembled(self, u, local):
+    """mask * scatter(local(gather(u))) in the layout of `u`."""
+    mesh = self.fespace.mesh
+    loc = local(self._nodal(u))
+    out = _ops.scatter_add(loc, mesh.elements, mesh.num_nodes, ncomp=mesh.ndim)
+    if self.mask is not None:
+      out = out * self.mask
+    return _like_layout(out, u) if u.dtype == out.dtype else out
+
+  def _launch(self, u_local, lambda0, want_state=False, want_psi=False):
+    fes = self.fespace
+    return _ops.hyperelastic_local(
+        self._to_grid(u_local), self.parts, self.host, fes.mesh.ndim,
+        fes.quadrature.num_points, self.point_weights(), self.lam, self.mu,
+        self.rho, lambda0, mode='residual', want_state=want_state,
+        want_psi=want_psi)
+
+  def residual_local(self, u_local, lambda0=0.0):
+    """(E, n, d) element displacements -> (E, n, d) local internal force."""
+    return self.fespace._interpolate_t(self._launch(u_local, lambda0)[0])
+
+  def residual(self, u, lambda0=0.0):
+    """u (N, d), dense or component-major -> mask * R(u) in that layout.  An
+    inverted state (J <= 0 at a point) gives non-finite entries."""
+    return self._assembled(u, lambda v: self.residual_local(v, lambda0))
+
+  def energy(self, u, lambda0=0.0) -> float:
+    """Psi(u), a Python float: the kernel's per-point values summed in fp64.
+    Non-finite for an inverted state."""
+    _, _, psi = self._launch(self._nodal(u), lambda0, want_psi=True)
+    return float(torch.sum(psi, dtype=torch.float64))
+
+  def linearize(self, u, lambda0=0.0) -> HyperelasticLinearization:
+    """One residual launch at `u` that also stores the state of the tangent;
+    the result carries the residual, so a Newton step launches once."""
+    box = {}
+
+    def local(v):
+      rq, box['state'], _ = self._launch(v, lambda0, want_state=True)
+      return self.fespace._interpolate_t(rq)
+    res = self._assembled(u, local)
+    return HyperelasticLinearization(state=box['state'], residual=res,
+                                     lambda0=float(lambda0))
+
+  def tangent(self, state, lambda0=0.0) -> HyperelasticTangent:
+    """The tangent at the linearisation `state` (a `HyperelasticLinearization`
+    or its state tensor): one tangent-mode launch per apply."""
+    if isinstance(state, HyperelasticLinearization):
+      state = state.state
+    return HyperelasticTangent(self, state, lambda0)

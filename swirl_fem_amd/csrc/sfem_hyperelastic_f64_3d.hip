@@ -1,0 +1,6 @@
+// Instantiations of the neo-Hookean kernel, residual and tangent modes:
+// double, 3D, P = 2..12.
+#include "sfem_hyperelastic.h"
+namespace sfem {
+SFEM_DEFINE_HYPERELASTIC_DISPATCH(double, 3)
+}  // namespace sfem

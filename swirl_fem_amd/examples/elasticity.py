@@ -208,27 +208,7 @@ def _solve(mesh: Mesh, body_force,
   dtype, device = mesh.dtype, mesh.device
   lambda0 = float(lambda0)
 
-  fixed = torch.zeros((N, d), dtype=torch.bool, device=device)
-  u_D = torch.zeros((N, d), dtype=dtype, device=device)
-  tractions = []
-  for group, (bctype, value) in boundary_conditions.items():
-    if bctype not in (BCType.DIRICHLET, BCType.NEUMANN):
-      raise ValueError(f'unsupported boundary condition type {bctype!r} on '
-                       f'{group!r}: DIRICHLET or NEUMANN')
-    entries = _component_values(group, value, d)
-    if bctype == BCType.DIRICHLET:
-      if group not in mesh.physical_masks:
-        raise KeyError(f'unknown physical group {group!r}')
-      m = mesh.physical_masks[group]
-      for c, entry in enumerate(entries):
-        if entry is None:
-          continue
-        u_D[:, c] = torch.where(m, _nodal(mesh, entry, dtype, device),
-                                u_D[:, c])
-        fixed[:, c] |= m
-    else:
-      tractions += [(group, c, g) for c, g in enumerate(entries)
-                    if g is not None]
+  fixed, u_D, tractions = _boundary_data(mesh, boundary_conditions)
   has_fixed = bool(fixed.any())
   singular = ValueError(
       'lambda0 rho = 0 everywhere and no component of any node is fixed: the '
@@ -247,16 +227,7 @@ def _solve(mesh: Mesh, body_force,
   if not has_fixed and bool((torch.as_tensor(op.rho) == 0).all()):
     raise singular
 
-  f = body_force(mesh.node_coords) if callable(body_force) else body_force
-  f = torch.as_tensor(f, dtype=dtype, device=device)
-  if tuple(f.shape) == (d,):
-    f = f[None, :].expand(N, d)
-  if tuple(f.shape) != (N, d):
-    raise ValueError(f'body_force: shape {tuple(f.shape)}; expected ({d},), '
-                     f'({N}, {d}) or a callable that returns ({N}, {d})')
-  rhs = fespace.helmholtz_operator(None).apply(f.contiguous(), 1.0, 0.0)
-  for group, c, g in tractions:
-    rhs[:, c] += fespace.boundary_covector(group, g)
+  rhs = _load_vector(fespace, body_force, tractions)
   if has_fixed:
     rhs = rhs - full.apply(u_D, lambda0)
   keep = (~fixed).to(dtype)
@@ -279,6 +250,54 @@ def _solve(mesh: Mesh, body_force,
   if return_info:
     return u, info
   return u
+
+
+def _boundary_data(mesh, boundary_conditions):
+  """(fixed (N, d) bool, u_D (N, d), [(group, component, traction)]) of the
+  `boundary_conditions` of `solve_elasticity`."""
+  d, N = mesh.ndim, mesh.num_nodes
+  dtype, device = mesh.dtype, mesh.device
+  fixed = torch.zeros((N, d), dtype=torch.bool, device=device)
+  u_D = torch.zeros((N, d), dtype=dtype, device=device)
+  tractions = []
+  for group, (bctype, value) in boundary_conditions.items():
+    if bctype not in (BCType.DIRICHLET, BCType.NEUMANN):
+      raise ValueError(f'unsupported boundary condition type {bctype!r} on '
+                       f'{group!r}: DIRICHLET or NEUMANN')
+    entries = _component_values(group, value, d)
+    if bctype == BCType.DIRICHLET:
+      if group not in mesh.physical_masks:
+        raise KeyError(f'unknown physical group {group!r}')
+      m = mesh.physical_masks[group]
+      for c, entry in enumerate(entries):
+        if entry is None:
+          continue
+        u_D[:, c] = torch.where(m, _nodal(mesh, entry, dtype, device),
+                                u_D[:, c])
+        fixed[:, c] |= m
+    else:
+      tractions += [(group, c, g) for c, g in enumerate(entries)
+                    if g is not None]
+  return fixed, u_D, tractions
+
+
+def _load_vector(fespace, body_force, tractions):
+  """The (N, d) covector B f + b_N of a nodal body force and the tractions of
+  `_boundary_data`."""
+  mesh = fespace.mesh
+  d, N = mesh.ndim, mesh.num_nodes
+  dtype, device = mesh.dtype, mesh.device
+  f = body_force(mesh.node_coords) if callable(body_force) else body_force
+  f = torch.as_tensor(f, dtype=dtype, device=device)
+  if tuple(f.shape) == (d,):
+    f = f[None, :].expand(N, d)
+  if tuple(f.shape) != (N, d):
+    raise ValueError(f'body_force: shape {tuple(f.shape)}; expected ({d},), '
+                     f'({N}, {d}) or a callable that returns ({N}, {d})')
+  rhs = fespace.helmholtz_operator(None).apply(f.contiguous(), 1.0, 0.0)
+  for group, c, g in tractions:
+    rhs[:, c] += fespace.boundary_covector(group, g)
+  return rhs
 
 
 def _check_mesh(mesh, who):

@@ -1,0 +1,218 @@
+"""Finite-strain elasticity of a compressible neo-Hookean solid.
+
+    lambda0 rho u - Div P(F) = f   in the reference mesh,   F = I + grad u,
+    P(F) = mu (F - F^-T) + lambda ln J F^-T,   J = det F,
+    u_c = g_c on the fixed components of Dirichlet groups,
+    (P N)_c = t_c on Neumann groups (dead loads: traction per unit reference
+    area in Cartesian components; zero on every free component of the
+    boundary that no group names),
+
+for displacements u (N, d), total Lagrangian; plane strain in 2D.  The stored
+energy is psi = mu/2 (F:F - d) - mu ln J + lambda/2 (ln J)^2, whose
+linearisation at u = 0 is the material of `examples/elasticity.py`.
+
+Quadrature, boundary data and the load vector are those of
+`solve_elasticity`.  The loads are applied in `load_steps` equal increments;
+each increment is solved by Newton's method on the free components,
+
+    r = keep (R(u) - f_ext),   T(u) dw = -r  (CG),   u <- u + t dw,
+
+with a backtracking line search on |r| (`FiniteElementSpace.
+hyperelastic_operator`): one residual launch per trial state,
+which also stores what the tangent needs, one tangent launch per CG iteration.
+"""
+
+from __future__ import annotations
+
+import math
+from typing import Mapping, Tuple
+
+import torch
+
+from swirl_fem_amd.core.fespace import FiniteElementSpace
+from swirl_fem_amd.core.interpolation import NodeType
+from swirl_fem_amd.core.interpolation import Quadrature1D
+from swirl_fem_amd.core.mesh import Mesh
+from swirl_fem_amd.examples.elasticity import _boundary_data
+from swirl_fem_amd.examples.elasticity import _check_every
+from swirl_fem_amd.examples.elasticity import _check_mesh
+from swirl_fem_amd.examples.elasticity import _load_vector
+from swirl_fem_amd.examples.elasticity import _requires_grad
+from swirl_fem_amd.examples.poisson import BCType
+from swirl_fem_amd.linalg.cg import cg
+
+# pylint: disable=invalid-name
+
+LINE_SEARCH_HALVINGS = 10     # t = 1, 1/2, ..., 2^-10
+ARMIJO = 1e-4
+
+
+def solve_hyperelasticity(mesh: Mesh, body_force,
+                          boundary_conditions: Mapping[str,
+                                                       Tuple[BCType, object]],
+                          *, lame_lambda, lame_mu, density=None,
+                          lambda0: float = 0.0, load_steps: int = 1,
+                          newton_rtol: float = 1e-8, newton_atol: float = 0.0,
+                          max_newton: int = 25, linear_rtol: float = 1e-6,
+                          preconditioner=None, u0=None,
+                          return_info: bool = False):
+  """Solves `lambda0 rho u - Div P(I + grad u) = body_force` for a
+  compressible neo-Hookean material; returns u (N, d).
+
+  `lame_lambda`, `lame_mu`, `density`, `body_force` and
+  `boundary_conditions` take the forms of `solve_elasticity`: per-component
+  Dirichlet values (None leaves a component free, so rollers and symmetry
+  planes work) and Neumann values, here dead loads: the traction P N per unit
+  reference area, in Cartesian components.
+
+  For load step k = 1 .. `load_steps` the body force, the tractions and the
+  Dirichlet values are scaled by k / load_steps, the fixed components of u are
+  set to the scaled values and Newton iterates on the free ones from the
+  previous step's solution (`u0` (N, d), default zero, before the first).  An
+  iteration stops the step when |r| <= max(newton_rtol |r_0|, newton_atol)
+  with r_0 the residual at the start of the step; otherwise it solves
+  T(u) dw = -r by CG to `linear_rtol` and backtracks t = 1, 1/2, .., 2^-10
+  until |r(u + t dw)| is finite and <= (1 - 1e-4 t) |r|.  A trial state with
+  an inverted element (J <= 0, a non-finite residual) is rejected like any
+  other.
+
+  `preconditioner`: None, 'jacobi' or a callable `(op, lambda0) -> M`, built
+  once per solve on the linear `ElasticityOperator` with the same mask and
+  coefficients (the tangent at u = 0), so
+  `linalg.pmg_elasticity.ElasticityPMultigrid` works unchanged.
+
+  Raises RuntimeError, naming the load step and the iteration, when the line
+  search is exhausted, when CG breaks down (the tangent can lose
+  definiteness) and when `max_newton` iterations do not converge.  With
+  `return_info` returns (u, info): info['load_steps'] is a list with, per load
+  step, 'residual_norms' (one per Newton iteration, the first is |r_0|),
+  'step_lengths', 'cg_iterations' and 'status'; info['status'] is
+  'converged'.
+
+  Not differentiable: inputs that require grad are refused, as are
+  partitioned meshes, ensembles, periodic images and ROBIN conditions."""
+  if isinstance(preconditioner, str) and preconditioner == 'pmg':
+    raise NotImplementedError(
+        "preconditioner='pmg' for elasticity: the V-cycle of that name is "
+        'built for the scalar operator; pass preconditioner='
+        'linalg.pmg_elasticity.ElasticityPMultigrid (or any callable '
+        '(op, lambda0) -> M)')
+  if not callable(preconditioner) and preconditioner not in (None, 'jacobi'):
+    raise ValueError(f'unknown preconditioner {preconditioner!r}')
+  if int(load_steps) != load_steps or load_steps < 1:
+    raise ValueError(f'load_steps must be a positive integer, got '
+                     f'{load_steps!r}')
+  if max_newton < 1:
+    raise ValueError(f'max_newton must be at least 1, got {max_newton!r}')
+  if _requires_grad(body_force, lame_lambda, lame_mu, density, u0):
+    raise NotImplementedError(
+        'autograd through solve_hyperelasticity: pass detached inputs')
+  _check_mesh(mesh, 'solve_hyperelasticity')
+  d, N = mesh.ndim, mesh.num_nodes
+  dtype = mesh.dtype
+  lambda0 = float(lambda0)
+  load_steps = int(load_steps)
+
+  fixed, u_D, tractions = _boundary_data(mesh, boundary_conditions)
+  has_fixed = bool(fixed.any())
+  singular = ValueError(
+      'lambda0 rho = 0 everywhere and no component of any node is fixed: the '
+      'rigid-body modes are not removed (the problem is singular)')
+  if lambda0 == 0.0 and not has_fixed:
+    raise singular
+
+  quadrature = Quadrature1D.create(
+      num_points=mesh.order + (d + 1) // 2,
+      quadrature_type=NodeType.GAUSS_LEGENDRE)
+  fespace = FiniteElementSpace.create(mesh, quadrature)
+  op = fespace.hyperelastic_operator(
+      fixed if has_fixed else None, lame_lambda=lame_lambda, lame_mu=lame_mu,
+      density=density)
+  if not has_fixed and bool((torch.as_tensor(op.rho) == 0).all()):
+    raise singular
+  f_ext = _load_vector(fespace, body_force, tractions)
+  keep = (~fixed).to(dtype)
+  f_ext = f_ext * keep
+
+  M = None
+  if preconditioner == 'jacobi':
+    from swirl_fem_amd.linalg.jacobi import JacobiPreconditioner
+    M = JacobiPreconditioner(op.linear.diagonal(lambda0).reshape(-1))
+  elif callable(preconditioner):
+    M = preconditioner(op.linear, lambda0)
+
+  if u0 is None:
+    u = torch.zeros((N, d), dtype=dtype, device=mesh.device)
+  else:
+    u = torch.as_tensor(u0, dtype=dtype, device=mesh.device)
+    if tuple(u.shape) != (N, d):
+      raise ValueError(f'u0: shape {tuple(u.shape)}; expected ({N}, {d})')
+    u = u.clone()
+
+  steps = []
+  for k in range(1, load_steps + 1):
+    scale = k / load_steps
+    u = torch.where(fixed, scale * u_D, u)
+    rec = dict(residual_norms=[], step_lengths=[], cg_iterations=[],
+               status='running')
+    steps.append(rec)
+    where = lambda it: f'load step {k} of {load_steps}, Newton iteration {it}'
+
+    def evaluate(v):
+      """(linearisation at v, r = keep (R(v) - scale f_ext), |r|)."""
+      lin = op.linearize(v, lambda0)       # the mask is applied: keep R(v)
+      r = lin.residual - scale * f_ext
+      return lin, r, float(torch.linalg.vector_norm(r))
+
+    lin, r, rnorm = evaluate(u)
+    if not math.isfinite(rnorm):
+      raise RuntimeError(
+          f'solve_hyperelasticity: the residual is not finite at the start '
+          f'of {where(0)} (an inverted element: more load steps may help)')
+    rec['residual_norms'].append(rnorm)
+    target = max(newton_rtol * rnorm, newton_atol)
+    it = 0
+    while rnorm > target:
+      if it == max_newton:
+        rec['status'] = 'max_newton'
+        raise RuntimeError(
+            f'solve_hyperelasticity: no convergence within max_newton = '
+            f'{max_newton} iterations in load step {k} of {load_steps} '
+            f'(|r| = {rnorm:.3e}, target {target:.3e})')
+      it += 1
+      T = op.tangent(lin, lambda0)
+      A = lambda x: T.apply(x.view(N, d)).reshape(-1)
+      dw, cg_info = cg(A, (-r).reshape(-1).contiguous(), tol=linear_rtol,
+                       M=M, check_every=_check_every(M))
+      rec['cg_iterations'].append(int(cg_info['num_iterations']))
+      if str(cg_info['status']).startswith('breakdown'):
+        rec['status'] = 'cg_' + cg_info['status']
+        raise RuntimeError(
+            f'solve_hyperelasticity: CG broke down ({cg_info["status"]}; the '
+            f'tangent may have lost definiteness) in {where(it)}')
+      dw = dw.view(N, d)
+      t, accepted = 1.0, False
+      for _ in range(LINE_SEARCH_HALVINGS + 1):
+        lin_t, r_t, n_t = evaluate(u + t * dw)
+        if math.isfinite(n_t) and n_t <= (1.0 - ARMIJO * t) * rnorm:
+          accepted = True
+          break
+        t *= 0.5
+      if not accepted:
+        rec['status'] = 'line_search'
+        raise RuntimeError(
+            f'solve_hyperelasticity: line search exhausted (t down to '
+            f'2^-{LINE_SEARCH_HALVINGS}) in {where(it)}, |r| = {rnorm:.3e}')
+      u = u + t * dw
+      lin, r, rnorm = lin_t, r_t, n_t
+      rec['step_lengths'].append(t)
+      rec['residual_norms'].append(rnorm)
+    rec['status'] = 'converged'
+  if return_info:
+    return u, {'load_steps': steps, 'status': 'converged',
+               'num_newton': sum(len(s['step_lengths']) for s in steps),
+               'num_cg': sum(sum(s['cg_iterations']) for s in steps)}
+  return u
+
+
+__all__ = ['BCType', 'solve_hyperelasticity']
