@@ -878,6 +878,51 @@ typedef struct sfem_hyperelastic_args {
 int sfem_hyperelastic_local(const sfem_hyperelastic_args* args,
                             sfem_stream_t stream);
 
+/* Lame and density sensitivities of that residual: for a displacement `u`
+ * whose residual launch stored `state` ((E, n, d*d + 1): F^-1 row-major and
+ * ln J per point), a second field `v` on the collocated grid ((E, n, ndim))
+ * and H_v = (1/W) Kw G_v as above, per point q
+ *
+ *   dlam[q] = W lnJ tr(F^-1 H_v)
+ *   dmu[q]  = W (F : H_v - tr(F^-1 H_v))
+ *   drho[q] = lambda0 W sum_c u_c v_c
+ *
+ * the derivatives of v^T R(u; lam, mu, rho) with respect to lam[q], mu[q] and
+ * rho[q]; tr(F^-1 H_v) = sum_{c,j} F^-1[j][c] H_v[c][j], and F is recovered
+ * from `state` by the adjugate of F^-1, so `u` is neither interpolated nor
+ * differentiated again and is read for `drho` alone.  Each output is (E, n) in
+ * the layout of the per-point coefficients, or NULL: its product and its
+ * stores are skipped, and with `dlam` and `dmu` both NULL no derivative is
+ * formed.  A point with W = 0 gives exactly 0 in every output whatever its
+ * state row holds.  Element-local: no gather, no scatter, no atomics.
+ * Geometry and launch arguments are those of sfem_elasticity_args.  ndim
+ * outside 2..3, P outside 2..12 and any other geo_mode return
+ * SFEM_EUNSUPPORTED; a NULL v, state, dmat or wdet, all three outputs NULL,
+ * `drho` without `u` or a missing geometry array is SFEM_EINVAL.  ABI version
+ * 10 (a pure addition).                                                      */
+typedef struct sfem_hyperelastic_sens_args {
+  const void* v;          /* (E, n, ndim)                                     */
+  const void* state;      /* (E, n, ndim*ndim + 1)                            */
+  const void* u;          /* (E, n, ndim), or NULL where drho is NULL         */
+  const void* wdet;       /* (E, n)                                           */
+  void* dlam;             /* (E, n) or NULL                                   */
+  void* dmu;              /* (E, n) or NULL                                   */
+  void* drho;             /* (E, n) or NULL                                   */
+  double lambda0;
+  const void* kfac;       /* per-point weighted cofactors or NULL             */
+  const void* geo_elem;   /* (E, 24) or NULL                                  */
+  const int32_t* geo_index; /* (E,) slot of element e in kfac, or NULL = e    */
+  const int32_t* elem_list; /* element ids of this launch, or NULL = all      */
+  const void* dmat;       /* HOST (P, P)                                      */
+  const void* weights;    /* HOST (P,)                                        */
+  const void* nodes;      /* HOST (P,)                                        */
+  int64_t num_elements;
+  int64_t num_listed;
+  int32_t ndim, P, dtype, geo_mode;
+} sfem_hyperelastic_sens_args;
+int sfem_hyperelastic_sens(const sfem_hyperelastic_sens_args* args,
+                           sfem_stream_t stream);
+
 /* ------------------------------------- fields at points: locate, eval, eval^T ---
  * A field of order P1 - 1 on element e is u(xi) = sum_n u[elements[e, n]]
  * l_n(xi) with l_n the tensor product of the 1D Lagrange polynomials on

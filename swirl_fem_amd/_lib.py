@@ -206,6 +206,18 @@ class HyperelasticArgs(ctypes.Structure):
   ]
 
 
+class HyperelasticSensArgs(ctypes.Structure):
+  """Mirror of `struct sfem_hyperelastic_sens_args`."""
+  _fields_ = [
+      ('v', c_ptr), ('state', c_ptr), ('u', c_ptr), ('wdet', c_ptr),
+      ('dlam', c_ptr), ('dmu', c_ptr), ('drho', c_ptr), ('lambda0', c_dbl),
+      ('kfac', c_ptr), ('geo_elem', c_ptr), ('geo_index', c_ptr),
+      ('elem_list', c_ptr), ('dmat', c_ptr), ('weights', c_ptr),
+      ('nodes', c_ptr), ('num_elements', c_i64), ('num_listed', c_i64),
+      ('ndim', c_i32), ('P', c_i32), ('dtype', c_i32), ('geo_mode', c_i32),
+  ]
+
+
 SFEM_POINT_CHUNK = 64
 
 
@@ -371,6 +383,7 @@ SIGNATURES = {
     'sfem_elasticity_stress_vjp': [ctypes.POINTER(ElasticityStressVjpArgs),
                                    c_ptr],
     'sfem_hyperelastic_local': [ctypes.POINTER(HyperelasticArgs), c_ptr],
+    'sfem_hyperelastic_sens': [ctypes.POINTER(HyperelasticSensArgs), c_ptr],
     'sfem_point_locate': [ctypes.POINTER(PointLocateArgs), c_ptr],
     'sfem_point_eval': [ctypes.POINTER(PointArgs), c_ptr],
     'sfem_point_eval_t': [ctypes.POINTER(PointArgs), c_ptr],

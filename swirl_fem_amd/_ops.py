@@ -1464,6 +1464,54 @@ def elasticity_sens(u_q, v_q, parts, host, ndim, P, wdet, lambda0=0.0,
   return out
 
 
+def hyperelastic_sens(v_q, state, parts, host, ndim, P, wdet, u_q=None,
+                      lambda0=0.0, want=(True, True, True)):
+  """Per-point sensitivities of v . R(u) of the neo-Hookean residual with
+  respect to (lam, mu, rho) on a collocated grid (`sfem_hyperelastic_sens`):
+  `v_q` (E, P^d, d), `state` (E, P^d, d*d + 1) as a residual launch of
+  `hyperelastic_local` stored it at u, `wdet` (E, P^d); `u_q` (E, P^d, d) is
+  read for drho alone.  Returns (dlam, dmu, drho), (E, P^d) each, None where
+  `want` is false."""
+  v_q = v_q.contiguous()
+  dev = _dev(v_q)
+  E, n, d = v_q.shape
+  if d != ndim or n != P ** ndim:
+    raise ValueError(f'expected (E, {P ** ndim}, {ndim}) local values, got '
+                     f'{tuple(v_q.shape)}')
+  if wdet is None:
+    raise ValueError('hyperelastic_sens needs `wdet`')
+  want = tuple(bool(w) for w in want)
+  if len(want) != 3 or not any(want):
+    raise ValueError('`want` names (dlam, dmu, drho), at least one of them')
+  tensors = []
+  state = _field(state, 'state', (E, n, d * d + 1), v_q, 'second field',
+                 tensors)
+  if state is None:
+    raise ValueError('hyperelastic_sens needs the `state` of a residual '
+                     'launch')
+  u_q = _field(u_q, 'displacement', (E, n, d), v_q, 'second field', tensors)
+  if want[2] and u_q is None:
+    raise ValueError('drho needs the displacement `u_q`')
+  wdet = _field(wdet, 'wdet', (E, n), v_q, 'second field', tensors)
+  out = tuple(torch.zeros((E, n), dtype=v_q.dtype, device=dev) if w else None
+              for w in want)
+  args = _lib.HyperelasticSensArgs(
+      v=v_q.data_ptr(), state=state.data_ptr(), u=_dptr(u_q),
+      wdet=wdet.data_ptr(), dlam=_dptr(out[0]), dmu=_dptr(out[1]),
+      drho=_dptr(out[2]), lambda0=float(lambda0))
+  host = {k: _host(v, v_q.dtype) for k, v in host.items()}
+  args.num_elements, args.ndim, args.P = E, ndim, P
+  args.dtype = _dtype_code(v_q)
+  with torch.cuda.device(dev):
+    for part in parts:
+      for name, value in _launch_fields(part, host, 'kfac').items():
+        setattr(args, name, value)
+      _lib.check(_lib.load().sfem_hyperelastic_sens(ctypes.byref(args),
+                                                    _stream(dev)),
+                 'sfem_hyperelastic_sens')
+  return out
+
+
 def _lame_fields(args, field, lam, mu):
   """`lam` and `mu` of a stress launch: a float or an (E, P^d) tensor each."""
   for name, value in (('lam', lam), ('mu', mu)):

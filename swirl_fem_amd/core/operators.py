@@ -2742,3 +2742,46 @@ class HyperelasticOperator:
     if isinstance(state, HyperelasticLinearization):
       state = state.state
     return HyperelasticTangent(self, state, lambda0)
+
+  def sensitivity(self, u, v, lambda0=0.0, want=(True, True, True),
+                  linearization=None):
+    """The gradient of v . R(u) WITHOUT the Dirichlet mask with respect to
+    (lame_lambda, lame_mu, density), each in the form the caller passed to
+    `create` (`reduce_coefficient_gradient`): a scalar gives a 0-dim tensor
+    (the sum over all points), (E,) the sum over each element's points,
+    (E, Q^d) per-point values.  None for a callable, for an absent density and
+    where `want` is false.  `u`, `v`: nodal (N, d), dense or component-major.
+    P is linear in the coefficients, so per point the gradients are W ln J
+    tr(F^-1 H_v), W (F : H_v - tr(F^-1 H_v)) and lambda0 W u . v (DESIGN
+    §3.21): `v` is gathered and interpolated to the quadrature grid, then one
+    launch of `sfem_hyperelastic_sens` per part reads F^-1 and ln J from the
+    state of `linearization` (a `HyperelasticLinearization` at `u`, or its
+    state tensor); without one, one `linearize(u)` launch forms it.  `u` itself
+    is interpolated for the density alone."""
+    fes = self.fespace
+    mesh = fes.mesh
+    d = mesh.ndim
+    for w in (u, v):
+      if tuple(w.shape) != (mesh.num_nodes, d):
+        raise ValueError(f'expected ({mesh.num_nodes}, {d}) nodal '
+                         f'displacements, got {tuple(w.shape)}')
+    source = self.linear.coef_source
+    if len(tuple(want)) != 3:
+      raise ValueError('`want` names (lame_lambda, lame_mu, density)')
+    tensor = lambda s: s is not None and not _is_callable_source(s)
+    wanted = tuple(bool(w) and tensor(s) for w, s in zip(want, source))
+    if not any(wanted):
+      return None, None, None
+    if linearization is None:
+      linearization = self.linearize(u.detach(), lambda0)
+    state = (linearization.state
+             if isinstance(linearization, HyperelasticLinearization)
+             else linearization)
+    grid = lambda w: fes._interpolate(_ops.gather_rows(
+        w.detach().to(fes.dtype).contiguous(), mesh.elements)).contiguous()
+    grads = _ops.hyperelastic_sens(
+        grid(v), state, self.parts, self.host, d, fes.quadrature.num_points,
+        self.point_weights(), grid(u) if wanted[2] else None, lambda0,
+        want=wanted)
+    return tuple(reduce_coefficient_gradient(g, s)
+                 for g, s in zip(grads, source))

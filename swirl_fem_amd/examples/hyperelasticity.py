@@ -20,6 +20,10 @@ each increment is solved by Newton's method on the free components,
 with a backtracking line search on |r| (`FiniteElementSpace.
 hyperelastic_operator`): one residual launch per trial state,
 which also stores what the tangent needs, one tangent launch per CG iteration.
+
+With `differentiable=True` the solve is one autograd node: the
+adjoint solve runs CG on the tangent at the converged state, the coefficient
+gradients come from `sfem_hyperelastic_sens` on the state that launch stored.
 """
 
 from __future__ import annotations
@@ -36,6 +40,7 @@ from swirl_fem_amd.core.mesh import Mesh
 from swirl_fem_amd.examples.elasticity import _boundary_data
 from swirl_fem_amd.examples.elasticity import _check_every
 from swirl_fem_amd.examples.elasticity import _check_mesh
+from swirl_fem_amd.examples.elasticity import _detached
 from swirl_fem_amd.examples.elasticity import _load_vector
 from swirl_fem_amd.examples.elasticity import _requires_grad
 from swirl_fem_amd.examples.poisson import BCType
@@ -47,6 +52,66 @@ LINE_SEARCH_HALVINGS = 10     # t = 1, 1/2, ..., 2^-10
 ARMIJO = 1e-4
 
 
+class _HyperelasticSolve(torch.autograd.Function):
+  """`_solve` as one autograd node: the adjoint solve on the tangent at the
+  final accepted linearisation, the mass apply and the coefficient
+  sensitivities in `backward`."""
+
+  @staticmethod
+  def forward(ctx, body_force, lame_lambda, lame_mu, density, mesh,
+              boundary_conditions, kwargs, adjoint_rtol, holder):
+    state = {}
+    u, info = _solve(mesh, _detached(body_force), boundary_conditions,
+                     lame_lambda=_detached(lame_lambda),
+                     lame_mu=_detached(lame_mu), density=_detached(density),
+                     return_info=True, _state=state, **kwargs)
+    holder['info'] = info
+    state.update(holder=holder, adjoint_rtol=adjoint_rtol)
+    ctx.state = state
+    ctx.save_for_backward(u)
+    ctx.force_shape = (tuple(body_force.shape)
+                       if isinstance(body_force, torch.Tensor) else None)
+    ctx.like = [(v.dtype, v.device) if isinstance(v, torch.Tensor) else None
+                for v in (body_force, lame_lambda, lame_mu, density)]
+    return u
+
+  @staticmethod
+  @torch.autograd.function.once_differentiable
+  def backward(ctx, u_bar):
+    st = ctx.state
+    op, keep, l0, lin = st['op'], st['keep'], st['lambda0'], st['lin']
+    N, d = keep.shape
+    # keep T(u) keep v = keep u_bar: the tangent is symmetric (dead loads)
+    # and the operator's mask is `keep`
+    T = op.tangent(lin, l0)
+    A = lambda x: T.apply(x.view(N, d)).reshape(-1)
+    rhs = (u_bar.detach().to(keep.dtype) * keep).reshape(-1).contiguous()
+    v, info = cg(A, rhs, tol=st['adjoint_rtol'], M=st['M'],
+                 check_every=_check_every(st['M']))
+    st['holder']['info']['adjoint'] = info
+    if str(info['status']).startswith('breakdown'):
+      raise RuntimeError(
+          f'solve_hyperelasticity: CG broke down in the adjoint solve of '
+          f'backward ({info["status"]}; the tangent at the converged state '
+          f'may have lost definiteness)')
+    v = v.view(N, d)
+    need = ctx.needs_input_grad
+    grads = [None, None, None, None]
+    if need[0]:
+      g = st['Bf'](v)
+      grads[0] = g.sum(dim=0) if ctx.force_shape == (d,) else g
+    if any(need[1:4]):
+      sens = op.sensitivity(ctx.saved_tensors[0], v, l0,
+                            want=tuple(need[1:4]), linearization=lin)
+      for n, g in enumerate(sens):
+        if need[1 + n] and g is not None:
+          grads[1 + n] = -g
+    for n, like in enumerate(ctx.like):
+      if grads[n] is not None and like is not None:
+        grads[n] = grads[n].to(dtype=like[0], device=like[1])
+    return (*grads, None, None, None, None, None)
+
+
 def solve_hyperelasticity(mesh: Mesh, body_force,
                           boundary_conditions: Mapping[str,
                                                        Tuple[BCType, object]],
@@ -55,7 +120,8 @@ def solve_hyperelasticity(mesh: Mesh, body_force,
                           newton_rtol: float = 1e-8, newton_atol: float = 0.0,
                           max_newton: int = 25, linear_rtol: float = 1e-6,
                           preconditioner=None, u0=None,
-                          return_info: bool = False):
+                          return_info: bool = False,
+                          differentiable: bool = False, adjoint_rtol=None):
   """Solves `lambda0 rho u - Div P(I + grad u) = body_force` for a
   compressible neo-Hookean material; returns u (N, d).
 
@@ -89,8 +155,28 @@ def solve_hyperelasticity(mesh: Mesh, body_force,
   'step_lengths', 'cg_iterations' and 'status'; info['status'] is
   'converged'.
 
-  Not differentiable: inputs that require grad are refused, as are
-  partitioned meshes, ensembles, periodic images and ROBIN conditions."""
+  Autograd is opt-in: without `differentiable=True` inputs that
+  require grad are refused.  With it the result is differentiable with respect
+  to `body_force` and to `lame_lambda`, `lame_mu` and `density` given as
+  tensors that require grad (scalar, (E,) or (E, Q^d); the gradient has the
+  form passed in).  The gradient is that of the converged state: load stepping
+  does not enter it, and its error scales with the Newton residual that is
+  left, so tighten `newton_rtol` for an accurate gradient.  Backward is one CG
+  solve on the tangent at the final accepted linearisation with the forward
+  solve's preconditioner, to `adjoint_rtol` (None: `newton_rtol`; the forward
+  `linear_rtol` is that of an inexact Newton step and would limit the
+  gradient), one launch of the sensitivity kernel
+  (`HyperelasticOperator.sensitivity`) and one mass apply; with `return_info`
+  the info then also carries `adjoint`, the adjoint solve's CG info.  A
+  breakdown of that CG raises RuntimeError and names the adjoint solve.
+  Gradients with respect to Dirichlet values, tractions, through callables and
+  with respect to the mesh are not propagated, nor are second derivatives.
+  `u0` that requires grad is refused either way: the solution does not depend
+  on it.  When nothing requires grad the solve runs exactly as without the
+  keyword and builds no autograd node.
+
+  Partitioned meshes, ensembles, periodic images and ROBIN conditions are
+  refused."""
   if isinstance(preconditioner, str) and preconditioner == 'pmg':
     raise NotImplementedError(
         "preconditioner='pmg' for elasticity: the V-cycle of that name is "
@@ -104,9 +190,38 @@ def solve_hyperelasticity(mesh: Mesh, body_force,
                      f'{load_steps!r}')
   if max_newton < 1:
     raise ValueError(f'max_newton must be at least 1, got {max_newton!r}')
-  if _requires_grad(body_force, lame_lambda, lame_mu, density, u0):
+  if _requires_grad(u0):
     raise NotImplementedError(
-        'autograd through solve_hyperelasticity: pass detached inputs')
+        'autograd through solve_hyperelasticity with respect to u0: the '
+        'solution does not depend on the initial guess; pass it detached')
+  grad = _requires_grad(body_force, lame_lambda, lame_mu, density)
+  if grad and not differentiable:
+    raise NotImplementedError(
+        'autograd through solve_hyperelasticity: pass differentiable=True, '
+        'or detached inputs')
+  kwargs = dict(lambda0=lambda0, load_steps=load_steps,
+                newton_rtol=newton_rtol, newton_atol=newton_atol,
+                max_newton=max_newton, linear_rtol=linear_rtol,
+                preconditioner=preconditioner, u0=u0)
+  if not grad:
+    return _solve(mesh, body_force, boundary_conditions,
+                  lame_lambda=lame_lambda, lame_mu=lame_mu, density=density,
+                  return_info=return_info, **kwargs)
+  holder = {}
+  rtol = newton_rtol if adjoint_rtol is None else adjoint_rtol
+  u = _HyperelasticSolve.apply(body_force, lame_lambda, lame_mu, density, mesh,
+                               boundary_conditions, kwargs, float(rtol),
+                               holder)
+  return (u, holder['info']) if return_info else u
+
+
+def _solve(mesh: Mesh, body_force, boundary_conditions, *, lame_lambda,
+           lame_mu, density, lambda0, load_steps, newton_rtol, newton_atol,
+           max_newton, linear_rtol, preconditioner, u0, return_info=False,
+           _state=None):
+  """The body of `solve_hyperelasticity`, its arguments checked.  `_state`: a
+  dict that receives what the adjoint solve needs (the operator, the mask,
+  the preconditioner, the final linearisation, the mass apply)."""
   _check_mesh(mesh, 'solve_hyperelasticity')
   d, N = mesh.ndim, mesh.num_nodes
   dtype = mesh.dtype
@@ -208,6 +323,10 @@ def solve_hyperelasticity(mesh: Mesh, body_force,
       rec['step_lengths'].append(t)
       rec['residual_norms'].append(rnorm)
     rec['status'] = 'converged'
+  if _state is not None:
+    _state.update(op=op, keep=keep, M=M, lambda0=lambda0, lin=lin,
+                  Bf=lambda x: fespace.helmholtz_operator(None).apply(
+                      x.contiguous(), 1.0, 0.0))
   if return_info:
     return u, {'load_steps': steps, 'status': 'converged',
                'num_newton': sum(len(s['step_lengths']) for s in steps),
