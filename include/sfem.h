@@ -1506,8 +1506,10 @@ int sfem_ell_spmv(const int32_t* cols, const void* vals, const void* x,
  * swirl_fem/examples/poisson.py:79-90, served by examples/helmholtz.py).
  * A facet is a (d-1)-dimensional isoparametric element with its own nodes,
  * integrated with the space's 1D rule in each facet direction.  One wave per
- * facet; (p1, q) pairs with q = p1 or p1 + 1, 2 <= p1 <= 13, are compiled
- * with fixed sizes, others (p1 <= 16, q <= 16) run with run-time sizes.
+ * facet.  Accepted: 2 <= p1 <= 16 and 1 <= q <= 16 (SFEM_EINVAL otherwise,
+ * for num_facets = 0 too).  The 24 pairs with q = p1 or p1 + 1, 2 <= p1 <= 13,
+ * are compiled with fixed sizes; every other pair (q < p1, q > p1 + 1,
+ * p1 >= 14) runs with run-time sizes.
  *   coords (N, ndim), facets (F, p1^(ndim-1)) int32 node ids in [0, N),
  *       lexicographic on the facet;
  *   bmat (q, p1) row-major: B, the 1D interpolation from the nodes to the

@@ -2178,6 +2178,10 @@ def boundary_covector(g, nodal, facets, wj, bmat, ndim):
     raise ValueError('boundary_covector: one dtype for g, wJ and B')
   q, p1 = bmat.shape
   F = facets.shape[0]
+  if (facets.dtype != torch.int32 or
+      tuple(facets.shape) != (F, p1 ** (ndim - 1))):
+    raise ValueError(f'boundary_covector: facets must be (F, '
+                     f'{p1 ** (ndim - 1)}) int32')
   if tuple(wj.shape) != (F, q ** (ndim - 1)):
     raise ValueError('boundary_covector: wJ does not match the facets')
   if not nodal and tuple(g.shape) != tuple(wj.shape):

@@ -6,10 +6,12 @@
 //
 // One wave per facet, the facet's values in LDS, one thread per LINE of the
 // axis being contracted (the scheme of `tensor_interp_kernel` and the
-// p-multigrid transfers).  The (P+1, Q) pairs the solvers use (Q = P+1: GLL,
-// Q = P+2 at most for the Gauss rule of `solve_poisson`) are compiled with
-// their sizes fixed for P = 1..12; any other pair runs the same code with
-// run-time sizes.
+// p-multigrid transfers).  Accepted: 2 <= P+1 <= 16 and 1 <= Q <= 16.  The 24
+// (P+1, Q) pairs the solvers use, Q = P+1 (the GLL rule, a Gauss rule of P+1
+// points) and Q = P+2 (the 3D Gauss rule of `solve_poisson`) for P+1 = 2..13,
+// are compiled with their sizes fixed; any other pair (Q < P+1, Q > P+2,
+// P+1 >= 14) runs the same code with run-time sizes and a register array of
+// 16.  Every pair is launched by `tests/test_gpu_boundary_kernels.py`.
 //
 // sfem_boundary_geom: x_q = (B (x) B) X, the tangents (D_q (x) B) X and
 //   (B (x) D_q) X, wJ_q = w_s w_t |x_s x x_t| (3D mesh, 2D facets) or
@@ -363,7 +365,7 @@ int launch_boundary(bool covector, const void* in, int nodal,
 }
 
 // (P+1, Q): Q = P+1 (the GLL rule on the nodes, a Gauss rule of P+1 points)
-// and Q = P+2 (the 3D Gauss rule of solve_poisson), P = 1..12.
+// and Q = P+2 (the 3D Gauss rule of solve_poisson), P+1 = 2..13.
 template <typename T, int K>
 int dispatch_boundary(bool covector, const void* in, int nodal,
                       const int32_t* facets, const void* bmat,
