@@ -923,6 +923,97 @@ typedef struct sfem_hyperelastic_sens_args {
 int sfem_hyperelastic_sens(const sfem_hyperelastic_sens_args* args,
                            sfem_stream_t stream);
 
+/* --------------------------------------- small-strain J2 (von Mises) plasticity ---
+ * Rate-independent von Mises plasticity with linear isotropic hardening on
+ * the collocated grid of sfem_elasticity_args, element-local, modelled on
+ * sfem_hyperelastic_local: a residual launch that stores a per-point state and
+ * a tangent launch that reads it.  With H[c][j] = d u_c / d x_j = (1/W) sum_a
+ * Kw[a][j] G[c][a] as above, eps = sym(H) (plane strain in 2D: the 3 x 3
+ * tensor with eps_zz = eps_xz = eps_yz = 0) and the committed history
+ * (eps_p, alpha) of the point, eps_p symmetric and trace-free, alpha >= 0:
+ *
+ *   e = eps - eps_p,  s_tr = 2 mu dev(e),  q = sqrt(3/2) |s_tr|
+ *   f = q - (sigma_y + Hh alpha)
+ *   f <= 0: sigma = lam tr(eps) I + 2 mu e,  history unchanged,
+ *           a = 2 mu, b = 0, n = 0
+ *   f >  0: dg = f / (3 mu + Hh),  n = s_tr / |s_tr|
+ *           eps_p' = eps_p + sqrt(3/2) dg n,  alpha' = alpha + dg
+ *           sigma  = (lam + 2 mu / 3) tr(eps) I + theta s_tr
+ *           theta  = 1 - 3 mu dg / q,  a = 2 mu theta
+ *           b      = 2 mu (1 / (1 + Hh / (3 mu)) - (1 - theta))
+ *   dsigma[deps] = lam tr(deps) I + 2 mu deps - (2 mu - a) dev(deps)
+ *                  - b (n : deps) n
+ *
+ * Voigt slots are those of sfem_elasticity_stress: 3D (xx, yy, zz, xy, xz,
+ * yz); 2D (xx, yy, xy), with zz last where it is stored.  Per point
+ *
+ *   history  NH = 7 in 3D: eps_p in the six slots, then alpha
+ *            NH = 4 in 2D: eps_p xx, yy, xy, then alpha (eps_p,zz = -(xx + yy))
+ *   lin      NL = 8 in 3D: a, b, then n in the six slots
+ *            NL = 5 in 2D: a, b, n_xx, n_yy, n_xy (deps_zz = 0)
+ *   stress   6 in 3D; 4 in 2D: xx, yy, xy, zz
+ *
+ * mode = SFEM_PLAST_RESIDUAL: `u` is the displacement and
+ *
+ *   out[e,m,c] = sum_a sum_q D_a[q,m] (sum_j Kw[a][j] sigma[c][j])(q)
+ *                + lambda0 rho W u_c(m)
+ *
+ * the local part of R(u) = int sigma : grad v + lambda0 int rho u . v.
+ * `hist_in` ((E, n, NH), or NULL for virgin material) is read and never
+ * written.  `hist_out` (E, n, NH) receives the trial history (eps_p',
+ * alpha'), `lin` (E, n, NL) the state of the tangent and `stress` (E, n, 6 | 4)
+ * sigma, each where non-NULL.  `hist_in` and `hist_out` must not be the same
+ * array.
+ *
+ * mode = SFEM_PLAST_TANGENT: `u` is an increment w, `lin` the output of a
+ * residual launch at the point of linearisation, and
+ *
+ *   out[e,m,c] = sum_a sum_q D_a[q,m] (sum_j Kw[a][j] dsigma[deps_w][c][j])(q)
+ *                + lambda0 rho W w_c(m)
+ *
+ * with no square root and no division.  With lin = (2 mu, 0, 0) this is
+ * sfem_elasticity_local.
+ *
+ * Points with W = 0 take H = 0 and every output is finite there.  `lam`,
+ * `mu`, `rho`, `yield` (sigma_y > 0) and `hard` (Hh >= 0) are (E, n) arrays
+ * or NULL for their constants; the geometry and launch arguments are those of
+ * sfem_elasticity_args.  ndim outside 2..3, P outside 2..12 and any other
+ * geo_mode or mode return SFEM_EUNSUPPORTED; a NULL u, out, dmat, wdet or a
+ * missing geometry array, the tangent mode with a NULL `lin` or with a
+ * non-NULL `hist_in`, `hist_out` or `stress`, and hist_in == hist_out (both
+ * non-NULL) are SFEM_EINVAL.  ABI version 10 (a pure addition).              */
+#define SFEM_PLAST_RESIDUAL 0
+#define SFEM_PLAST_TANGENT 1
+typedef struct sfem_plasticity_args {
+  const void* u;          /* (E, n, ndim): displacement, or the increment     */
+  void* out;              /* (E, n, ndim)                                     */
+  const void* wdet;       /* (E, n)                                           */
+  const void* lam;        /* (E, n) or NULL                                   */
+  const void* mu;         /* (E, n) or NULL                                   */
+  const void* rho;        /* (E, n) or NULL                                   */
+  double lam_const, mu_const, rho_const, lambda0;
+  const void* kfac;       /* per-point weighted cofactors or NULL             */
+  const void* geo_elem;   /* (E, 24) or NULL                                  */
+  const int32_t* geo_index; /* (E,) slot of element e in kfac, or NULL = e    */
+  const int32_t* elem_list; /* element ids of this launch, or NULL = all      */
+  const void* dmat;       /* HOST (P, P)                                      */
+  const void* weights;    /* HOST (P,)                                        */
+  const void* nodes;      /* HOST (P,)                                        */
+  int64_t num_elements;
+  int64_t num_listed;
+  int32_t ndim, P, dtype, geo_mode;
+  double yield_const, hard_const;
+  void* yield;            /* (E, n) or NULL                                   */
+  void* hard;             /* (E, n) or NULL                                   */
+  void* hist_in;          /* (E, n, NH) or NULL = virgin; residual only       */
+  void* hist_out;         /* (E, n, NH) or NULL; residual only                */
+  void* lin;              /* (E, n, NL): out (residual, or NULL), in (tangent)*/
+  void* stress;           /* (E, n, 6 | 4) or NULL; residual only             */
+  int32_t mode;           /* SFEM_PLAST_RESIDUAL / SFEM_PLAST_TANGENT         */
+} sfem_plasticity_args;
+int sfem_plasticity_local(const sfem_plasticity_args* args,
+                          sfem_stream_t stream);
+
 /* ------------------------------------- fields at points: locate, eval, eval^T ---
  * A field of order P1 - 1 on element e is u(xi) = sum_n u[elements[e, n]]
  * l_n(xi) with l_n the tensor product of the 1D Lagrange polynomials on

@@ -218,6 +218,18 @@ class HyperelasticSensArgs(ctypes.Structure):
   ]
 
 
+SFEM_PLAST_RESIDUAL, SFEM_PLAST_TANGENT = 0, 1
+
+
+class PlasticityArgs(ctypes.Structure):
+  """Mirror of `struct sfem_plasticity_args`."""
+  _fields_ = ElasticityArgs._fields_ + [
+      ('yield_const', c_dbl), ('hard_const', c_dbl), ('yield', c_ptr),
+      ('hard', c_ptr), ('hist_in', c_ptr), ('hist_out', c_ptr),
+      ('lin', c_ptr), ('stress', c_ptr), ('mode', c_i32),
+  ]
+
+
 SFEM_POINT_CHUNK = 64
 
 
@@ -384,6 +396,7 @@ SIGNATURES = {
                                    c_ptr],
     'sfem_hyperelastic_local': [ctypes.POINTER(HyperelasticArgs), c_ptr],
     'sfem_hyperelastic_sens': [ctypes.POINTER(HyperelasticSensArgs), c_ptr],
+    'sfem_plasticity_local': [ctypes.POINTER(PlasticityArgs), c_ptr],
     'sfem_point_locate': [ctypes.POINTER(PointLocateArgs), c_ptr],
     'sfem_point_eval': [ctypes.POINTER(PointArgs), c_ptr],
     'sfem_point_eval_t': [ctypes.POINTER(PointArgs), c_ptr],

@@ -1423,6 +1423,86 @@ def hyperelastic_local(u_q, parts, host, ndim, P, wdet, lam, mu, rho=None,
   return out if tangent else (out, state, psi)
 
 
+def plasticity_sizes(ndim):
+  """(NH, NL, NV): reals per point of the history, of the tangent's state
+  and of the stress of `sfem_plasticity_local`."""
+  return {2: (4, 5, 4), 3: (7, 8, 6)}[ndim]
+
+
+def plasticity_local(u_q, parts, host, ndim, P, wdet, lam, mu, rho, lambda0,
+                     yield_stress, hardening, *, mode, hist=None, lin=None,
+                     want_hist=False, want_lin=False, want_stress=False):
+  """The J2 plasticity residual or tangent on a collocated grid
+  (`sfem_plasticity_local`): `u_q` (E, P^d, d), `wdet` (E, P^d); `lam`, `mu`,
+  `rho` as in `elasticity_local`, `yield_stress` and `hardening` likewise a
+  float or an (E, P^d) tensor each.
+
+  `mode='residual'`: `u_q` is the displacement and `hist` the committed
+  history (E, P^d, NH), None for virgin material; it is read only.  Returns
+  (R (E, P^d, d), trial history (E, P^d, NH), lin (E, P^d, NL), stress
+  (E, P^d, NV)), the last three where `want_hist`, `want_lin`, `want_stress`
+  and None otherwise.  `mode='tangent'`: `u_q` is the increment and `lin`
+  that of a residual launch; returns T w (E, P^d, d).  Rows of the optional
+  outputs of elements that no part lists are zero."""
+  if mode not in ('residual', 'tangent'):
+    raise ValueError(f"mode: 'residual' or 'tangent', got {mode!r}")
+  tangent = mode == 'tangent'
+  u_q = u_q.contiguous()
+  dev = _dev(u_q)
+  E, n, d = u_q.shape
+  if d != ndim or n != P ** ndim:
+    raise ValueError(f'expected (E, {P ** ndim}, {ndim}) local values, got '
+                     f'{tuple(u_q.shape)}')
+  if wdet is None:
+    raise ValueError('plasticity_local needs `wdet`')
+  NH, NL, NV = plasticity_sizes(ndim)
+  if tangent and (want_hist or want_lin or want_stress or hist is not None):
+    raise ValueError('the history, lin and the stress belong to the residual '
+                     'mode')
+  if tangent and lin is None:
+    raise ValueError('the tangent mode needs the `lin` of a residual launch')
+  if not tangent and lin is not None:
+    raise ValueError('`lin` is an input of the tangent mode only')
+  tensors = []
+  field = lambda t, name: _field(t, name, (E, n), u_q, 'displacement', tensors)
+  if tangent:
+    lin = _field(lin, 'lin', (E, n, NL), u_q, 'displacement', tensors)
+  elif hist is not None:
+    hist = _field(hist, 'hist', (E, n, NH), u_q, 'displacement', tensors)
+  zeros = lambda k: torch.zeros((E, n, k), dtype=u_q.dtype, device=dev)
+  hist_out = zeros(NH) if want_hist else None
+  if want_lin:
+    lin = zeros(NL)
+  stress = zeros(NV) if want_stress else None
+  args = _lib.PlasticityArgs(
+      u=u_q.data_ptr(), lambda0=float(lambda0),
+      wdet=field(wdet, 'wdet').data_ptr(), hist_in=_dptr(hist),
+      hist_out=_dptr(hist_out), lin=_dptr(lin), stress=_dptr(stress),
+      mode=_lib.SFEM_PLAST_TANGENT if tangent else _lib.SFEM_PLAST_RESIDUAL)
+  for name, const, value in (
+      ('lam', 'lam_const', lam), ('mu', 'mu_const', mu),
+      ('rho', 'rho_const', 1.0 if rho is None else rho),
+      ('yield', 'yield_const', yield_stress),
+      ('hard', 'hard_const', hardening)):
+    if isinstance(value, torch.Tensor):
+      setattr(args, name, field(value, name).data_ptr())
+    else:
+      setattr(args, const, float(value))
+  out = torch.empty_like(u_q)
+  host = {k: _host(v, u_q.dtype) for k, v in host.items()}
+  args.out = out.data_ptr()
+  args.num_elements, args.ndim, args.P = E, ndim, P
+  args.dtype = _dtype_code(u_q)
+  with torch.cuda.device(dev):
+    for part in parts:
+      for name, value in _launch_fields(part, host, 'kfac').items():
+        setattr(args, name, value)
+      _lib.check(_lib.load().sfem_plasticity_local(ctypes.byref(args),
+                                                   _stream(dev)),
+                 'sfem_plasticity_local')
+  return out if tangent else (out, hist_out, lin, stress)
+
+
 def elasticity_sens(u_q, v_q, parts, host, ndim, P, wdet, lambda0=0.0,
                     want=(True, True, True)):
   """Per-point sensitivities of v . (K + lambda0 M_rho) u with respect to

@@ -623,6 +623,21 @@ class FiniteElementSpace:
         self, dirichlet_mask, lame_lambda=lame_lambda, lame_mu=lame_mu,
         density=density, geometry=geometry)
 
+  def plasticity_operator(self, dirichlet_mask=None, *, lame_lambda, lame_mu,
+                          yield_stress, hardening_modulus=0.0, density=None,
+                          geometry='auto'):
+    """Small-strain von Mises (J2) plasticity with linear isotropic hardening:
+    residual, algorithmic tangent and stress for displacements u (N, d) and a
+    history at the quadrature points (`operators.PlasticityOperator`, DESIGN
+    §3.22).  `yield_stress` > 0 and `hardening_modulus` >= 0 take the forms of
+    the Lame parameters; the other arguments are those of
+    `elasticity_operator`, which is its tangent before first yield."""
+    from swirl_fem_amd.core import operators
+    return operators.PlasticityOperator.create(
+        self, dirichlet_mask, lame_lambda=lame_lambda, lame_mu=lame_mu,
+        yield_stress=yield_stress, hardening_modulus=hardening_modulus,
+        density=density, geometry=geometry)
+
 
 class BoundaryMassOperator:
   """`scale * M u` with M the facet mass matrix `(B (x) B)^T diag(aw) (B (x) B)`
