@@ -1321,41 +1321,65 @@ def transport_rhs_vjp(cotangent, levels, parts, host, ndim, P, wdet, want):
   return out, dsource
 
 
+def _local_shape(x, ndim, P, wdet, who):
+  """(E, n, d) of the (E, P^d, d) values `x` of an elasticity-family launch,
+  after the checks every one of them makes; `who` needs `wdet`."""
+  E, n, d = x.shape
+  if d != ndim or n != P ** ndim:
+    raise ValueError(f'expected (E, {P ** ndim}, {ndim}) local values, got '
+                     f'{tuple(x.shape)}')
+  if wdet is None:
+    raise ValueError(f'{who} needs `wdet`')
+  return E, n, d
+
+
+def _coefficients(args, field, triples):
+  """Coefficients that are a float or an (E, P^d) tensor each: `triples` of
+  (field of `args` for the tensor, field for the float, value)."""
+  for name, const, value in triples:
+    if isinstance(value, torch.Tensor):
+      setattr(args, name, field(value, name).data_ptr())
+    else:
+      setattr(args, const, float(value))
+
+
+def _lame(lam, mu, rho=None):
+  """The triples of `_coefficients` for lam, mu and rho (None = 1)."""
+  return (('lam', 'lam_const', lam), ('mu', 'mu_const', mu),
+          ('rho', 'rho_const', 1.0 if rho is None else rho))
+
+
+def _launch_parts(entry, args, ref, E, ndim, P, parts, host):
+  """One launch of the entry point `entry` per geometry part, after the sizes
+  and the dtype of `ref` are set in `args`."""
+  dev = ref.device
+  host = {k: _host(v, ref.dtype) for k, v in host.items()}
+  args.num_elements, args.ndim, args.P = E, ndim, P
+  args.dtype = _dtype_code(ref)
+  fn = getattr(_lib.load(), entry)
+  with torch.cuda.device(dev):
+    for part in parts:
+      for name, value in _launch_fields(part, host, 'kfac').items():
+        setattr(args, name, value)
+      _lib.check(fn(ctypes.byref(args), _stream(dev)), entry)
+
+
 def elasticity_local(u_q, parts, host, ndim, P, wdet, lam, mu, rho=None,
                      lambda0=0.0):
   """Linear elasticity on a collocated grid (`sfem_elasticity_local`): `u_q`
   (E, P^d, d) -> K u + lambda0 M_rho u there, (E, P^d, d).  `wdet` (E, P^d);
   `lam`, `mu`, `rho`: a float or an (E, P^d) tensor each (`rho` None = 1)."""
   u_q = u_q.contiguous()
-  dev = _dev(u_q)
-  E, n, d = u_q.shape
-  if d != ndim or n != P ** ndim:
-    raise ValueError(f'expected (E, {P ** ndim}, {ndim}) local values, got '
-                     f'{tuple(u_q.shape)}')
-  if wdet is None:
-    raise ValueError('elasticity_local needs `wdet`')
+  _dev(u_q)
+  E, n, d = _local_shape(u_q, ndim, P, wdet, 'elasticity_local')
   tensors = []
   field = lambda t, name: _field(t, name, (E, n), u_q, 'displacement', tensors)
   args = _lib.ElasticityArgs(u=u_q.data_ptr(), lambda0=float(lambda0),
                              wdet=field(wdet, 'wdet').data_ptr())
-  for name, value in (('lam', lam), ('mu', mu),
-                      ('rho', 1.0 if rho is None else rho)):
-    if isinstance(value, torch.Tensor):
-      setattr(args, name, field(value, name).data_ptr())
-    else:
-      setattr(args, name + '_const', float(value))
+  _coefficients(args, field, _lame(lam, mu, rho))
   out = torch.empty_like(u_q)
-  host = {k: _host(v, u_q.dtype) for k, v in host.items()}
   args.out = out.data_ptr()
-  args.num_elements, args.ndim, args.P = E, ndim, P
-  args.dtype = _dtype_code(u_q)
-  with torch.cuda.device(dev):
-    for part in parts:
-      for name, value in _launch_fields(part, host, 'kfac').items():
-        setattr(args, name, value)
-      _lib.check(_lib.load().sfem_elasticity_local(ctypes.byref(args),
-                                                   _stream(dev)),
-                 'sfem_elasticity_local')
+  _launch_parts('sfem_elasticity_local', args, u_q, E, ndim, P, parts, host)
   return out
 
 
@@ -1377,12 +1401,7 @@ def hyperelastic_local(u_q, parts, host, ndim, P, wdet, lam, mu, rho=None,
   tangent = mode == 'tangent'
   u_q = u_q.contiguous()
   dev = _dev(u_q)
-  E, n, d = u_q.shape
-  if d != ndim or n != P ** ndim:
-    raise ValueError(f'expected (E, {P ** ndim}, {ndim}) local values, got '
-                     f'{tuple(u_q.shape)}')
-  if wdet is None:
-    raise ValueError('hyperelastic_local needs `wdet`')
+  E, n, d = _local_shape(u_q, ndim, P, wdet, 'hyperelastic_local')
   if tangent and (want_state or want_psi):
     raise ValueError('the state and psi are outputs of the residual mode')
   if tangent and state is None:
@@ -1402,24 +1421,10 @@ def hyperelastic_local(u_q, parts, host, ndim, P, wdet, lam, mu, rho=None,
       u=u_q.data_ptr(), lambda0=float(lambda0),
       wdet=field(wdet, 'wdet').data_ptr(), state=_dptr(state), psi=_dptr(psi),
       mode=_lib.SFEM_HYPER_TANGENT if tangent else _lib.SFEM_HYPER_RESIDUAL)
-  for name, value in (('lam', lam), ('mu', mu),
-                      ('rho', 1.0 if rho is None else rho)):
-    if isinstance(value, torch.Tensor):
-      setattr(args, name, field(value, name).data_ptr())
-    else:
-      setattr(args, name + '_const', float(value))
+  _coefficients(args, field, _lame(lam, mu, rho))
   out = torch.empty_like(u_q)
-  host = {k: _host(v, u_q.dtype) for k, v in host.items()}
   args.out = out.data_ptr()
-  args.num_elements, args.ndim, args.P = E, ndim, P
-  args.dtype = _dtype_code(u_q)
-  with torch.cuda.device(dev):
-    for part in parts:
-      for name, value in _launch_fields(part, host, 'kfac').items():
-        setattr(args, name, value)
-      _lib.check(_lib.load().sfem_hyperelastic_local(ctypes.byref(args),
-                                                     _stream(dev)),
-                 'sfem_hyperelastic_local')
+  _launch_parts('sfem_hyperelastic_local', args, u_q, E, ndim, P, parts, host)
   return out if tangent else (out, state, psi)
 
 
@@ -1449,12 +1454,7 @@ def plasticity_local(u_q, parts, host, ndim, P, wdet, lam, mu, rho, lambda0,
   tangent = mode == 'tangent'
   u_q = u_q.contiguous()
   dev = _dev(u_q)
-  E, n, d = u_q.shape
-  if d != ndim or n != P ** ndim:
-    raise ValueError(f'expected (E, {P ** ndim}, {ndim}) local values, got '
-                     f'{tuple(u_q.shape)}')
-  if wdet is None:
-    raise ValueError('plasticity_local needs `wdet`')
+  E, n, d = _local_shape(u_q, ndim, P, wdet, 'plasticity_local')
   NH, NL, NV = plasticity_sizes(ndim)
   if tangent and (want_hist or want_lin or want_stress or hist is not None):
     raise ValueError('the history, lin and the stress belong to the residual '
@@ -1479,27 +1479,12 @@ def plasticity_local(u_q, parts, host, ndim, P, wdet, lam, mu, rho, lambda0,
       wdet=field(wdet, 'wdet').data_ptr(), hist_in=_dptr(hist),
       hist_out=_dptr(hist_out), lin=_dptr(lin), stress=_dptr(stress),
       mode=_lib.SFEM_PLAST_TANGENT if tangent else _lib.SFEM_PLAST_RESIDUAL)
-  for name, const, value in (
-      ('lam', 'lam_const', lam), ('mu', 'mu_const', mu),
-      ('rho', 'rho_const', 1.0 if rho is None else rho),
+  _coefficients(args, field, _lame(lam, mu, rho) + (
       ('yield', 'yield_const', yield_stress),
-      ('hard', 'hard_const', hardening)):
-    if isinstance(value, torch.Tensor):
-      setattr(args, name, field(value, name).data_ptr())
-    else:
-      setattr(args, const, float(value))
+      ('hard', 'hard_const', hardening)))
   out = torch.empty_like(u_q)
-  host = {k: _host(v, u_q.dtype) for k, v in host.items()}
   args.out = out.data_ptr()
-  args.num_elements, args.ndim, args.P = E, ndim, P
-  args.dtype = _dtype_code(u_q)
-  with torch.cuda.device(dev):
-    for part in parts:
-      for name, value in _launch_fields(part, host, 'kfac').items():
-        setattr(args, name, value)
-      _lib.check(_lib.load().sfem_plasticity_local(ctypes.byref(args),
-                                                   _stream(dev)),
-                 'sfem_plasticity_local')
+  _launch_parts('sfem_plasticity_local', args, u_q, E, ndim, P, parts, host)
   return out if tangent else (out, hist_out, lin, stress)
 
 
@@ -1511,12 +1496,7 @@ def elasticity_sens(u_q, v_q, parts, host, ndim, P, wdet, lambda0=0.0,
   None where `want` is false."""
   u_q = u_q.contiguous()
   dev = _dev(u_q)
-  E, n, d = u_q.shape
-  if d != ndim or n != P ** ndim:
-    raise ValueError(f'expected (E, {P ** ndim}, {ndim}) local values, got '
-                     f'{tuple(u_q.shape)}')
-  if wdet is None:
-    raise ValueError('elasticity_sens needs `wdet`')
+  E, n, d = _local_shape(u_q, ndim, P, wdet, 'elasticity_sens')
   want = tuple(bool(w) for w in want)
   if len(want) != 3 or not any(want):
     raise ValueError('`want` names (dlam, dmu, drho), at least one of them')
@@ -1531,16 +1511,7 @@ def elasticity_sens(u_q, v_q, parts, host, ndim, P, wdet, lambda0=0.0,
       u=u_q.data_ptr(), v=v_q.data_ptr(), wdet=wdet.data_ptr(),
       dlam=_dptr(out[0]), dmu=_dptr(out[1]), drho=_dptr(out[2]),
       lambda0=float(lambda0))
-  host = {k: _host(v, u_q.dtype) for k, v in host.items()}
-  args.num_elements, args.ndim, args.P = E, ndim, P
-  args.dtype = _dtype_code(u_q)
-  with torch.cuda.device(dev):
-    for part in parts:
-      for name, value in _launch_fields(part, host, 'kfac').items():
-        setattr(args, name, value)
-      _lib.check(_lib.load().sfem_elasticity_sens(ctypes.byref(args),
-                                                  _stream(dev)),
-                 'sfem_elasticity_sens')
+  _launch_parts('sfem_elasticity_sens', args, u_q, E, ndim, P, parts, host)
   return out
 
 
@@ -1554,12 +1525,7 @@ def hyperelastic_sens(v_q, state, parts, host, ndim, P, wdet, u_q=None,
   `want` is false."""
   v_q = v_q.contiguous()
   dev = _dev(v_q)
-  E, n, d = v_q.shape
-  if d != ndim or n != P ** ndim:
-    raise ValueError(f'expected (E, {P ** ndim}, {ndim}) local values, got '
-                     f'{tuple(v_q.shape)}')
-  if wdet is None:
-    raise ValueError('hyperelastic_sens needs `wdet`')
+  E, n, d = _local_shape(v_q, ndim, P, wdet, 'hyperelastic_sens')
   want = tuple(bool(w) for w in want)
   if len(want) != 3 or not any(want):
     raise ValueError('`want` names (dlam, dmu, drho), at least one of them')
@@ -1579,26 +1545,8 @@ def hyperelastic_sens(v_q, state, parts, host, ndim, P, wdet, u_q=None,
       v=v_q.data_ptr(), state=state.data_ptr(), u=_dptr(u_q),
       wdet=wdet.data_ptr(), dlam=_dptr(out[0]), dmu=_dptr(out[1]),
       drho=_dptr(out[2]), lambda0=float(lambda0))
-  host = {k: _host(v, v_q.dtype) for k, v in host.items()}
-  args.num_elements, args.ndim, args.P = E, ndim, P
-  args.dtype = _dtype_code(v_q)
-  with torch.cuda.device(dev):
-    for part in parts:
-      for name, value in _launch_fields(part, host, 'kfac').items():
-        setattr(args, name, value)
-      _lib.check(_lib.load().sfem_hyperelastic_sens(ctypes.byref(args),
-                                                    _stream(dev)),
-                 'sfem_hyperelastic_sens')
+  _launch_parts('sfem_hyperelastic_sens', args, v_q, E, ndim, P, parts, host)
   return out
-
-
-def _lame_fields(args, field, lam, mu):
-  """`lam` and `mu` of a stress launch: a float or an (E, P^d) tensor each."""
-  for name, value in (('lam', lam), ('mu', mu)):
-    if isinstance(value, torch.Tensor):
-      setattr(args, name, field(value, name).data_ptr())
-    else:
-      setattr(args, name + '_const', float(value))
 
 
 def elasticity_stress(u_q, parts, host, ndim, P, wdet, lam, mu,
@@ -1612,12 +1560,7 @@ def elasticity_stress(u_q, parts, host, ndim, P, wdet, lam, mu,
   Rows of elements that no part lists and points with wdet = 0 are zero."""
   u_q = u_q.contiguous()
   dev = _dev(u_q)
-  E, n, d = u_q.shape
-  if d != ndim or n != P ** ndim:
-    raise ValueError(f'expected (E, {P ** ndim}, {ndim}) local values, got '
-                     f'{tuple(u_q.shape)}')
-  if wdet is None:
-    raise ValueError('elasticity_stress needs `wdet`')
+  E, n, d = _local_shape(u_q, ndim, P, wdet, 'elasticity_stress')
   want = tuple(bool(w) for w in want)
   if len(want) != 2 or not any(want):
     raise ValueError('`want` names (sigma, von Mises), at least one of them')
@@ -1630,17 +1573,8 @@ def elasticity_stress(u_q, parts, host, ndim, P, wdet, lam, mu,
   args = _lib.ElasticityStressArgs(
       u=u_q.data_ptr(), sigma=_dptr(sigma), vm=_dptr(vm),
       wdet=field(wdet, 'wdet').data_ptr(), plane_stress=int(bool(plane_stress)))
-  _lame_fields(args, field, lam, mu)
-  host = {k: _host(v, u_q.dtype) for k, v in host.items()}
-  args.num_elements, args.ndim, args.P = E, ndim, P
-  args.dtype = _dtype_code(u_q)
-  with torch.cuda.device(dev):
-    for part in parts:
-      for name, value in _launch_fields(part, host, 'kfac').items():
-        setattr(args, name, value)
-      _lib.check(_lib.load().sfem_elasticity_stress(ctypes.byref(args),
-                                                    _stream(dev)),
-                 'sfem_elasticity_stress')
+  _coefficients(args, field, _lame(lam, mu)[:2])
+  _launch_parts('sfem_elasticity_stress', args, u_q, E, ndim, P, parts, host)
   return sigma, vm
 
 
@@ -1675,17 +1609,9 @@ def elasticity_stress_vjp(s_bar, u_q, parts, host, ndim, P, wdet, lam, mu,
       sbar=s_bar.data_ptr(), u=_dptr(u_q), ubar=_dptr(out[0]),
       dlam=_dptr(out[1]), dmu=_dptr(out[2]),
       wdet=field(wdet, 'wdet').data_ptr(), plane_stress=int(bool(plane_stress)))
-  _lame_fields(args, field, lam, mu)
-  host = {k: _host(v, s_bar.dtype) for k, v in host.items()}
-  args.num_elements, args.ndim, args.P = E, ndim, P
-  args.dtype = _dtype_code(s_bar)
-  with torch.cuda.device(dev):
-    for part in parts:
-      for name, value in _launch_fields(part, host, 'kfac').items():
-        setattr(args, name, value)
-      _lib.check(_lib.load().sfem_elasticity_stress_vjp(ctypes.byref(args),
-                                                        _stream(dev)),
-                 'sfem_elasticity_stress_vjp')
+  _coefficients(args, field, _lame(lam, mu)[:2])
+  _launch_parts('sfem_elasticity_stress_vjp', args, s_bar, E, ndim, P, parts,
+                host)
   return out
 
 

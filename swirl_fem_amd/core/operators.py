@@ -2275,8 +2275,64 @@ def von_mises(sigma, ndim):
 _von_mises = von_mises   # `ElasticityOperator.stress` has a flag of that name
 
 
+def _elastic_coefficient(fespace, value, name, positive):
+  """A coefficient of the elasticity family as its kernels read it: a float,
+  or an (E, Q^d) tensor (per-element values are expanded here: the kernels
+  read per-point arrays only)."""
+  if value is None:
+    raise ValueError(f'{name} is required')
+  mesh = fespace.mesh
+  E = mesh.num_elements
+  npts = fespace.quadrature.num_points ** mesh.ndim
+  points = lambda: fespace._interpolate(mesh.element_coords())
+  c = coefficient(value, name, E, npts, points, fespace.dtype, fespace.device,
+                  positive)
+  if isinstance(c, tuple):
+    mode, t = c
+    from swirl_fem_amd import _lib
+    if mode == _lib.COEF_ELEM:
+      t = t[:, None].expand(E, npts)
+    return t.contiguous()
+  return c
+
+
+class _DisplacementOperator:
+  """Intake and assembly of nodal displacements (N, d) for an operator with a
+  `fespace` and a `mask`; the refusals carry the subclass's name."""
+
+  def _to_grid(self, u_local):
+    """(E, n, d) element values -> (E, Q^d, d) on the quadrature grid."""
+    fes = self.fespace
+    if autodiff.needs_grad(u_local):
+      raise NotImplementedError(f'autograd through {type(self).__name__}')
+    d = fes.mesh.ndim
+    if u_local.dim() != 3 or u_local.shape[-1] != d:
+      raise ValueError(f'expected (E, n, {d}) local values, got '
+                       f'{tuple(u_local.shape)}')
+    return fes._interpolate(u_local.to(fes.dtype)).contiguous()
+
+  def _nodal(self, u):
+    mesh = self.fespace.mesh
+    if tuple(u.shape) != (mesh.num_nodes, mesh.ndim):
+      raise ValueError(f'expected ({mesh.num_nodes}, {mesh.ndim}) nodal '
+                       f'displacements, got {tuple(u.shape)}')
+    if autodiff.needs_grad(u):
+      raise NotImplementedError(f'autograd through {type(self).__name__}')
+    return _ops.gather_rows(u.to(self.fespace.dtype).contiguous(),
+                            mesh.elements)
+
+  def _assembled(self, u, local):
+    """mask * scatter(local(gather(u))) in the layout of `u`."""
+    mesh = self.fespace.mesh
+    loc = local(self._nodal(u))
+    out = _ops.scatter_add(loc, mesh.elements, mesh.num_nodes, ncomp=mesh.ndim)
+    if self.mask is not None:
+      out = out * self.mask
+    return _like_layout(out, u) if u.dtype == out.dtype else out
+
+
 @dataclasses.dataclass(eq=False)
-class ElasticityOperator:
+class ElasticityOperator(_DisplacementOperator):
   """`K u + lambda0 M_rho u` for displacements u (N, d), with `v^T K u = int
   sigma(u) : grad v`, sigma = lambda tr(eps) I + 2 mu eps (plane strain in
   2D) and M_rho the mass matrix with density rho.  Interpolate
@@ -2321,25 +2377,13 @@ class ElasticityOperator:
       raise NotImplementedError(f'{what} unavailable: {why}')
     if geometry not in ('auto', 'stored'):
       raise ValueError(f'unknown geometry mode {geometry!r}')
-    E, d = mesh.num_elements, mesh.ndim
-    npts = fespace.quadrature.num_points ** d
-    points = lambda: fespace._interpolate(mesh.element_coords())
-
-    def intake(value, name, positive):
-      c = coefficient(value, name, E, npts, points, fespace.dtype,
-                      fespace.device, positive)
-      if isinstance(c, tuple):      # per-element values are expanded here: the
-        mode, t = c                 # kernel reads per-point arrays only
-        from swirl_fem_amd import _lib
-        if mode == _lib.COEF_ELEM:
-          t = t[:, None].expand(E, npts)
-        return t.contiguous()
-      return c
+    d = mesh.ndim
     if lame_lambda is None or lame_mu is None:
       raise ValueError('lame_lambda and lame_mu are required')
-    lam = intake(lame_lambda, 'lame_lambda', False)
-    mu = intake(lame_mu, 'lame_mu', True)
-    rho = intake(1.0 if density is None else density, 'density', False)
+    lam = _elastic_coefficient(fespace, lame_lambda, 'lame_lambda', False)
+    mu = _elastic_coefficient(fespace, lame_mu, 'lame_mu', True)
+    rho = _elastic_coefficient(fespace, 1.0 if density is None else density,
+                               'density', False)
     mask = None
     if dirichlet_mask is not None:
       m = torch.as_tensor(dirichlet_mask, device=fespace.device)
@@ -2363,14 +2407,8 @@ class ElasticityOperator:
   def apply_local(self, u_local, lambda0=0.0):
     """(E, n, d) element displacements -> (E, n, d) local covector."""
     fes = self.fespace
-    if autodiff.needs_grad(u_local):
-      raise NotImplementedError('autograd through ElasticityOperator')
-    d = fes.mesh.ndim
-    if u_local.dim() != 3 or u_local.shape[-1] != d:
-      raise ValueError(f'expected (E, n, {d}) local values, got '
-                       f'{tuple(u_local.shape)}')
-    uq = fes._interpolate(u_local.to(fes.dtype)).contiguous()
-    rq = _ops.elasticity_local(uq, self.parts, self.host, d,
+    uq = self._to_grid(u_local)
+    rq = _ops.elasticity_local(uq, self.parts, self.host, fes.mesh.ndim,
                                fes.quadrature.num_points,
                                self.point_weights(), self.lam, self.mu,
                                self.rho, lambda0)
@@ -2379,18 +2417,7 @@ class ElasticityOperator:
   def apply(self, u, lambda0=0.0):
     """u (N, d), dense or component-major -> mask * scatter(local(gather(u)))
     in the layout of `u`."""
-    mesh = self.fespace.mesh
-    if tuple(u.shape) != (mesh.num_nodes, mesh.ndim):
-      raise ValueError(f'expected ({mesh.num_nodes}, {mesh.ndim}) nodal '
-                       f'displacements, got {tuple(u.shape)}')
-    if autodiff.needs_grad(u):
-      raise NotImplementedError('autograd through ElasticityOperator')
-    v = u.to(self.fespace.dtype).contiguous()
-    loc = self.apply_local(_ops.gather_rows(v, mesh.elements), lambda0)
-    out = _ops.scatter_add(loc, mesh.elements, mesh.num_nodes, ncomp=mesh.ndim)
-    if self.mask is not None:
-      out = out * self.mask
-    return _like_layout(out, u) if u.dtype == out.dtype else out
+    return self._assembled(u, lambda v: self.apply_local(v, lambda0))
 
   def linear_operator(self, lambda0=0.0):
     return lambda u: self.apply(u, lambda0)
@@ -2609,22 +2636,39 @@ class HyperelasticLinearization:
   lambda0: float
 
 
-class HyperelasticTangent:
-  """`T(u) w` at a linearisation: `apply(w)` (N, d) in any layout, returned
-  in the layout given; `linear_operator()` the callable CG takes."""
+class _OnLinearElasticity(_DisplacementOperator):
+  """An operator built on a linear `ElasticityOperator`, its field `linear`:
+  geometry, coefficients, mask and point weights are that operator's."""
+  fespace = property(lambda self: self.linear.fespace)
+  parts = property(lambda self: self.linear.parts)
+  host = property(lambda self: self.linear.host)
+  lam = property(lambda self: self.linear.lam)
+  mu = property(lambda self: self.linear.mu)
+  rho = property(lambda self: self.linear.rho)
+  mask = property(lambda self: self.linear.mask)
 
-  def __init__(self, op, state, lambda0):
-    self.op, self.state, self.lambda0 = op, state, float(lambda0)
+  def point_weights(self):
+    """W = w detJ (E, Q^d)."""
+    return self.linear.point_weights()
+
+  def _grid_args(self, lambda0):
+    """What a launch on the quadrature grid takes after the values there."""
+    fes = self.fespace
+    return (self.parts, self.host, fes.mesh.ndim, fes.quadrature.num_points,
+            self.point_weights(), self.lam, self.mu, self.rho, lambda0)
+
+
+class _Tangent:
+  """`T w` at a linearisation: `apply(w)` (N, d) in any layout, returned in
+  the layout given; `linear_operator()` the callable CG takes.  `launch(wq)`
+  is the tangent-mode launch on the quadrature grid."""
+
+  def __init__(self, op, lambda0, launch):
+    self.op, self.lambda0, self._launch = op, float(lambda0), launch
 
   def apply_local(self, w_local):
-    op = self.op
-    fes = op.fespace
-    wq = op._to_grid(w_local)
-    tq = _ops.hyperelastic_local(
-        wq, op.parts, op.host, fes.mesh.ndim, fes.quadrature.num_points,
-        op.point_weights(), op.lam, op.mu, op.rho, self.lambda0,
-        mode='tangent', state=self.state)
-    return fes._interpolate_t(tq)
+    return self.op.fespace._interpolate_t(
+        self._launch(self.op._to_grid(w_local)))
 
   def apply(self, w):
     return self.op._assembled(w, self.apply_local)
@@ -2633,8 +2677,17 @@ class HyperelasticTangent:
     return self.apply
 
 
+class HyperelasticTangent(_Tangent):
+  """`T(u) w` at the linearisation `state`."""
+
+  def __init__(self, op, state, lambda0):
+    super().__init__(op, lambda0, lambda wq: _ops.hyperelastic_local(
+        wq, *op._grid_args(self.lambda0), mode='tangent', state=state))
+    self.state = state
+
+
 @dataclasses.dataclass(eq=False)
-class HyperelasticOperator:
+class HyperelasticOperator(_OnLinearElasticity):
   """The internal force of a compressible neo-Hookean solid in the total-
   Lagrangian formulation, for displacements u (N, d):
 
@@ -2659,55 +2712,10 @@ class HyperelasticOperator:
         fespace, dirichlet_mask, lame_lambda, lame_mu, density, geometry,
         'HyperelasticOperator', 'fused hyperelasticity'))
 
-  fespace = property(lambda self: self.linear.fespace)
-  parts = property(lambda self: self.linear.parts)
-  host = property(lambda self: self.linear.host)
-  lam = property(lambda self: self.linear.lam)
-  mu = property(lambda self: self.linear.mu)
-  rho = property(lambda self: self.linear.rho)
-  mask = property(lambda self: self.linear.mask)
-
-  def point_weights(self):
-    """W = w detJ (E, Q^d)."""
-    return self.linear.point_weights()
-
-  def _to_grid(self, u_local):
-    """(E, n, d) element values -> (E, Q^d, d) on the quadrature grid."""
-    fes = self.fespace
-    if autodiff.needs_grad(u_local):
-      raise NotImplementedError('autograd through HyperelasticOperator')
-    d = fes.mesh.ndim
-    if u_local.dim() != 3 or u_local.shape[-1] != d:
-      raise ValueError(f'expected (E, n, {d}) local values, got '
-                       f'{tuple(u_local.shape)}')
-    return fes._interpolate(u_local.to(fes.dtype)).contiguous()
-
-  def _nodal(self, u):
-    mesh = self.fespace.mesh
-    if tuple(u.shape) != (mesh.num_nodes, mesh.ndim):
-      raise ValueError(f'expected ({mesh.num_nodes}, {mesh.ndim}) nodal '
-                       f'displacements, got {tuple(u.shape)}')
-    if autodiff.needs_grad(u):
-      raise NotImplementedError('autograd through HyperelasticOperator')
-    return _ops.gather_rows(u.to(self.fespace.dtype).contiguous(),
-                            mesh.elements)
-
-  def _assembled(self, u, local):
-    """mask * scatter(local(gather(u))) in the layout of `u`."""
-    mesh = self.fespace.mesh
-    loc = local(self._nodal(u))
-    out = _ops.scatter_add(loc, mesh.elements, mesh.num_nodes, ncomp=mesh.ndim)
-    if self.mask is not None:
-      out = out * self.mask
-    return _like_layout(out, u) if u.dtype == out.dtype else out
-
   def _launch(self, u_local, lambda0, want_state=False, want_psi=False):
-    fes = self.fespace
     return _ops.hyperelastic_local(
-        self._to_grid(u_local), self.parts, self.host, fes.mesh.ndim,
-        fes.quadrature.num_points, self.point_weights(), self.lam, self.mu,
-        self.rho, lambda0, mode='residual', want_state=want_state,
-        want_psi=want_psi)
+        self._to_grid(u_local), *self._grid_args(lambda0), mode='residual',
+        want_state=want_state, want_psi=want_psi)
 
   def residual_local(self, u_local, lambda0=0.0):
     """(E, n, d) element displacements -> (E, n, d) local internal force."""
@@ -2808,32 +2816,18 @@ class PlasticityLinearization:
     return int((self.lin[..., 2:] != 0).any(dim=-1).sum())
 
 
-class PlasticityTangent:
-  """`T w` at a linearisation: `apply(w)` (N, d) in any layout, returned in
-  the layout given; `linear_operator()` the callable CG takes."""
+class PlasticityTangent(_Tangent):
+  """The algorithmic tangent at the linearisation `lin`."""
 
   def __init__(self, op, lin, lambda0):
-    self.op, self.lin, self.lambda0 = op, lin, float(lambda0)
-
-  def apply_local(self, w_local):
-    op = self.op
-    fes = op.fespace
-    wq = op._to_grid(w_local)
-    tq = _ops.plasticity_local(
-        wq, op.parts, op.host, fes.mesh.ndim, fes.quadrature.num_points,
-        op.point_weights(), op.lam, op.mu, op.rho, self.lambda0,
-        op.yield_stress, op.hardening, mode='tangent', lin=self.lin)
-    return fes._interpolate_t(tq)
-
-  def apply(self, w):
-    return self.op._assembled(w, self.apply_local)
-
-  def linear_operator(self):
-    return self.apply
+    super().__init__(op, lambda0, lambda wq: _ops.plasticity_local(
+        wq, *op._grid_args(self.lambda0), op.yield_stress, op.hardening,
+        mode='tangent', lin=lin))
+    self.lin = lin
 
 
 @dataclasses.dataclass(eq=False)
-class PlasticityOperator:
+class PlasticityOperator(_OnLinearElasticity):
   """The internal force of a small-strain von Mises (J2) elastoplastic solid
   with linear isotropic hardening, for displacements u (N, d)
   and a committed history (E, Q^d, NH) at the quadrature points:
@@ -2861,38 +2855,11 @@ class PlasticityOperator:
     linear = ElasticityOperator._intake(
         fespace, dirichlet_mask, lame_lambda, lame_mu, density, geometry,
         'PlasticityOperator', 'fused plasticity')
-    mesh = fespace.mesh
-    E = mesh.num_elements
-    npts = fespace.quadrature.num_points ** mesh.ndim
-    points = lambda: fespace._interpolate(mesh.element_coords())
-
-    def intake(value, name, positive):
-      if value is None:
-        raise ValueError(f'{name} is required')
-      c = coefficient(value, name, E, npts, points, fespace.dtype,
-                      fespace.device, positive)
-      if isinstance(c, tuple):
-        from swirl_fem_amd import _lib
-        mode, t = c
-        if mode == _lib.COEF_ELEM:
-          t = t[:, None].expand(E, npts)
-        return t.contiguous()
-      return c
     return cls(linear=linear,
-               yield_stress=intake(yield_stress, 'yield_stress', True),
-               hardening=intake(hardening_modulus, 'hardening_modulus', False))
-
-  fespace = property(lambda self: self.linear.fespace)
-  parts = property(lambda self: self.linear.parts)
-  host = property(lambda self: self.linear.host)
-  lam = property(lambda self: self.linear.lam)
-  mu = property(lambda self: self.linear.mu)
-  rho = property(lambda self: self.linear.rho)
-  mask = property(lambda self: self.linear.mask)
-
-  def point_weights(self):
-    """W = w detJ (E, Q^d)."""
-    return self.linear.point_weights()
+               yield_stress=_elastic_coefficient(fespace, yield_stress,
+                                                 'yield_stress', True),
+               hardening=_elastic_coefficient(fespace, hardening_modulus,
+                                              'hardening_modulus', False))
 
   def history_shape(self):
     mesh = self.fespace.mesh
@@ -2914,43 +2881,10 @@ class PlasticityOperator:
                        f'{tuple(history.shape)}')
     return history.to(self.fespace.dtype).contiguous()
 
-  def _to_grid(self, u_local):
-    """(E, n, d) element values -> (E, Q^d, d) on the quadrature grid."""
-    fes = self.fespace
-    if autodiff.needs_grad(u_local):
-      raise NotImplementedError('autograd through PlasticityOperator')
-    d = fes.mesh.ndim
-    if u_local.dim() != 3 or u_local.shape[-1] != d:
-      raise ValueError(f'expected (E, n, {d}) local values, got '
-                       f'{tuple(u_local.shape)}')
-    return fes._interpolate(u_local.to(fes.dtype)).contiguous()
-
-  def _nodal(self, u):
-    mesh = self.fespace.mesh
-    if tuple(u.shape) != (mesh.num_nodes, mesh.ndim):
-      raise ValueError(f'expected ({mesh.num_nodes}, {mesh.ndim}) nodal '
-                       f'displacements, got {tuple(u.shape)}')
-    if autodiff.needs_grad(u):
-      raise NotImplementedError('autograd through PlasticityOperator')
-    return _ops.gather_rows(u.to(self.fespace.dtype).contiguous(),
-                            mesh.elements)
-
-  def _assembled(self, u, local):
-    """mask * scatter(local(gather(u))) in the layout of `u`."""
-    mesh = self.fespace.mesh
-    loc = local(self._nodal(u))
-    out = _ops.scatter_add(loc, mesh.elements, mesh.num_nodes, ncomp=mesh.ndim)
-    if self.mask is not None:
-      out = out * self.mask
-    return _like_layout(out, u) if u.dtype == out.dtype else out
-
   def _launch(self, u_local, history, lambda0, **want):
-    fes = self.fespace
     return _ops.plasticity_local(
-        self._to_grid(u_local), self.parts, self.host, fes.mesh.ndim,
-        fes.quadrature.num_points, self.point_weights(), self.lam, self.mu,
-        self.rho, lambda0, self.yield_stress, self.hardening, mode='residual',
-        hist=self._history(history), **want)
+        self._to_grid(u_local), *self._grid_args(lambda0), self.yield_stress,
+        self.hardening, mode='residual', hist=self._history(history), **want)
 
   def residual_local(self, u_local, history=None, lambda0=0.0):
     """(E, n, d) element displacements -> (E, n, d) local internal force."""

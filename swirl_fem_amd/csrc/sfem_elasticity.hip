@@ -6,20 +6,6 @@
 
 using namespace sfem;
 
-// The geometry and launch fields shared by the two stress entry points.
-template <typename T, typename Args>
-static void stress_geometry(const Args* a, int64_t work, StokesParams<T>* g) {
-  g->kfac = (const T*)a->kfac;
-  g->geo_elem = (const T*)a->geo_elem;
-  g->geo_index = a->geo_index;
-  g->elem_list = a->elem_list;
-  g->dmat_host = (const T*)a->dmat;
-  g->weights_host = (const T*)a->weights;
-  g->nodes_host = (const T*)a->nodes;
-  g->num_elements = work;
-  g->geo_mode = a->geo_mode;
-}
-
 extern "C" {
 
 int sfem_elasticity_local(const sfem_elasticity_args* a, sfem_stream_t stream) {
@@ -43,25 +29,7 @@ int sfem_elasticity_local(const sfem_elasticity_args* a, sfem_stream_t stream) {
   return with_real(a->dtype, [&](auto zero) {
     using T = decltype(zero);
     ElasticityParams<T> ep{};
-    ep.geo.kfac = (const T*)a->kfac;
-    ep.geo.geo_elem = (const T*)a->geo_elem;
-    ep.geo.geo_index = a->geo_index;
-    ep.geo.elem_list = a->elem_list;
-    ep.geo.dmat_host = (const T*)a->dmat;
-    ep.geo.weights_host = (const T*)a->weights;
-    ep.geo.nodes_host = (const T*)a->nodes;
-    ep.geo.num_elements = work;
-    ep.geo.geo_mode = a->geo_mode;
-    ep.u = (const T*)a->u;
-    ep.out = (T*)a->out;
-    ep.wdet = (const T*)a->wdet;
-    ep.lam = (const T*)a->lam;
-    ep.mu = (const T*)a->mu;
-    ep.rho = (const T*)a->rho;
-    ep.lam_const = (T)a->lam_const;
-    ep.mu_const = (T)a->mu_const;
-    ep.rho_const = (T)a->rho_const;
-    ep.lambda0 = (T)a->lambda0;
+    fill_elasticity<T>(a, work, &ep);
     return with_dim(a->ndim, [&](auto d) {
       return dispatch_elasticity<T, decltype(d)::value>(ep, a->P,
                                                         as_stream(stream));
@@ -92,15 +60,7 @@ int sfem_elasticity_sens(const sfem_elasticity_sens_args* a,
   return with_real(a->dtype, [&](auto zero) {
     using T = decltype(zero);
     ElasticitySensParams<T> sp{};
-    sp.geo.kfac = (const T*)a->kfac;
-    sp.geo.geo_elem = (const T*)a->geo_elem;
-    sp.geo.geo_index = a->geo_index;
-    sp.geo.elem_list = a->elem_list;
-    sp.geo.dmat_host = (const T*)a->dmat;
-    sp.geo.weights_host = (const T*)a->weights;
-    sp.geo.nodes_host = (const T*)a->nodes;
-    sp.geo.num_elements = work;
-    sp.geo.geo_mode = a->geo_mode;
+    fill_geometry<T>(a, work, &sp.geo);
     sp.u = (const T*)a->u;
     sp.v = (const T*)a->v;
     sp.wdet = (const T*)a->wdet;
@@ -138,7 +98,7 @@ int sfem_elasticity_stress(const sfem_elasticity_stress_args* a,
   return with_real(a->dtype, [&](auto zero) {
     using T = decltype(zero);
     ElasticityStressParams<T> sp{};
-    stress_geometry<T>(a, work, &sp.geo);
+    fill_geometry<T>(a, work, &sp.geo);
     sp.u = (const T*)a->u;
     sp.wdet = (const T*)a->wdet;
     sp.lam = (const T*)a->lam;
@@ -180,7 +140,7 @@ int sfem_elasticity_stress_vjp(const sfem_elasticity_stress_vjp_args* a,
   return with_real(a->dtype, [&](auto zero) {
     using T = decltype(zero);
     ElasticityStressVjpParams<T> sp{};
-    stress_geometry<T>(a, work, &sp.geo);
+    fill_geometry<T>(a, work, &sp.geo);
     sp.sbar = (const T*)a->sbar;
     sp.u = (const T*)a->u;
     sp.wdet = (const T*)a->wdet;

@@ -38,7 +38,7 @@
 // barriers stay outside the `active` / `lane_ok` branches (the `want_*` tests
 // are kernel arguments, uniform over the grid).
 #pragma once
-#include "sfem_stokes.h"
+#include "sfem_elasticity.h"
 
 namespace sfem {
 
@@ -98,40 +98,6 @@ struct ElasticityStressVjpBudget {
                       : (LIVE_REGS > 60 ? 2 : HelmholtzTile<T, P, DIM>::MINW);
 };
 
-// Row c of the physical gradient at the lane's point of slice a, from the
-// axis-0 derivative G0 and the LDS pair.  Expects geom, dm, wd, s0, s1, i, j,
-// t, SA, SB, TPE in scope; H is T[DIM].  W = 0 gives a zero row.
-#define SFEM_STRESS_GRADIENT_ROW(A, G0, H)                                    \
-  do {                                                                        \
-    const int o_ = (A) * SA + i * SB + j;                                     \
-    T K_[DIM * DIM];                                                          \
-    geom.cof(dm, (A), K_);                                                    \
-    const T wq_ = wd[t + (A) * TPE];                                          \
-    const T iw_ = wq_ != T(0) ? T(1) / wq_ : T(0);                            \
-    T g_[DIM];                                                                \
-    g_[0] = (G0);                                                             \
-    g_[1] = s0[o_];                                                           \
-    if constexpr (DIM == 3) g_[2] = s1[o_];                                   \
-    _Pragma("unroll") for (int jj_ = 0; jj_ < DIM; ++jj_) {                   \
-      T s_ = T(0);                                                            \
-      _Pragma("unroll") for (int ax_ = 0; ax_ < DIM; ++ax_)                   \
-          s_ += K_[ax_ * DIM + jj_] * g_[ax_];                                \
-      (H)[jj_] = iw_ * s_;                                                    \
-    }                                                                         \
-  } while (0)
-
-// Derivative stage of one component: X[a] = the lane's values (a, i, j) in,
-// DX0[a] = the axis-0 derivative out; the axis-1 / axis-2 derivatives at
-// (a, i, j) are left in s0 / s1.  Barriers included, so not under a branch.
-#define SFEM_STRESS_DERIVATIVES(X, DX0)                                       \
-  do {                                                                        \
-    line_apply<T, P, false>(dm, X, DX0);                                      \
-    SFEM_PAIR_SPREAD(X);                                                      \
-    __syncthreads();                                                          \
-    SFEM_PAIR_LINES_DM(false);                                                \
-    __syncthreads();                                                          \
-  } while (0)
-
 template <typename T, int P, int DIM, int GM>
 __global__ void __launch_bounds__((HelmholtzTile<T, P, DIM>::BLOCK),
                                   (ElasticityStressBudget<T, P, DIM>::MINW))
@@ -158,12 +124,12 @@ elasticity_stress_kernel(ElasticityStressParams<T> sp, DMat<T, P> dm) {
 #pragma unroll
     for (int a = 0; a < P; ++a)
       xa[a] = active ? ue[(int64_t)(t + a * TPE) * DIM + c] : T(0);
-    SFEM_STRESS_DERIVATIVES(xa, g0);
+    SFEM_ELAST_DERIVATIVES(xa, g0);
     if (active) {
 #pragma unroll
       for (int a = 0; a < P; ++a) {
         T h[DIM];
-        SFEM_STRESS_GRADIENT_ROW(a, g0[a], h);
+        SFEM_ELAST_GRADIENT_ROW(a, g0[a], h);
 #pragma unroll
         for (int jj = 0; jj < DIM; ++jj) {
           if (jj == c)
@@ -265,12 +231,12 @@ elasticity_stress_vjp_kernel(ElasticityStressVjpParams<T> sp, DMat<T, P> dm) {
 #pragma unroll
       for (int a = 0; a < P; ++a)
         xa[a] = active ? ue[(int64_t)(t + a * TPE) * DIM + c] : T(0);
-      SFEM_STRESS_DERIVATIVES(xa, g0);
+      SFEM_ELAST_DERIVATIVES(xa, g0);
       if (active) {
 #pragma unroll
         for (int a = 0; a < P; ++a) {
           T h[DIM];
-          SFEM_STRESS_GRADIENT_ROW(a, g0[a], h);
+          SFEM_ELAST_GRADIENT_ROW(a, g0[a], h);
           tru[a] += h[c];
           if (want_m) {
             const int q = t + a * TPE;
@@ -326,19 +292,8 @@ elasticity_stress_vjp_kernel(ElasticityStressVjpParams<T> sp, DMat<T, P> dm) {
           }
         }
       }
-      if (lane_ok) {
-#pragma unroll
-        for (int a = 0; a < P; ++a) {
-          const int o = a * SA + i * SB + j;
-          s0[o] = g[1][a];
-          if constexpr (DIM == 3) s1[o] = g[2][a];
-        }
-      }
-      __syncthreads();
-      SFEM_PAIR_LINES_DM(true);   // the transposed derivatives, in place
       T dt0[P];
-      line_apply<T, P, true>(dm, g[0], dt0);
-      __syncthreads();
+      SFEM_ELAST_DERIVATIVES_T(g, dt0);
       if (active) {
 #pragma unroll
         for (int a = 0; a < P; ++a) {

@@ -35,26 +35,7 @@ int sfem_hyperelastic_local(const sfem_hyperelastic_args* a,
   return with_real(a->dtype, [&](auto zero) {
     using T = decltype(zero);
     HyperelasticParams<T> hp{};
-    ElasticityParams<T>& ep = hp.el;
-    ep.geo.kfac = (const T*)a->kfac;
-    ep.geo.geo_elem = (const T*)a->geo_elem;
-    ep.geo.geo_index = a->geo_index;
-    ep.geo.elem_list = a->elem_list;
-    ep.geo.dmat_host = (const T*)a->dmat;
-    ep.geo.weights_host = (const T*)a->weights;
-    ep.geo.nodes_host = (const T*)a->nodes;
-    ep.geo.num_elements = work;
-    ep.geo.geo_mode = a->geo_mode;
-    ep.u = (const T*)a->u;
-    ep.out = (T*)a->out;
-    ep.wdet = (const T*)a->wdet;
-    ep.lam = (const T*)a->lam;
-    ep.mu = (const T*)a->mu;
-    ep.rho = (const T*)a->rho;
-    ep.lam_const = (T)a->lam_const;
-    ep.mu_const = (T)a->mu_const;
-    ep.rho_const = (T)a->rho_const;
-    ep.lambda0 = (T)a->lambda0;
+    fill_elasticity<T>(a, work, &hp.el);
     hp.state = (T*)a->state;
     hp.psi = (T*)a->psi;
     return with_dim(a->ndim, [&](auto d) {

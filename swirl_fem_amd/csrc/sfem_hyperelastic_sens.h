@@ -93,35 +93,14 @@ hyperelastic_sens_kernel(HyperelasticSensParams<T> sp, DMat<T, P> dm) {
     ElemCof<T, P, DIM, GM> geom;
     geom.init(prm, dm, e, active, i, j, t);
 
-    // derivative stage of one component: x[a] = the lane's values (a, i, j)
-    // in, dx0[a] = the axis-0 derivative out; the axis-1 / axis-2
-    // derivatives at (a, i, j) are left in s0 / s1
+    // The shared stages, as lambdas: this kernel was written with lambdas, and
+    // its register allocation follows their inlining (the macros alone move
+    // registers in every instantiation).
     auto derivatives = [&](const T (&x)[P], T (&dx0)[P]) {
-      line_apply<T, P, false>(dm, x, dx0);
-      SFEM_PAIR_SPREAD(x);
-      __syncthreads();
-      SFEM_PAIR_LINES_DM(false);
-      __syncthreads();
+      SFEM_ELAST_DERIVATIVES(x, dx0);
     };
-
-    // row c of the physical gradient at the lane's point of slice a
     auto gradient_row = [&](int a, T g0, T (&h)[DIM]) {
-      const int o = a * SA + i * SB + j;
-      T K[DIM * DIM];
-      geom.cof(dm, a, K);
-      const T wq = wd[t + a * TPE];
-      const T iw = wq != T(0) ? T(1) / wq : T(0);
-      T g[DIM];
-      g[0] = g0;
-      g[1] = s0[o];
-      if constexpr (DIM == 3) g[2] = s1[o];
-#pragma unroll
-      for (int jj = 0; jj < DIM; ++jj) {
-        T s = T(0);
-#pragma unroll
-        for (int ax = 0; ax < DIM; ++ax) s += K[ax * DIM + jj] * g[ax];
-        h[jj] = iw * s;
-      }
+      SFEM_ELAST_GRADIENT_ROW(a, g0, h);
     };
 
 #pragma unroll

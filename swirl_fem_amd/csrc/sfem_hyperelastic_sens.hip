@@ -30,15 +30,7 @@ int sfem_hyperelastic_sens(const sfem_hyperelastic_sens_args* a,
   return with_real(a->dtype, [&](auto zero) {
     using T = decltype(zero);
     HyperelasticSensParams<T> sp{};
-    sp.geo.kfac = (const T*)a->kfac;
-    sp.geo.geo_elem = (const T*)a->geo_elem;
-    sp.geo.geo_index = a->geo_index;
-    sp.geo.elem_list = a->elem_list;
-    sp.geo.dmat_host = (const T*)a->dmat;
-    sp.geo.weights_host = (const T*)a->weights;
-    sp.geo.nodes_host = (const T*)a->nodes;
-    sp.geo.num_elements = work;
-    sp.geo.geo_mode = a->geo_mode;
+    fill_geometry<T>(a, work, &sp.geo);
     sp.v = (const T*)a->v;
     sp.state = (const T*)a->state;
     sp.u = (const T*)a->u;

@@ -16,10 +16,11 @@
 //                  - b (n : deps) n                   (the algorithmic tangent)
 //
 // plasticity_kernel is a sibling of elasticity_kernel (sfem_elasticity.h) and
-// hyperelastic_kernel (sfem_hyperelastic.h): the same lane mapping, derivative
-// stages, DIM x DIM x P register lines per lane, mass term, stores and
-// barriers.  Only the pointwise stage differs, per element and point with
-// Kw[a][j] = w detJ d xi_a / d x_j (ElemCof) and W = w detJ:
+// hyperelastic_kernel (sfem_hyperelastic.h) and is made of the same stages,
+// the SFEM_ELAST_* macros of sfem_elasticity.h: the same lane mapping,
+// derivative stages, DIM x DIM x P register lines per lane, mass term, stores
+// and barriers.  Only the pointwise stage is its own, per element and point,
+// with Kw[a][j] = w detJ d xi_a / d x_j (ElemCof) and W = w detJ:
 //
 //   MODE = PLAST_RESIDUAL, out = R(u):
 //     H = (1/W) Kw G,  the return mapping from hist_in (null: virgin)
@@ -98,25 +99,7 @@ plasticity_kernel(PlasticityParams<T> pp, DMat<T, P> dm) {
   // g[c][ax][a]: d u_c / d xi_ax at the lane's point of slice a, then the
   // folded stress (or its increment)
   T g[DIM][DIM][P];
-#pragma unroll
-  for (int c = 0; c < DIM; ++c) {
-    T ua[P];
-#pragma unroll
-    for (int a = 0; a < P; ++a)
-      ua[a] = active ? ue[(int64_t)(t + a * TPE) * DIM + c] : T(0);
-    line_apply<T, P, false>(dm, ua, g[c][0]);
-    SFEM_PAIR_SPREAD(ua);
-    __syncthreads();
-    SFEM_PAIR_LINES_DM(false);
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < P; ++a) {
-      const int o = a * SA + i * SB + j;
-      g[c][1][a] = lane_ok ? s0[o] : T(0);
-      if constexpr (DIM == 3) g[c][2][a] = lane_ok ? s1[o] : T(0);
-    }
-    __syncthreads();   // the next component overwrites the tensor pair
-  }
+  SFEM_ELAST_INTAKE();
 
   // pointwise: reference derivatives -> eps (or deps) -> sigma (or dsigma)
   // -> fold
@@ -141,15 +124,7 @@ plasticity_kernel(PlasticityParams<T> pp, DMat<T, P> dm) {
       const T mq = mue ? mue[q] : ep.mu_const;
       T H[DIM][DIM];
 #pragma unroll
-      for (int c = 0; c < DIM; ++c) {
-#pragma unroll
-        for (int jj = 0; jj < DIM; ++jj) {
-          T h = T(0);
-#pragma unroll
-          for (int ax = 0; ax < DIM; ++ax) h += K[ax * DIM + jj] * g[c][ax][a];
-          H[c][jj] = iw * h;
-        }
-      }
+      for (int c = 0; c < DIM; ++c) SFEM_ELAST_GRADIENT(c, a, iw, H);
       // the strain (or its increment) in the stored slots; 2D: eps_zz = 0
       T ev[NE];
       ev[0] = H[0][0];
@@ -284,71 +259,23 @@ plasticity_kernel(PlasticityParams<T> pp, DMat<T, P> dm) {
           S[0] = c == 0 ? sg[0] : sg[2];
           S[1] = c == 0 ? sg[2] : sg[1];
         }
-#pragma unroll
-        for (int ax = 0; ax < DIM; ++ax) {
-          T f = T(0);
-#pragma unroll
-          for (int jj = 0; jj < DIM; ++jj) f += K[ax * DIM + jj] * S[jj];
-          g[c][ax][a] = f;
-        }
+        SFEM_ELAST_FOLD(c, a, S);
       }
     }
   }
 
-  const bool mass = ep.lambda0 != T(0);
-#pragma unroll
-  for (int c = 0; c < DIM; ++c) {
-    if (lane_ok) {
-#pragma unroll
-      for (int a = 0; a < P; ++a) {
-        const int o = a * SA + i * SB + j;
-        s0[o] = g[c][1][a];
-        if constexpr (DIM == 3) s1[o] = g[c][2][a];
-      }
-    }
-    __syncthreads();
-    SFEM_PAIR_LINES_DM(true);   // the transposed derivatives, in place
-    T dt0[P];
-    line_apply<T, P, true>(dm, g[c][0], dt0);
-    __syncthreads();
-    if (active) {
-      const T* wd = ep.wdet + e * N;
-      const T* rhoe = ep.rho ? ep.rho + e * N : nullptr;
-#pragma unroll
-      for (int a = 0; a < P; ++a) {
-        const int o = a * SA + i * SB + j;
-        const int q = t + a * TPE;
-        T v = dt0[a] + s0[o];
-        if (DIM == 3) v += s1[o];
-        if (mass)
-          v += ep.lambda0 * (rhoe ? rhoe[q] : ep.rho_const) * wd[q] *
-               ue[(int64_t)q * DIM + c];
-        oe[(int64_t)q * DIM + c] = v;
-      }
-    }
-    __syncthreads();   // the next component overwrites the tensor pair
-  }
+  SFEM_ELAST_OUTPUT();
 }
 
 template <typename T, int P, int DIM>
 int launch_plasticity(const PlasticityParams<T>& pp, int mode,
                       hipStream_t stream) {
-  ElementLaunch<T, P> L;
-  if (int rc = element_launch<HelmholtzTile<T, P, DIM>>("plasticity",
-                                                        pp.el.geo, &L))
-    return rc;
-  with_geo_mode(pp.el.geo.geo_mode, [&](auto gm) {
-    if (mode == PLAST_TANGENT)
-      hipLaunchKernelGGL((plasticity_kernel<T, P, DIM, decltype(gm)::value,
-                                            PLAST_TANGENT>),
-                         L.grid, L.block, 0, stream, pp, L.dm);
-    else
-      hipLaunchKernelGGL((plasticity_kernel<T, P, DIM, decltype(gm)::value,
-                                            PLAST_RESIDUAL>),
-                         L.grid, L.block, 0, stream, pp, L.dm);
-  });
-  SFEM_LAUNCH_CHECK();
-  return SFEM_OK;
+  static_assert(PLAST_TANGENT == 1, "mode 1 of launch_two_mode");
+  return launch_two_mode<T, P, DIM>(
+      "plasticity", pp, mode, stream, [](auto gm, auto tangent) {
+        return plasticity_kernel<T, P, DIM, decltype(gm)::value,
+                                 decltype(tangent)::value>;
+      });
 }
 
 // Defined once per (dtype, ndim) translation unit, P = 2..12.

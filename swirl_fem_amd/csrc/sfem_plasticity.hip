@@ -40,26 +40,7 @@ int sfem_plasticity_local(const sfem_plasticity_args* a,
   return with_real(a->dtype, [&](auto zero) {
     using T = decltype(zero);
     PlasticityParams<T> pp{};
-    ElasticityParams<T>& ep = pp.el;
-    ep.geo.kfac = (const T*)a->kfac;
-    ep.geo.geo_elem = (const T*)a->geo_elem;
-    ep.geo.geo_index = a->geo_index;
-    ep.geo.elem_list = a->elem_list;
-    ep.geo.dmat_host = (const T*)a->dmat;
-    ep.geo.weights_host = (const T*)a->weights;
-    ep.geo.nodes_host = (const T*)a->nodes;
-    ep.geo.num_elements = work;
-    ep.geo.geo_mode = a->geo_mode;
-    ep.u = (const T*)a->u;
-    ep.out = (T*)a->out;
-    ep.wdet = (const T*)a->wdet;
-    ep.lam = (const T*)a->lam;
-    ep.mu = (const T*)a->mu;
-    ep.rho = (const T*)a->rho;
-    ep.lam_const = (T)a->lam_const;
-    ep.mu_const = (T)a->mu_const;
-    ep.rho_const = (T)a->rho_const;
-    ep.lambda0 = (T)a->lambda0;
+    fill_elasticity<T>(a, work, &pp.el);
     pp.yield = (const T*)a->yield;
     pp.hard = (const T*)a->hard;
     pp.yield_const = (T)a->yield_const;

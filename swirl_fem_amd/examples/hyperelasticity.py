@@ -28,28 +28,23 @@ gradients come from `sfem_hyperelastic_sens` on the state that launch stored.
 
 from __future__ import annotations
 
-import math
 from typing import Mapping, Tuple
 
 import torch
 
-from swirl_fem_amd.core.fespace import FiniteElementSpace
-from swirl_fem_amd.core.interpolation import NodeType
-from swirl_fem_amd.core.interpolation import Quadrature1D
 from swirl_fem_amd.core.mesh import Mesh
-from swirl_fem_amd.examples.elasticity import _boundary_data
 from swirl_fem_amd.examples.elasticity import _check_every
-from swirl_fem_amd.examples.elasticity import _check_mesh
+from swirl_fem_amd.examples.elasticity import _check_preconditioner
 from swirl_fem_amd.examples.elasticity import _detached
-from swirl_fem_amd.examples.elasticity import _load_vector
 from swirl_fem_amd.examples.elasticity import _requires_grad
+from swirl_fem_amd.examples.elasticity import _setup
 from swirl_fem_amd.examples.poisson import BCType
 from swirl_fem_amd.linalg.cg import cg
+# (the two constants stay importable from here)
+from swirl_fem_amd.linalg.newton import ARMIJO, LINE_SEARCH_HALVINGS
+from swirl_fem_amd.linalg.newton import newton_cg
 
 # pylint: disable=invalid-name
-
-LINE_SEARCH_HALVINGS = 10     # t = 1, 1/2, ..., 2^-10
-ARMIJO = 1e-4
 
 
 class _HyperelasticSolve(torch.autograd.Function):
@@ -177,14 +172,7 @@ def solve_hyperelasticity(mesh: Mesh, body_force,
 
   Partitioned meshes, ensembles, periodic images and ROBIN conditions are
   refused."""
-  if isinstance(preconditioner, str) and preconditioner == 'pmg':
-    raise NotImplementedError(
-        "preconditioner='pmg' for elasticity: the V-cycle of that name is "
-        'built for the scalar operator; pass preconditioner='
-        'linalg.pmg_elasticity.ElasticityPMultigrid (or any callable '
-        '(op, lambda0) -> M)')
-  if not callable(preconditioner) and preconditioner not in (None, 'jacobi'):
-    raise ValueError(f'unknown preconditioner {preconditioner!r}')
+  _check_preconditioner(preconditioner)
   if int(load_steps) != load_steps or load_steps < 1:
     raise ValueError(f'load_steps must be a positive integer, got '
                      f'{load_steps!r}')
@@ -222,56 +210,29 @@ def _solve(mesh: Mesh, body_force, boundary_conditions, *, lame_lambda,
   """The body of `solve_hyperelasticity`, its arguments checked.  `_state`: a
   dict that receives what the adjoint solve needs (the operator, the mask,
   the preconditioner, the final linearisation, the mass apply)."""
-  _check_mesh(mesh, 'solve_hyperelasticity')
-  d, N = mesh.ndim, mesh.num_nodes
-  dtype = mesh.dtype
-  lambda0 = float(lambda0)
   load_steps = int(load_steps)
-
-  fixed, u_D, tractions = _boundary_data(mesh, boundary_conditions)
-  has_fixed = bool(fixed.any())
-  singular = ValueError(
-      'lambda0 rho = 0 everywhere and no component of any node is fixed: the '
-      'rigid-body modes are not removed (the problem is singular)')
-  if lambda0 == 0.0 and not has_fixed:
-    raise singular
-
-  quadrature = Quadrature1D.create(
-      num_points=mesh.order + (d + 1) // 2,
-      quadrature_type=NodeType.GAUSS_LEGENDRE)
-  fespace = FiniteElementSpace.create(mesh, quadrature)
-  op = fespace.hyperelastic_operator(
-      fixed if has_fixed else None, lame_lambda=lame_lambda, lame_mu=lame_mu,
-      density=density)
-  if not has_fixed and bool((torch.as_tensor(op.rho) == 0).all()):
-    raise singular
-  f_ext = _load_vector(fespace, body_force, tractions)
-  keep = (~fixed).to(dtype)
-  f_ext = f_ext * keep
-
-  M = None
-  if preconditioner == 'jacobi':
-    from swirl_fem_amd.linalg.jacobi import JacobiPreconditioner
-    M = JacobiPreconditioner(op.linear.diagonal(lambda0).reshape(-1))
-  elif callable(preconditioner):
-    M = preconditioner(op.linear, lambda0)
-
-  if u0 is None:
-    u = torch.zeros((N, d), dtype=dtype, device=mesh.device)
-  else:
-    u = torch.as_tensor(u0, dtype=dtype, device=mesh.device)
-    if tuple(u.shape) != (N, d):
-      raise ValueError(f'u0: shape {tuple(u.shape)}; expected ({N}, {d})')
-    u = u.clone()
+  st = _setup(
+      'solve_hyperelasticity', mesh, body_force, boundary_conditions, lambda0,
+      preconditioner,
+      lambda fespace, mask: fespace.hyperelastic_operator(
+          mask, lame_lambda=lame_lambda, lame_mu=lame_mu, density=density),
+      linear=lambda op: op.linear, u0=u0)
+  op, fespace, keep, M, u = st.op, st.fespace, st.keep, st.M, st.u
+  lambda0 = st.lambda0
+  f_ext = st.load * keep
 
   steps = []
   for k in range(1, load_steps + 1):
     scale = k / load_steps
-    u = torch.where(fixed, scale * u_D, u)
+    u = torch.where(st.fixed, scale * st.u_D, u)
     rec = dict(residual_norms=[], step_lengths=[], cg_iterations=[],
                status='running')
     steps.append(rec)
-    where = lambda it: f'load step {k} of {load_steps}, Newton iteration {it}'
+
+    def where(it, note=None):
+      step = f'load step {k} of {load_steps}'
+      return (f'{step} ({note})' if it is None
+              else f'{step}, Newton iteration {it}')
 
     def evaluate(v):
       """(linearisation at v, r = keep (R(v) - scale f_ext), |r|)."""
@@ -279,50 +240,14 @@ def _solve(mesh: Mesh, body_force, boundary_conditions, *, lame_lambda,
       r = lin.residual - scale * f_ext
       return lin, r, float(torch.linalg.vector_norm(r))
 
-    lin, r, rnorm = evaluate(u)
-    if not math.isfinite(rnorm):
-      raise RuntimeError(
-          f'solve_hyperelasticity: the residual is not finite at the start '
-          f'of {where(0)} (an inverted element: more load steps may help)')
-    rec['residual_norms'].append(rnorm)
-    target = max(newton_rtol * rnorm, newton_atol)
-    it = 0
-    while rnorm > target:
-      if it == max_newton:
-        rec['status'] = 'max_newton'
-        raise RuntimeError(
-            f'solve_hyperelasticity: no convergence within max_newton = '
-            f'{max_newton} iterations in load step {k} of {load_steps} '
-            f'(|r| = {rnorm:.3e}, target {target:.3e})')
-      it += 1
-      T = op.tangent(lin, lambda0)
-      A = lambda x: T.apply(x.view(N, d)).reshape(-1)
-      dw, cg_info = cg(A, (-r).reshape(-1).contiguous(), tol=linear_rtol,
-                       M=M, check_every=_check_every(M))
-      rec['cg_iterations'].append(int(cg_info['num_iterations']))
-      if str(cg_info['status']).startswith('breakdown'):
-        rec['status'] = 'cg_' + cg_info['status']
-        raise RuntimeError(
-            f'solve_hyperelasticity: CG broke down ({cg_info["status"]}; the '
-            f'tangent may have lost definiteness) in {where(it)}')
-      dw = dw.view(N, d)
-      t, accepted = 1.0, False
-      for _ in range(LINE_SEARCH_HALVINGS + 1):
-        lin_t, r_t, n_t = evaluate(u + t * dw)
-        if math.isfinite(n_t) and n_t <= (1.0 - ARMIJO * t) * rnorm:
-          accepted = True
-          break
-        t *= 0.5
-      if not accepted:
-        rec['status'] = 'line_search'
-        raise RuntimeError(
-            f'solve_hyperelasticity: line search exhausted (t down to '
-            f'2^-{LINE_SEARCH_HALVINGS}) in {where(it)}, |r| = {rnorm:.3e}')
-      u = u + t * dw
-      lin, r, rnorm = lin_t, r_t, n_t
-      rec['step_lengths'].append(t)
-      rec['residual_norms'].append(rnorm)
-    rec['status'] = 'converged'
+    u, lin, _ = newton_cg(
+        evaluate, lambda lin: op.tangent(lin, lambda0).apply, u, M,
+        newton_rtol=newton_rtol, newton_atol=newton_atol,
+        max_newton=max_newton, linear_rtol=linear_rtol,
+        who='solve_hyperelasticity', where=where,
+        breakdown_hint='the tangent may have lost definiteness',
+        nonfinite_hint=' (an inverted element: more load steps may help)',
+        check_every=_check_every(M), rec=rec)
   if _state is not None:
     _state.update(op=op, keep=keep, M=M, lambda0=lambda0, lin=lin,
                   Bf=lambda x: fespace.helmholtz_operator(None).apply(

@@ -38,19 +38,13 @@ from typing import Mapping, Tuple
 
 import torch
 
-from swirl_fem_amd.core.fespace import FiniteElementSpace
-from swirl_fem_amd.core.interpolation import NodeType
-from swirl_fem_amd.core.interpolation import Quadrature1D
 from swirl_fem_amd.core.mesh import Mesh
-from swirl_fem_amd.examples.elasticity import _boundary_data
 from swirl_fem_amd.examples.elasticity import _check_every
-from swirl_fem_amd.examples.elasticity import _check_mesh
-from swirl_fem_amd.examples.elasticity import _load_vector
+from swirl_fem_amd.examples.elasticity import _check_preconditioner
 from swirl_fem_amd.examples.elasticity import _requires_grad
-from swirl_fem_amd.examples.hyperelasticity import ARMIJO
-from swirl_fem_amd.examples.hyperelasticity import LINE_SEARCH_HALVINGS
+from swirl_fem_amd.examples.elasticity import _setup
 from swirl_fem_amd.examples.poisson import BCType
-from swirl_fem_amd.linalg.cg import cg
+from swirl_fem_amd.linalg.newton import newton_cg
 
 # pylint: disable=invalid-name
 
@@ -126,14 +120,7 @@ def solve_plasticity(mesh: Mesh, body_force,
   Partitioned meshes, ensembles, periodic images, ROBIN conditions and inputs
   that require grad are refused; 2D is plane strain."""
   who = 'solve_plasticity'
-  if isinstance(preconditioner, str) and preconditioner == 'pmg':
-    raise NotImplementedError(
-        "preconditioner='pmg' for elasticity: the V-cycle of that name is "
-        'built for the scalar operator; pass preconditioner='
-        'linalg.pmg_elasticity.ElasticityPMultigrid (or any callable '
-        '(op, lambda0) -> M)')
-  if not callable(preconditioner) and preconditioner not in (None, 'jacobi'):
-    raise ValueError(f'unknown preconditioner {preconditioner!r}')
+  _check_preconditioner(preconditioner)
   path = _load_path(load_factors)
   if max_newton < 1:
     raise ValueError(f'max_newton must be at least 1, got {max_newton!r}')
@@ -142,51 +129,20 @@ def solve_plasticity(mesh: Mesh, body_force,
     raise NotImplementedError(
         f'autograd through {who}: the solve depends on the load path and is '
         'not differentiated; pass detached inputs')
-  _check_mesh(mesh, who)
-  d, N = mesh.ndim, mesh.num_nodes
-  dtype = mesh.dtype
-  lambda0 = float(lambda0)
-
-  fixed, u_D, tractions = _boundary_data(mesh, boundary_conditions)
-  has_fixed = bool(fixed.any())
-  singular = ValueError(
-      'lambda0 rho = 0 everywhere and no component of any node is fixed: the '
-      'rigid-body modes are not removed (the problem is singular)')
-  if lambda0 == 0.0 and not has_fixed:
-    raise singular
-
-  quadrature = Quadrature1D.create(
-      num_points=mesh.order + (d + 1) // 2,
-      quadrature_type=NodeType.GAUSS_LEGENDRE)
-  fespace = FiniteElementSpace.create(mesh, quadrature)
-  op = fespace.plasticity_operator(
-      fixed if has_fixed else None, lame_lambda=lame_lambda, lame_mu=lame_mu,
-      yield_stress=yield_stress, hardening_modulus=hardening_modulus,
-      density=density)
-  if not has_fixed and bool((torch.as_tensor(op.rho) == 0).all()):
-    raise singular
-  f_ext = _load_vector(fespace, body_force, tractions)
-  keep = (~fixed).to(dtype)
-  f_ext = f_ext * keep
-
-  M = None
-  if preconditioner == 'jacobi':
-    from swirl_fem_amd.linalg.jacobi import JacobiPreconditioner
-    M = JacobiPreconditioner(op.linear.diagonal(lambda0).reshape(-1))
-  elif callable(preconditioner):
-    M = preconditioner(op.linear, lambda0)
-
-  if u0 is None:
-    u = torch.zeros((N, d), dtype=dtype, device=mesh.device)
-  else:
-    u = torch.as_tensor(u0, dtype=dtype, device=mesh.device)
-    if tuple(u.shape) != (N, d):
-      raise ValueError(f'u0: shape {tuple(u.shape)}; expected ({N}, {d})')
-    u = u.clone()
+  st = _setup(
+      who, mesh, body_force, boundary_conditions, lambda0, preconditioner,
+      lambda fespace, mask: fespace.plasticity_operator(
+          mask, lame_lambda=lame_lambda, lame_mu=lame_mu,
+          yield_stress=yield_stress, hardening_modulus=hardening_modulus,
+          density=density),
+      linear=lambda op: op.linear, u0=u0)
+  op, M, u, lambda0 = st.op, st.M, st.u, st.lambda0
+  f_ext = st.load * st.keep
   if history is None:
     committed = op.virgin_history()
   else:
-    committed = torch.as_tensor(history, dtype=dtype, device=mesh.device)
+    committed = torch.as_tensor(history, dtype=mesh.dtype,
+                                device=mesh.device)
     if tuple(committed.shape) != op.history_shape():
       raise ValueError(f'history: shape {tuple(committed.shape)}; expected '
                        f'{op.history_shape()}')
@@ -194,12 +150,15 @@ def solve_plasticity(mesh: Mesh, body_force,
 
   entries = []
   for k, scale in enumerate(path, start=1):
-    u = torch.where(fixed, scale * u_D, u)
+    u = torch.where(st.fixed, scale * st.u_D, u)
     rec = dict(factor=scale, residual_norms=[], step_lengths=[],
                cg_iterations=[], plastic_points=0, status='running')
     entries.append(rec)
-    where = lambda it: (f'entry {k} of {len(path)} of the load path (factor '
-                        f'{scale:g}), Newton iteration {it}')
+
+    def where(it, note=None):
+      entry = f'entry {k} of {len(path)} of the load path'
+      return (f'{entry} (factor {scale:g}, {note})' if it is None
+              else f'{entry} (factor {scale:g}), Newton iteration {it}')
 
     def evaluate(v):
       """(linearisation at v from the committed history, r = keep (R(v) -
@@ -208,53 +167,16 @@ def solve_plasticity(mesh: Mesh, body_force,
       r = lin.residual - scale * f_ext
       return lin, r, float(torch.linalg.vector_norm(r))
 
-    lin, r, rnorm = evaluate(u)
-    if not math.isfinite(rnorm):
-      raise RuntimeError(f'{who}: the residual is not finite at the start of '
-                         f'{where(0)}')
-    rec['residual_norms'].append(rnorm)
-    target = max(newton_rtol * rnorm, newton_atol)
-    it = 0
-    while rnorm > target:
-      if it == max_newton:
-        rec['status'] = 'max_newton'
-        raise RuntimeError(
-            f'{who}: no convergence within max_newton = {max_newton} '
-            f'iterations in entry {k} of {len(path)} of the load path '
-            f'(factor {scale:g}, |r| = {rnorm:.3e}, target {target:.3e})')
-      it += 1
-      T = op.tangent(lin, lambda0)
-      A = lambda x: T.apply(x.view(N, d)).reshape(-1)
-      dw, cg_info = cg(A, (-r).reshape(-1).contiguous(), tol=linear_rtol,
-                       M=M, check_every=_check_every(M))
-      rec['cg_iterations'].append(int(cg_info['num_iterations']))
-      if str(cg_info['status']).startswith('breakdown'):
-        rec['status'] = 'cg_' + cg_info['status']
-        raise RuntimeError(
-            f'{who}: CG broke down ({cg_info["status"]}; without hardening '
-            f'the tangent is only semi-definite at a limit load) in '
-            f'{where(it)}')
-      dw = dw.view(N, d)
-      t, accepted = 1.0, False
-      for _ in range(LINE_SEARCH_HALVINGS + 1):
-        lin_t, r_t, n_t = evaluate(u + t * dw)
-        if math.isfinite(n_t) and n_t <= (1.0 - ARMIJO * t) * rnorm:
-          accepted = True
-          break
-        t *= 0.5
-      if not accepted:
-        rec['status'] = 'line_search'
-        raise RuntimeError(
-            f'{who}: line search exhausted (t down to '
-            f'2^-{LINE_SEARCH_HALVINGS}) in {where(it)}, |r| = {rnorm:.3e}')
-      u = u + t * dw
-      lin, r, rnorm = lin_t, r_t, n_t
-      rec['step_lengths'].append(t)
-      rec['residual_norms'].append(rnorm)
+    u, lin, _ = newton_cg(
+        evaluate, lambda lin: op.tangent(lin, lambda0).apply, u, M,
+        newton_rtol=newton_rtol, newton_atol=newton_atol,
+        max_newton=max_newton, linear_rtol=linear_rtol, who=who, where=where,
+        breakdown_hint=('without hardening the tangent is only semi-definite '
+                        'at a limit load'),
+        check_every=_check_every(M), rec=rec)
     # the accepted state's launch already formed its history: commit it
     committed = lin.history
     rec['plastic_points'] = lin.num_plastic()
-    rec['status'] = 'converged'
   if return_info:
     return u, committed, {
         'load_path': entries, 'status': 'converged',
