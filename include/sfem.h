@@ -1014,6 +1014,84 @@ typedef struct sfem_plasticity_args {
 int sfem_plasticity_local(const sfem_plasticity_args* args,
                           sfem_stream_t stream);
 
+/* ---------------------------- vector-Jacobian product of the radial return ---
+ * The point map of sfem_plasticity_local is (eps, eps_p, alpha; lam, mu,
+ * sigma_y, Hh) -> (sigma, eps_p', alpha').  With cotangents S of sigma, Pb of
+ * eps_p' (symmetric 3 x 3) and ab of alpha', r32 = sqrt(3/2), e = eps - eps_p,
+ * s = 2 mu dev(e), sn = |s|, n = s / sn, f = r32 sn - sigma_y - Hh alpha,
+ * c = 1 / (3 mu + Hh), dg = c f:
+ *
+ *   common:   eps_b = lam tr(S) I + 2 mu S;  lam_b = tr(eps) tr(S);
+ *             Z = Pb - 2 mu S
+ *   f <= 0:   epsp_b = Z;  alpha_b = ab;  mu_b = 2 (eps - eps_p) : S;
+ *             sy_b = Hh_b = 0
+ *   f >  0:   mu_b   = 2 (eps - eps_p') : S
+ *             dg_b   = ab + r32 (n : Z);      n_b = r32 dg Z
+ *             f_b    = c dg_b;   mu_b -= 3 c dg dg_b
+ *             Hh_b   = -c dg dg_b - alpha f_b
+ *             sy_b   = -f_b;     alpha_b = ab - Hh f_b
+ *             s_b    = (n_b - (n : n_b) n) / sn + r32 f_b n
+ *             e_b    = 2 mu dev(s_b);   mu_b += (s : s_b) / mu
+ *             eps_b += e_b;   epsp_b = Z - e_b
+ *
+ * Cotangents of histories refer to the stored (E, n, NH) arrays: Pb_xy =
+ * hbar[xy] / 2 on input and hbar_prev[xy] = 2 epsp_b_xy on output (a stored
+ * off-diagonal slot stands for two tensor entries); in 2D Pb_zz = 0 and
+ * hbar_prev[xx] = epsp_b_xx - epsp_b_zz, likewise yy (eps_p,zz = -(xx + yy)
+ * is implied).  The launch repeats the return mapping from `u` on the grid
+ * and `hist_in` (NULL: virgin); it reads no output of a forward launch.
+ *
+ * mode = SFEM_PLAST_VJP_DISPLACEMENT: `out` (E, n, ndim) = d(hbar . Phi)/du,
+ * Phi the history update hist_in -> (eps_p', alpha'): the point VJP with
+ * S = 0, eps_b / W folded through the cofactors and the transposed
+ * derivatives as the stress of the residual is (no quadrature weight).
+ * Needs u, hbar, out; w, hbar_prev and the five d* must be NULL.
+ *
+ * mode = SFEM_PLAST_VJP_STATE: for a second field `w` (E, n, ndim), the point
+ * VJP with S = W sym(H_w), Pb and ab from `hbar` (NULL: zero).  Each where
+ * non-NULL: `hbar_prev` (E, n, NH) the cotangent of hist_in, `dlam`, `dmu`,
+ * `dyield`, `dhard` (E, n) the derivatives of w . R(u) + hbar . Phi(u) by the
+ * point's coefficients, `drho` (E, n) = lambda0 W u . w.  Needs u, w and one
+ * output; `out` must be NULL.  hbar_prev must be neither hist_in nor hbar.
+ *
+ * A point with W = 0 stores exact zeros in every output.  The coefficient,
+ * geometry and launch arguments are those of sfem_plasticity_args; the return
+ * codes follow sfem_plasticity_local.  ABI version 10 (a pure addition).     */
+#define SFEM_PLAST_VJP_DISPLACEMENT 0
+#define SFEM_PLAST_VJP_STATE 1
+typedef struct sfem_plasticity_vjp_args {
+  const void* u;          /* (E, n, ndim): displacement                       */
+  const void* w;          /* (E, n, ndim): second field; state mode           */
+  const void* wdet;       /* (E, n)                                           */
+  const void* lam;        /* (E, n) or NULL                                   */
+  const void* mu;         /* (E, n) or NULL                                   */
+  const void* yield;      /* (E, n) or NULL                                   */
+  const void* hard;       /* (E, n) or NULL                                   */
+  double lam_const, mu_const, yield_const, hard_const, lambda0;
+  const void* hist_in;    /* (E, n, NH) or NULL = virgin                      */
+  const void* hbar;       /* (E, n, NH); NULL = zero in the state mode        */
+  void* out;              /* (E, n, ndim); displacement mode                  */
+  void* hbar_prev;        /* (E, n, NH) or NULL; state mode, as the five below*/
+  void* dlam;             /* (E, n) or NULL                                   */
+  void* dmu;
+  void* dyield;
+  void* dhard;
+  void* drho;
+  const void* kfac;       /* per-point weighted cofactors or NULL             */
+  const void* geo_elem;   /* (E, 24) or NULL                                  */
+  const int32_t* geo_index; /* (E,) slot of element e in kfac, or NULL = e    */
+  const int32_t* elem_list; /* element ids of this launch, or NULL = all      */
+  const void* dmat;       /* HOST (P, P)                                      */
+  const void* weights;    /* HOST (P,)                                        */
+  const void* nodes;      /* HOST (P,)                                        */
+  int64_t num_elements;
+  int64_t num_listed;
+  int32_t ndim, P, dtype, geo_mode;
+  int32_t mode;           /* SFEM_PLAST_VJP_DISPLACEMENT / SFEM_PLAST_VJP_STATE */
+} sfem_plasticity_vjp_args;
+int sfem_plasticity_vjp(const sfem_plasticity_vjp_args* args,
+                        sfem_stream_t stream);
+
 /* ------------------------------------- fields at points: locate, eval, eval^T ---
  * A field of order P1 - 1 on element e is u(xi) = sum_n u[elements[e, n]]
  * l_n(xi) with l_n the tensor product of the 1D Lagrange polynomials on

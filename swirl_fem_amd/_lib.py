@@ -230,6 +230,25 @@ class PlasticityArgs(ctypes.Structure):
   ]
 
 
+SFEM_PLAST_VJP_DISPLACEMENT, SFEM_PLAST_VJP_STATE = 0, 1
+
+
+class PlasticityVjpArgs(ctypes.Structure):
+  """Mirror of `struct sfem_plasticity_vjp_args`."""
+  _fields_ = [
+      ('u', c_ptr), ('w', c_ptr), ('wdet', c_ptr), ('lam', c_ptr),
+      ('mu', c_ptr), ('yield', c_ptr), ('hard', c_ptr), ('lam_const', c_dbl),
+      ('mu_const', c_dbl), ('yield_const', c_dbl), ('hard_const', c_dbl),
+      ('lambda0', c_dbl), ('hist_in', c_ptr), ('hbar', c_ptr), ('out', c_ptr),
+      ('hbar_prev', c_ptr), ('dlam', c_ptr), ('dmu', c_ptr),
+      ('dyield', c_ptr), ('dhard', c_ptr), ('drho', c_ptr), ('kfac', c_ptr),
+      ('geo_elem', c_ptr), ('geo_index', c_ptr), ('elem_list', c_ptr),
+      ('dmat', c_ptr), ('weights', c_ptr), ('nodes', c_ptr),
+      ('num_elements', c_i64), ('num_listed', c_i64), ('ndim', c_i32),
+      ('P', c_i32), ('dtype', c_i32), ('geo_mode', c_i32), ('mode', c_i32),
+  ]
+
+
 SFEM_POINT_CHUNK = 64
 
 
@@ -397,6 +416,7 @@ SIGNATURES = {
     'sfem_hyperelastic_local': [ctypes.POINTER(HyperelasticArgs), c_ptr],
     'sfem_hyperelastic_sens': [ctypes.POINTER(HyperelasticSensArgs), c_ptr],
     'sfem_plasticity_local': [ctypes.POINTER(PlasticityArgs), c_ptr],
+    'sfem_plasticity_vjp': [ctypes.POINTER(PlasticityVjpArgs), c_ptr],
     'sfem_point_locate': [ctypes.POINTER(PointLocateArgs), c_ptr],
     'sfem_point_eval': [ctypes.POINTER(PointArgs), c_ptr],
     'sfem_point_eval_t': [ctypes.POINTER(PointArgs), c_ptr],

@@ -1488,6 +1488,72 @@ def plasticity_local(u_q, parts, host, ndim, P, wdet, lam, mu, rho, lambda0,
   return out if tangent else (out, hist_out, lin, stress)
 
 
+def plasticity_vjp(u_q, parts, host, ndim, P, wdet, lam, mu, yield_stress,
+                   hardening, *, mode, hist=None, hbar=None, w_q=None,
+                   lambda0=0.0, want=(True,) * 5, want_history=True):
+  """The vector-Jacobian product of the radial return on a collocated grid
+  (`sfem_plasticity_vjp`): `u_q` (E, P^d, d) the displacement, `hist` the
+  committed history (E, P^d, NH) or None for virgin material, `hbar` the
+  cotangent of the trial history (eps_p', alpha') in the stored layout;
+  `wdet` and the coefficients as in `plasticity_local`.  The return mapping
+  is repeated from `u_q` and `hist`; nothing is written to an input.
+
+  `mode='displacement'`: returns d(hbar . Phi)/du (E, P^d, d) for the history
+  update Phi; `hbar` is required.  `mode='state'`: for the second field `w_q`
+  (E, P^d, d) returns (hbar_prev (E, P^d, NH), dlam, dmu, dyield, dhard, drho
+  (E, P^d) each): the derivatives of w . R(u) + hbar . Phi(u) (`hbar` None =
+  0) by the committed history and the point's coefficients, drho = lambda0 W
+  u . w; `hbar_prev` is None unless `want_history`, the others where `want`
+  is false.  Rows of elements that no part lists are zero."""
+  if mode not in ('displacement', 'state'):
+    raise ValueError(f"mode: 'displacement' or 'state', got {mode!r}")
+  state = mode == 'state'
+  u_q = u_q.contiguous()
+  dev = _dev(u_q)
+  E, n, d = _local_shape(u_q, ndim, P, wdet, 'plasticity_vjp')
+  NH = plasticity_sizes(ndim)[0]
+  want = tuple(bool(w) for w in want)
+  if len(want) != 5:
+    raise ValueError('`want` names (dlam, dmu, dyield, dhard, drho)')
+  tensors = []
+  field = lambda t, name: _field(t, name, (E, n), u_q, 'displacement', tensors)
+  hist = _field(hist, 'hist', (E, n, NH), u_q, 'displacement', tensors)
+  hbar = _field(hbar, 'hbar', (E, n, NH), u_q, 'displacement', tensors)
+  w_q = _field(w_q, 'second field', (E, n, d), u_q, 'displacement', tensors)
+  args = _lib.PlasticityVjpArgs(
+      u=u_q.data_ptr(), w=_dptr(w_q), lambda0=float(lambda0),
+      wdet=field(wdet, 'wdet').data_ptr(), hist_in=_dptr(hist),
+      hbar=_dptr(hbar),
+      mode=(_lib.SFEM_PLAST_VJP_STATE if state
+            else _lib.SFEM_PLAST_VJP_DISPLACEMENT))
+  _coefficients(args, field, (
+      ('lam', 'lam_const', lam), ('mu', 'mu_const', mu),
+      ('yield', 'yield_const', yield_stress),
+      ('hard', 'hard_const', hardening)))
+  if not state:
+    if hbar is None:
+      raise ValueError('the displacement mode needs the cotangent `hbar`')
+    if w_q is not None:
+      raise ValueError('`w_q` is an input of the state mode only')
+    out = torch.empty_like(u_q)
+    args.out = out.data_ptr()
+    _launch_parts('sfem_plasticity_vjp', args, u_q, E, ndim, P, parts, host)
+    return out
+  if w_q is None:
+    raise ValueError('the state mode needs the second field `w_q`')
+  if not (any(want) or want_history):
+    raise ValueError('the state mode needs an output: `want` or '
+                     '`want_history`')
+  zeros = lambda *k: torch.zeros((E, n) + k, dtype=u_q.dtype, device=dev)
+  hbar_prev = zeros(NH) if want_history else None
+  outs = tuple(zeros() if w else None for w in want)
+  args.hbar_prev = _dptr(hbar_prev)
+  for name, t in zip(('dlam', 'dmu', 'dyield', 'dhard', 'drho'), outs):
+    setattr(args, name, _dptr(t))
+  _launch_parts('sfem_plasticity_vjp', args, u_q, E, ndim, P, parts, host)
+  return (hbar_prev,) + outs
+
+
 def elasticity_sens(u_q, v_q, parts, host, ndim, P, wdet, lambda0=0.0,
                     want=(True, True, True)):
   """Per-point sensitivities of v . (K + lambda0 M_rho) u with respect to

@@ -2847,6 +2847,9 @@ class PlasticityOperator(_OnLinearElasticity):
   linear: ElasticityOperator
   yield_stress: object
   hardening: object
+  # (yield_stress, hardening_modulus) as the caller passed them: `sensitivity`
+  # returns its gradients in these forms
+  plastic_source: tuple = (None, None)
 
   @classmethod
   def create(cls, fespace, dirichlet_mask=None, *, lame_lambda, lame_mu,
@@ -2859,7 +2862,8 @@ class PlasticityOperator(_OnLinearElasticity):
                yield_stress=_elastic_coefficient(fespace, yield_stress,
                                                  'yield_stress', True),
                hardening=_elastic_coefficient(fespace, hardening_modulus,
-                                              'hardening_modulus', False))
+                                              'hardening_modulus', False),
+               plastic_source=(yield_stress, hardening_modulus))
 
   def history_shape(self):
     mesh = self.fespace.mesh
@@ -2927,3 +2931,80 @@ class PlasticityOperator(_OnLinearElasticity):
     _, hist, _, sigma = self._launch(self._nodal(u), history, 0.0,
                                      want_hist=True, want_stress=True)
     return sigma, hist
+
+  # ----------------------------------------------------------------- adjoint
+  def _cotangent(self, hbar):
+    if hbar is None:
+      return None
+    if tuple(hbar.shape) != self.history_shape():
+      raise ValueError(f'hbar: expected {self.history_shape()}, got '
+                       f'{tuple(hbar.shape)}')
+    return hbar.detach().to(self.fespace.dtype).contiguous()
+
+  def _vjp_args(self):
+    fes = self.fespace
+    return (self.parts, self.host, fes.mesh.ndim, fes.quadrature.num_points,
+            self.point_weights(), self.lam, self.mu, self.yield_stress,
+            self.hardening)
+
+  def history_vjp(self, u, history, hbar):
+    """mask * d(hbar . Phi)/du (N, d) in the layout of `u`, for the history
+    update Phi: (u, committed `history`) -> trial history and a cotangent
+    `hbar` (E, Q^d, NH) of the trial history.  Interpolation
+    to the quadrature grid, one displacement-mode launch of
+    `sfem_plasticity_vjp` per part, transposed interpolation and scatter, as
+    in `residual`.  The return mapping is repeated from `u` and `history`
+    (None: virgin material)."""
+    if hbar is None:
+      raise ValueError('history_vjp needs the cotangent `hbar`')
+    hbar = self._cotangent(hbar)
+    hist = self._history(history)
+
+    def local(v):
+      return self.fespace._interpolate_t(_ops.plasticity_vjp(
+          self._to_grid(v), *self._vjp_args(), mode='displacement', hist=hist,
+          hbar=hbar))
+    return self._assembled(u, local)
+
+  def sensitivity(self, u, w, history=None, hbar=None, lambda0=0.0,
+                  want=(True, True, True, True, True), want_history=True):
+    """((d/dlame_lambda, d/dlame_mu, d/dyield_stress, d/dhardening_modulus,
+    d/ddensity), hbar_prev): the gradient of w . R(u; history) + hbar .
+    Phi(u; history) WITHOUT the Dirichlet mask, Phi the history update, with
+    respect to the coefficients and to the committed `history` (None: virgin;
+    `hbar` None: zero).  Each coefficient gradient comes in the form the
+    caller passed to `create` (`reduce_coefficient_gradient`): a scalar gives
+    a 0-dim tensor (the sum over all points), (E,) the sum over each
+    element's points, (E, Q^d) per-point values; None for a callable, for an
+    absent density and where `want` is false.  `hbar_prev` (E, Q^d, NH) is
+    None unless `want_history`.  `u`, `w`: nodal (N, d), dense or component-
+    major; both are gathered and interpolated to the quadrature grid, then
+    one state-mode launch of `sfem_plasticity_vjp` per part repeats the
+    return mapping and forms the point VJP with S = W sym(grad w) (DESIGN
+    §3.23).  Nothing of size (E, Q^d, d, d) is stored."""
+    fes = self.fespace
+    mesh = fes.mesh
+    d = mesh.ndim
+    for x in (u, w):
+      if tuple(x.shape) != (mesh.num_nodes, d):
+        raise ValueError(f'expected ({mesh.num_nodes}, {d}) nodal '
+                         f'displacements, got {tuple(x.shape)}')
+    if len(tuple(want)) != 5:
+      raise ValueError('`want` names (lame_lambda, lame_mu, yield_stress, '
+                       'hardening_modulus, density)')
+    lam_s, mu_s, rho_s = self.linear.coef_source
+    source = (lam_s, mu_s) + tuple(self.plastic_source) + (rho_s,)
+    tensor = lambda s: s is not None and not _is_callable_source(s)
+    wanted = tuple(bool(k) and tensor(s) for k, s in zip(want, source))
+    if not (any(wanted) or want_history):
+      return (None,) * 5, None
+    hbar = self._cotangent(hbar)
+    hist = self._history(history)
+    grid = lambda x: fes._interpolate(_ops.gather_rows(
+        x.detach().to(fes.dtype).contiguous(), mesh.elements)).contiguous()
+    out = _ops.plasticity_vjp(
+        grid(u), *self._vjp_args(), mode='state', hist=hist, hbar=hbar,
+        w_q=grid(w), lambda0=lambda0, want=wanted,
+        want_history=bool(want_history))
+    return (tuple(reduce_coefficient_gradient(g, s)
+                  for g, s in zip(out[1:], source)), out[0])
